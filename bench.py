@@ -12,6 +12,10 @@ backward, RCCL bucketed all-reduce (N>1), global-norm clip, AdamW update.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29511 bench.py --gpus 8 --steps 20 --warmup 5
 
+``--dump-outputs DIR`` writes what the last timed step left (loss, gradient norm, a seeded sample of gradients and
+weights) as ``DIR/<name>.npy``; the inputs depend on the arguments only, so two builds compare output for output.
+``--full`` is where measurements and checks beside the headline figure belong; a plain run does none.
+
 Weak scaling: the per-GPU micro-batch is fixed, global batch = N * micro-batch.
 Rank 0 prints one JSON line; the time is the MAX over ranks of K steps
 bracketed by barrier + device synchronize.
@@ -61,6 +65,36 @@ def load_gemm_tuning(spec: str, model: str, batch: int, seq: int) -> str | None:
     return os.path.basename(path)
 
 
+DUMP_SAMPLE = 1 << 21  # elements kept of each flat buffer: 8 MB per array as float32
+
+
+def dump_outputs(directory: str, engine, loss: torch.Tensor | None) -> None:
+    """Write what the last timed step left to ``directory/<name>.npy`` (float32), for output-by-output comparison
+    of two builds run with the same arguments: the loss it returned, the gradient norm it clipped by, and the same
+    seeded sample (sorted indices into the flat buffers) of its gradients, of the weights the model now holds and
+    -- where every rank keeps all of them -- of the fp32 master weights."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    engine.sync_params()
+    n = engine.flat.numel
+    idx = np.arange(n) if n <= DUMP_SAMPLE else np.unique(np.random.RandomState(20240607).randint(0, n, DUMP_SAMPLE))
+    idx_t = torch.from_numpy(idx.astype(np.int64)).to(engine.flat.data.device)
+
+    def sample(t: torch.Tensor):
+        return t.detach()[idx_t].float().cpu().numpy()
+
+    arrays = {"grad_sample": sample(engine.flat.grad), "weight_sample": sample(engine.flat.data)}
+    if not engine.zero and engine.opt.master is not engine.flat.data:
+        arrays["master_weight_sample"] = sample(engine.opt.master)
+    if loss is not None:
+        arrays["loss"] = loss.detach().float().cpu().numpy().reshape(1)
+    if engine.last_grad_norm is not None:
+        arrays["grad_norm"] = engine.last_grad_norm.detach().float().cpu().numpy().reshape(1)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -94,6 +128,14 @@ def main() -> int:
     ap.add_argument("--device", choices=["cuda", "cpu"], default="cuda",
                     help="cpu = the plumbing config path (fp32, no HIP kernels), e.g. --model tinystories-17m --seq 256")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one left as DIR/<name>.npy (float32): the loss, "
+                         "the gradient norm, and a fixed seeded sample of the gradients and of the updated weights")
+    ap.add_argument("--full", action="store_true",
+                    help="also run whatever the benchmark measures or checks beside the headline figure; a plain "
+                         "run only sets up, warms up, times --steps steps and prints the result line (every figure "
+                         "of today's result line already comes out of the timed steps themselves, so nothing is "
+                         "behind this switch yet)")
     ap.add_argument("--no-dp-check", action="store_true",
                     help="N>1: skip the untimed replica-consistency step after warmup (default: run it)")
     ap.add_argument("--debug-corrupt-rank", type=int, default=-1,
@@ -174,6 +216,10 @@ def main() -> int:
     dt = all_reduce_max(dt, dev)
     phases = {k: round(all_reduce_max(v, dev), 3) for k, v in sorted(engine.phase_times().items())}
     loss_v = float(loss.item()) if loss is not None else float("nan")
+    if args.dump_outputs:
+        engine.sync_params()  # every rank: sharded data parallelism still has weight all-gathers in flight
+        if info.is_main:
+            dump_outputs(args.dump_outputs, engine, loss)
 
     n = info.world_size
     tokens = args.steps * args.batch * args.seq * n

@@ -41,6 +41,10 @@ already full, so the two streams only compete for the same CUs.)
 
 Without ``main_grad`` (e.g. a plain module, tests) the same function returns
 ordinary per-parameter gradients.
+
+Document masking: ``doc_bounds`` (the int32 ``(doc_start, doc_end)`` pair of ``ops.doc_bounds``) travels in ``meta``
+(integer tensors, no gradient); attention then runs ``fa_fwd_doc`` / ``fa_bwd_doc`` on the pre-rotated QKV activation
+(bf16 and fp8 blocks alike: the QKV GEMMs' RoPE epilogues are untouched, positions stay ``0..S-1``).
 """
 
 from __future__ import annotations
@@ -147,6 +151,7 @@ class FusedBlockFn(torch.autograd.Function):
         # gradients) or None
         fp8 = meta[7]
         train = meta[8]  # a backward will run (decided by the caller: grad mode is off inside forward)
+        doc = meta[9] if len(meta) > 9 else None  # (doc_start, doc_end) int32 [B, S], or None
         scale = 1.0 / math.sqrt(D)
         w_qkv = _cat_weights([wq, wk, wv])
         w_13 = _cat_weights([w1, w3])
@@ -183,7 +188,8 @@ class FusedBlockFn(torch.autograd.Function):
                     xt8s.append(xt8)
                 return y
 
-        pre = use_rope and prerotate_default(D)
+        # (the document kernels take pre-rotated Q / K only)
+        pre = use_rope and (prerotate_default(D) or doc is not None)
         rope8 = False
         if fp8 is not None:
             xin = h1 if h1 is not None else h1q[0]
@@ -201,9 +207,13 @@ class FusedBlockFn(torch.autograd.Function):
         # training: the forward kernel zeroes the backward's fp32 dQ accumulator in its epilogue (hidden under
         # its compute; the backward pre-pass then only reads O / dO).  Only the fused atomics backward has that
         # accumulator (D != 64), and only when a backward will run.
-        dq_acc = (torch.empty(B * ((S + 63) // 64 * 64), H * D, device=q.device, dtype=torch.float32)
-                  if train and hip().fa_bwd_needs_dq_acc(D) else None)
-        o, lse = hip().fa_fwd(q, k, v, cos, sin, B, S, H, Hkv, D, True, use_rope, scale, pre, dq_acc)
+        if doc is not None:  # document mask: the split backward always, so no dQ accumulator
+            dq_acc = None
+            o, lse = hip().fa_fwd_doc(q, k, v, doc[0], doc[1], B, S, H, Hkv, D, True, use_rope, scale)
+        else:
+            dq_acc = (torch.empty(B * ((S + 63) // 64 * 64), H * D, device=q.device, dtype=torch.float32)
+                      if train and hip().fa_bwd_needs_dq_acc(D) else None)
+            o, lse = hip().fa_fwd(q, k, v, cos, sin, B, S, H, Hkv, D, True, use_rope, scale, pre, dq_acc)
         ctx.dq_acc = dq_acc
         g1 = mm(o, wo.detach(), 1) if fp8 is not None else torch.matmul(o, wo.t())
         if norm8:
@@ -394,8 +404,13 @@ class FusedBlockFn(torch.autograd.Function):
         group_attn = xt8s is None and main and _gemm._GROUP
         do = dx(dxm, [wo], 1) if group_attn else proj(dxm, [wo], 1, o)
         q, k, v = qkv[:, : H * D], qkv[:, H * D : (H + Hkv) * D], qkv[:, (H + Hkv) * D :]
-        dqkv = hip().fa_bwd(do, q, k, v, o, lse, cos, sin, B, S, H, Hkv, D, True, use_rope, scale, ctx.prerotated,
-                            ctx.dq_acc)
+        doc = ctx.meta[9] if len(ctx.meta) > 9 else None
+        if doc is not None:
+            dqkv = hip().fa_bwd_doc(do, q, k, v, o, lse, cos, sin, doc[0], doc[1], B, S, H, Hkv, D, True, use_rope,
+                                    scale)
+        else:
+            dqkv = hip().fa_bwd(do, q, k, v, o, lse, cos, sin, B, S, H, Hkv, D, True, use_rope, scale,
+                                ctx.prerotated, ctx.dq_acc)
         ctx.dq_acc = None
         if group_attn:
             acc_weights([([wo], dxm, o), ([wq, wk, wv], dqkv, h1)])
@@ -436,9 +451,19 @@ class AddRMSNormFn(torch.autograd.Function):
 _EMPTY: dict = {}
 
 
-def fused_block_pair(block, xr: Tensor, xd: Tensor | None, B: int, S: int) -> tuple[Tensor, Tensor]:
+def _doc_meta(doc_bounds, B: int, S: int, device) -> tuple[Tensor, Tensor] | None:
+    """The document bounds as they travel in ``meta``: checked once here (dtype, shape, device; no value is read)."""
+    if doc_bounds is None:
+        return None
+    from ..ops.attention import _check_doc_bounds
+
+    return _check_doc_bounds(doc_bounds, B, S, device, True)
+
+
+def fused_block_pair(block, xr: Tensor, xd: Tensor | None, B: int, S: int, doc_bounds=None) -> tuple[Tensor, Tensor]:
     """Run ``block`` on input ``xr + xd`` ([B*S, d] each; xd may be None); returns (residual, delta) whose sum
-    is the block output -- the next block (or the final norm) adds them inside its RMSNorm."""
+    is the block output -- the next block (or the final norm) adds them inside its RMSNorm.  ``doc_bounds``: the
+    ``(doc_start, doc_end)`` pair of ``ops.doc_bounds`` for document-masked attention."""
     attn, ffn = block.attn, block.ffn
     if attn.rope is not None:
         cos, sin, use_rope = attn.rope.cos, attn.rope.sin, True
@@ -450,28 +475,30 @@ def fused_block_pair(block, xr: Tensor, xd: Tensor | None, B: int, S: int) -> tu
         use_rope = False
     train = torch.is_grad_enabled() and (xr.requires_grad or any(p.requires_grad for p in block.parameters()))
     meta = (B, S, attn.num_heads, attn.num_kv_heads, attn.d_k, block.ln1.eps, use_rope, getattr(block, "fp8", None),
-            train)
+            train, _doc_meta(doc_bounds, B, S, xr.device))
     return FusedBlockFn.apply(xr, xd, block.ln1.weight, attn.q_proj.weight, attn.k_proj.weight,
                               attn.v_proj.weight, attn.output_proj.weight, block.ln2.weight, ffn.w1.weight,
                               ffn.w3.weight, ffn.w2.weight, cos, sin, meta)
 
 
-def fused_block_forward(block, x: Tensor) -> Tensor:
+def fused_block_forward(block, x: Tensor, doc_bounds=None) -> Tensor:
     """Run one ``block`` (a TransformerBlock) through :class:`FusedBlockFn`; x: [B, S, d] bf16 on the GPU."""
     B, S, d = x.shape
-    xm, g2 = fused_block_pair(block, x.reshape(B * S, d).contiguous(), None, B, S)
+    xm, g2 = fused_block_pair(block, x.reshape(B * S, d).contiguous(), None, B, S, doc_bounds)
     return (xm + g2).view(B, S, d)
 
 
-def fused_stack_forward(layers, ln_final, x: Tensor, fence=None) -> Tensor:
+def fused_stack_forward(layers, ln_final, x: Tensor, fence=None, doc_bounds=None) -> Tensor:
     """All blocks + the final RMSNorm with every residual add fused into the following norm.  ``fence``
-    (optional callable(module)) runs before each module's weights are read (sharded DP weight all-gathers)."""
+    (optional callable(module)) runs before each module's weights are read (sharded DP weight all-gathers).
+    ``doc_bounds``: the ``(doc_start, doc_end)`` pair of ``ops.doc_bounds``, the same for every block."""
     B, S, d = x.shape
     xr, xd = x.reshape(B * S, d).contiguous(), None
+    doc_bounds = _doc_meta(doc_bounds, B, S, x.device)
     for layer in layers:
         if fence is not None:
             fence(layer)
-        xr, xd = fused_block_pair(layer, xr, xd, B, S)
+        xr, xd = fused_block_pair(layer, xr, xd, B, S, doc_bounds)
     if fence is not None:
         fence(ln_final)
     return AddRMSNormFn.apply(xr, xd, ln_final.weight, ln_final.eps).view(B, S, d)

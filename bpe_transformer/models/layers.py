@@ -179,21 +179,27 @@ class MultiHeadSelfAttention(nn.Module):
             and (self.rope is None or x.shape[1] <= self.rope.max_seq_len)
         )
 
-    def attend(self, x2: Tensor, batch: int, seq: int) -> Tensor:
-        """Fused GPU path on ``x2 = [batch*seq, d_model]``; returns pre-output-projection ``[batch*seq, d_model]``."""
+    def attend(self, x2: Tensor, batch: int, seq: int, doc_bounds=None) -> Tensor:
+        """Fused GPU path on ``x2 = [batch*seq, d_model]``; returns pre-output-projection ``[batch*seq, d_model]``.
+        ``doc_bounds``: the ``(doc_start, doc_end)`` pair of ``ops.doc_bounds`` for document-masked attention."""
         qkv = torch.matmul(x2, self.qkv_weight().t())
         cos = self.rope.cos if self.rope is not None else None
         sin = self.rope.sin if self.rope is not None else None
-        return ops.flash_attention_qkv(qkv, batch, seq, self.num_heads, self.num_kv_heads, self.d_k, cos, sin, True)
+        return ops.flash_attention_qkv(qkv, batch, seq, self.num_heads, self.num_kv_heads, self.d_k, cos, sin, True,
+                                       doc_bounds=doc_bounds)
 
-    def forward(self, x: Tensor, token_positions: Tensor | None = None) -> Tensor:
+    def forward(self, x: Tensor, token_positions: Tensor | None = None, doc_bounds=None) -> Tensor:
+        """``doc_bounds`` (``ops.doc_bounds`` of the ``[B, S]`` token ids): a token attends only to the earlier tokens
+        of its own document.  RoPE positions stay those of the window (``0..S-1`` or ``token_positions``): RoPE scores
+        depend on the position difference only, so inside a document they equal the ones with positions restarted
+        at its first token."""
         if self._fused_ok(x, token_positions):
             B, S, _ = x.shape
-            o = self.attend(x.reshape(B * S, -1), B, S)
+            o = self.attend(x.reshape(B * S, -1), B, S, doc_bounds)
             return self.output_proj(o).view(B, S, -1)
-        return self._forward_reference(x, token_positions)
+        return self._forward_reference(x, token_positions, doc_bounds)
 
-    def _forward_reference(self, x: Tensor, token_positions: Tensor | None) -> Tensor:
+    def _forward_reference(self, x: Tensor, token_positions: Tensor | None, doc_bounds=None) -> Tensor:
         *lead, S, _ = x.shape
         H, Hkv, D = self.num_heads, self.num_kv_heads, self.d_k
         q = self.q_proj(x).view(*lead, S, H, D).transpose(-2, -3)
@@ -209,6 +215,12 @@ class MultiHeadSelfAttention(nn.Module):
             k = k.repeat_interleave(H // Hkv, dim=-3)
             v = v.repeat_interleave(H // Hkv, dim=-3)
         mask = F.causal_mask(S, device=x.device)
+        if doc_bounds is not None:  # key >= doc_start[query], per batch row: [..., 1(head), S(query), S(key)]
+            start = doc_bounds[0].to(x.device).long()
+            if start.shape != x.shape[:-1]:
+                raise ValueError(f"doc_bounds: doc_start must be {tuple(x.shape[:-1])}, got {tuple(start.shape)}")
+            keys = torch.arange(S, device=x.device)
+            mask = mask & (keys >= start.unsqueeze(-1)).unsqueeze(-3)
         o = F.scaled_dot_product_attention(q, k, v, mask)
         o = o.transpose(-2, -3).reshape(*lead, S, H * D)
         return self.output_proj(o)
@@ -263,19 +275,19 @@ class TransformerBlock(nn.Module):
             and self.attn._fused_ok(x, None)
         )
 
-    def forward(self, x: Tensor, token_positions: Tensor | None = None) -> Tensor:
+    def forward(self, x: Tensor, token_positions: Tensor | None = None, doc_bounds=None) -> Tensor:
         if token_positions is None and self._fused_ok(x):
-            return self._forward_fused(x)
+            return self._forward_fused(x, doc_bounds)
         if self.use_post_norm:
-            x = self.ln1(x + self.attn(x, token_positions))
+            x = self.ln1(x + self.attn(x, token_positions, doc_bounds))
             return self.ln2(x + self.ffn(x))
-        x = x + self.attn(self.ln1(x), token_positions)
+        x = x + self.attn(self.ln1(x), token_positions, doc_bounds)
         return x + self.ffn(self.ln2(x))
 
-    def _forward_fused(self, x: Tensor) -> Tensor:
+    def _forward_fused(self, x: Tensor, doc_bounds=None) -> Tensor:
         from .fused_block import fused_block_forward
 
-        return fused_block_forward(self, x)
+        return fused_block_forward(self, x, doc_bounds)
 
     def _forward_fused_unfused_ops(self, x: Tensor) -> Tensor:
         """Same math as :meth:`_forward_fused` through per-op autograd (kept for A/B and debugging)."""

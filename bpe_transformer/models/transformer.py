@@ -85,6 +85,17 @@ class TransformerLM(nn.Module):
 
     fp8_state = None
     fp8_grad_state = None
+    # document masking (off by default): the separator token id (``<|endoftext|>``).  When set, ``forward`` and
+    # ``loss`` compute ``ops.doc_bounds(in_indices, doc_mask_token)`` unless bounds are passed, and every block's
+    # attention is restricted to the query's own document.  ``generate`` and the KV-cache decode path ignore it.
+    doc_mask_token: int | None = None
+
+    def _doc_bounds(self, in_indices: Tensor, doc_bounds):
+        if doc_bounds is None and self.doc_mask_token is not None:
+            shape = in_indices.shape  # [..., S]: every row of the leading dims is one window
+            start, end = ops.doc_bounds(in_indices.reshape(-1, shape[-1]), int(self.doc_mask_token))
+            doc_bounds = (start.view(shape), end.view(shape))
+        return doc_bounds
 
     def enable_fp8(self, history: int = 16, margin: float = 1.0, dgrad: bool = True, wgrad: bool | None = None,
                    grad_margin: float = 2.0):
@@ -119,7 +130,11 @@ class TransformerLM(nn.Module):
     def fp8_states(self) -> list:
         return [s for s in (self.fp8_state, self.fp8_grad_state) if s is not None]
 
-    def hidden_states(self, in_indices: Tensor) -> Tensor:
+    def hidden_states(self, in_indices: Tensor, doc_bounds=None) -> Tensor:
+        """Final-norm hidden states.  ``doc_bounds``: the ``(doc_start, doc_end)`` pair of ``ops.doc_bounds`` for
+        document-masked attention (explicit only; ``forward`` / ``loss`` derive it from ``doc_mask_token``).  RoPE
+        positions stay ``0..S-1``: RoPE scores depend on ``i - j`` only, so within a document the result equals the
+        one with positions restarted at the document's first token, up to rounding."""
         assert in_indices.shape[-1] <= self.context_length, "sequence longer than context_length"
         fence = self._bpe_param_fence
         if fence is not None:
@@ -129,23 +144,25 @@ class TransformerLM(nn.Module):
                 and all(layer._fused_ok(x) for layer in self.layers)):
             from .fused_block import fused_stack_forward
 
-            return fused_stack_forward(self.layers, self.ln_final, x, fence)
+            return fused_stack_forward(self.layers, self.ln_final, x, fence, doc_bounds)
         for layer in self.layers:
             if fence is not None:
                 fence(layer)
-            x = layer(x)
+            x = layer(x, doc_bounds=doc_bounds) if doc_bounds is not None else layer(x)
         if fence is not None:
             fence(self.ln_final)
         return self.ln_final(x)
 
-    def forward(self, in_indices: Tensor) -> Tensor:
-        h = self.hidden_states(in_indices)
+    def forward(self, in_indices: Tensor, doc_bounds=None) -> Tensor:
+        h = self.hidden_states(in_indices, self._doc_bounds(in_indices, doc_bounds))
         self._fence(self.lm_head)
         return self.lm_head(h)
 
-    def loss(self, in_indices: Tensor, targets: Tensor, ignore_index: int = ops.IGNORE_INDEX) -> Tensor:
-        """Mean next-token cross-entropy; fused LM head + CE on the GPU."""
-        h = self.hidden_states(in_indices)
+    def loss(self, in_indices: Tensor, targets: Tensor, ignore_index: int = ops.IGNORE_INDEX,
+             doc_bounds=None) -> Tensor:
+        """Mean next-token cross-entropy; fused LM head + CE on the GPU.  ``doc_bounds`` / ``doc_mask_token``:
+        document-masked attention (:meth:`hidden_states`)."""
+        h = self.hidden_states(in_indices, self._doc_bounds(in_indices, doc_bounds))
         self._fence(self.lm_head)
         return ops.lm_head_cross_entropy(h, self.lm_head.weight, targets, ignore_index,
                                          chunk=getattr(self, "lm_head_chunk", None),
@@ -185,7 +202,8 @@ class TransformerLM(nn.Module):
             return out[0] if squeeze else out
         for _ in range(max_new_tokens):
             ctx = ids[:, -self.context_length :]
-            logits = self.forward(ctx)[:, -1, :].float()
+            # (sampling is not document-masked: hidden_states takes explicit bounds only, never doc_mask_token)
+            logits = self.lm_head(self.hidden_states(ctx))[:, -1, :].float()
             if temperature <= 0:
                 nxt = logits.argmax(-1, keepdim=True)
             else:

@@ -10,7 +10,8 @@ training step is here.
 
 from ._ext import is_built, library_path, load
 from .activations import gelu, silu, swiglu_gate
-from .attention import attention_qkv_reference, flash_attention_qkv, flash_supported, scaled_dot_product_attention
+from .attention import (attention_qkv_reference, doc_bounds, flash_attention_qkv, flash_supported,
+                        scaled_dot_product_attention)
 from .decode import decode_attention, kv_append
 from .embedding import embedding
 from .loss import IGNORE_INDEX, cross_entropy, lm_head_cross_entropy
@@ -26,6 +27,7 @@ __all__ = [
     "clip_grad_norm_",
     "cross_entropy",
     "decode_attention",
+    "doc_bounds",
     "embedding",
     "flash_attention_qkv",
     "flash_supported",

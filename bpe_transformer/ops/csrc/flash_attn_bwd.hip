@@ -525,8 +525,13 @@ static void bwd_launch(const FaArgs& a, hipStream_t s) {
 }
 
 bool launch_fa_bwd_split(const FaArgs& a, hipStream_t s);  // flash_attn_bwd_split.hip
+void launch_fa_bwd_doc(const FaArgs& a, hipStream_t s);    // flash_attn_bwd_split.hip
 
 void launch_fa_bwd(const FaArgs& a, hipStream_t s) {
+    if (a.doc_start != nullptr) {  // document mask: the split kernels' DOC variants, always
+        launch_fa_bwd_doc(a, s);
+        return;
+    }
     if (launch_fa_bwd_split(a, s)) return;  // D = 64: the split (dQ kernel + dK/dV kernel) form
     // a.rope: 0 none, 1 rotate Q / K on load and dQ / dK on output, 2 outputs only (Q / K pre-rotated)
 #define BWD_CASE(DD)                                                                                        \

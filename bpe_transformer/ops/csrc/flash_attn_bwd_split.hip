@@ -72,16 +72,26 @@ __device__ long long g_stamps[65536 * 8];
 
 // (D = 128: 2 waves per SIMD with 7-9 VGPRs spilled measured 0.44 / 0.71 ms against 0.49 / 0.80 ms at one wave
 // per SIMD without spills, B 4 S 2048 H 16 / GQA 32:8, profiles/bench/attn_d128_split_r4.log)
-template <int D, bool CAUSAL, bool ROPE, bool ROPE_IN>
+//
+// Document mask (DOC; causal, Q / K pre-rotated or no RoPE, so always LDS-DMA staging): query i sees keys
+// doc_start[b, i] <= j <= i, key j is seen by queries j <= i < doc_end[b, j]; both bounds are non-decreasing along a
+// row.  The dQ kernel starts its key sweep at the tile of its first query's doc_start (the block's smallest), the
+// dK/dV kernel ends its query sweep at the tile of its last key's doc_end (the block's largest); inside, a wave skips
+// the 32-row steps wholly outside its own range and takes the masked branch on the steps its range's edge crosses.
+// The wave's two bounds are scalars (uniform-address loads), the lane's own bound one register.  Every bound is
+// clamped into the plain causal range (doc_start to [0, i], doc_end to [j + 1, S]), so any int32 contents walk tiles
+// the causal kernel would have walked.
+template <int D, bool CAUSAL, bool ROPE, bool ROPE_IN, bool DOC = false>
 __global__ void __launch_bounds__(NW * 64, 2)
 fa_bwd_dq_kernel(const __bf16* __restrict__ Q, const __bf16* __restrict__ K, const __bf16* __restrict__ Vv,
                  long ld_q, long ld_kv, const __bf16* __restrict__ O, long ld_o, const __bf16* __restrict__ dO,
                  long ld_do, const float* __restrict__ LSE, float* __restrict__ DELTA, __bf16* __restrict__ dQ,
                  long ld_dq, const float* __restrict__ cosT, const float* __restrict__ sinT, int B, int H, int Hkv,
-                 int S, float scale_log2, float scale, int group) {
+                 int S, float scale_log2, float scale, int group, const int* __restrict__ DS) {
     using G = Geo<D>;
     constexpr int RB = G::RB, TILE = G::TILE, KS = G::KS, ND = G::ND, CPT = G::CPT;
     static_assert(D == 64 || !ROPE_IN, "D = 128: Q / K are rotated before the kernels");
+    static_assert(!DOC || (CAUSAL && !ROPE_IN), "document mask: causal, Q / K pre-rotated or no RoPE");
     constexpr int NT = NW * 64, QB = 32 * NW;
     // keys per K / V tile (one barrier each): 128 with LDS-DMA staging (two 64-row images side by side), 64 with
     // register staging (ROPE_IN: K is rotated on its way to LDS) and at D = 128 (64 KiB of LDS already)
@@ -152,11 +162,22 @@ fa_bwd_dq_kernel(const __bf16* __restrict__ Q, const __bf16* __restrict__ K, con
     const int wu = __builtin_amdgcn_readfirstlane(w);
     const int hbytes = head_bytes(ld_kv, S, D);
     const DmaVoff<NW, RB> kvo = dma_voff<NW, RB>(ld_kv, wu, l);
+    // DOC: first key tile of the block, the wave's smallest / largest doc_start (scalars), the lane's own
+    int it0 = 0, ds_lo = 0, ds_hi = 0, ds_q = 0;
+    if constexpr (DOC) {
+        const int* dsb = DS + (long)b * S;
+        const int qf0 = min(q0, S - 1), qwf = min(q0 + 32 * wu, S - 1), qwl = min(q0 + 32 * wu + 31, S - 1);
+        it0 = __builtin_amdgcn_readfirstlane(min(max(dsb[qf0], 0), qf0)) / KT;  // <= qf0 / KT < nkt
+        ds_lo = __builtin_amdgcn_readfirstlane(min(max(dsb[qwf], 0), qwf));
+        ds_hi = __builtin_amdgcn_readfirstlane(min(max(dsb[qwl], 0), qwl));
+        ds_q = min(max(dsb[qc], 0), (int)qc);
+    }
     if constexpr (DM) {
+        const int b0 = DOC ? (it0 & 1) * BUF : 0;
 #pragma unroll
         for (int sb = 0; sb < NSUB; ++sb) {
-            dma_tile64_buf(kb, hbytes, kvo, 64 * sb, ld_kv, Ks + sb * TILE, wu);
-            dma_tile64_buf(vb, hbytes, kvo, 64 * sb, ld_kv, Vs + sb * TILE, wu);
+            dma_tile64_buf(kb, hbytes, kvo, it0 * KT + 64 * sb, ld_kv, Ks + b0 + sb * TILE, wu);
+            dma_tile64_buf(vb, hbytes, kvo, it0 * KT + 64 * sb, ld_kv, Vs + b0 + sb * TILE, wu);
         }
     } else {
         load_tile(0);
@@ -208,7 +229,7 @@ fa_bwd_dq_kernel(const __bf16* __restrict__ Q, const __bf16* __restrict__ K, con
 
     const int trow = 4 * hh + ((l & 15) >> 2);          // tr-read row inside a 16-key step
     const int tcol = 16 * ((l >> 4) & 1) + 4 * (l & 3);  // tr-read column inside a 32-wide d tile
-    for (int it = 0; it < nkt; ++it) {
+    for (int it = it0; it < nkt; ++it) {
         const int cur = it & 1, k0 = it * KT;
         if (it + 1 == nkt) FA_STAMP(0, 2, 0);
         // the current and next buffers as __restrict__ parameters (see fa_bwd_dkv_kernel): no DMA drain mid-tile
@@ -225,13 +246,16 @@ fa_bwd_dq_kernel(const __bf16* __restrict__ Q, const __bf16* __restrict__ K, con
                     load_tile(it + 1);
                 }
             }
-            if (!CAUSAL || k0 <= qw + 31) {
+            if ((!CAUSAL || k0 <= qw + 31) && (!DOC || k0 + KT - 1 >= ds_lo)) {
 #pragma unroll
                 for (int kq = 0; kq < KT / 32; ++kq) {
                     if (CAUSAL && k0 + 32 * kq > qw + 31) break;  // this 32-key step is past every query of the wave
+                    if (DOC && k0 + 32 * kq + 31 < ds_lo) continue;  // ... or before every query's document
                     // masked only where a key of the step can pass a query of the wave (the diagonal 32 x 32 step)
                     // or the sequence end: the other steps of a diagonal tile take the unmasked path
-                    const bool need_mask = (CAUSAL && k0 + 32 * kq + 31 > qw) || (k0 + 32 * kq + 32 > S);
+                    // (DOC: or a document of the wave starts past the step's first key)
+                    const bool need_mask = (CAUSAL && k0 + 32 * kq + 31 > qw) || (k0 + 32 * kq + 32 > S) ||
+                                           (DOC && k0 + 32 * kq < ds_hi);
                     // step kq: image kq / 2 of the tile, its 32-key half kh
                     char* Kh = Kc + (kq >> 1) * TILE;
                     const char* Vh = Vc + (kq >> 1) * TILE;
@@ -291,10 +315,11 @@ fa_bwd_dq_kernel(const __bf16* __restrict__ Q, const __bf16* __restrict__ K, con
                         // key k0 + 32 kq + acc_row(r, hh) is valid iff <= min(q, S - 1) (causal) / S - 1: the
                         // per-lane limit against the register's compile-time row offset, one compare per score
                         const int klim = (CAUSAL ? min(q, S - 1) : S - 1) - k0 - 32 * kq - 4 * hh;
+                        const int klo = ds_q - k0 - 32 * kq - 4 * hh;  // DOC: the same for the lower limit doc_start
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
                             const float p = fast_exp2(sp[r]);
-                            const bool ok = (r & 3) + 8 * (r >> 2) <= klim;
+                            const bool ok = (r & 3) + 8 * (r >> 2) <= klim && (!DOC || (r & 3) + 8 * (r >> 2) >= klo);
                             dp[r] = ok ? p * dp[r] : 0.f;
                         }
                     } else {
@@ -355,16 +380,17 @@ fa_bwd_dq_kernel(const __bf16* __restrict__ Q, const __bf16* __restrict__ K, con
     }
 }
 
-template <int D, bool CAUSAL, bool ROPE, bool ROPE_IN>
+template <int D, bool CAUSAL, bool ROPE, bool ROPE_IN, bool DOC = false>
 __global__ void __launch_bounds__(NW * 64, D == 64 ? 2 : 1)
 fa_bwd_dkv_kernel(const __bf16* __restrict__ Q, const __bf16* __restrict__ K, const __bf16* __restrict__ Vv,
                   long ld_q, long ld_kv, const __bf16* __restrict__ dO, long ld_do, const float* __restrict__ LSE,
                   const float* __restrict__ DELTA, __bf16* __restrict__ dK, __bf16* __restrict__ dV, long ld_dkv,
                   const float* __restrict__ cosT, const float* __restrict__ sinT, int B,
-                  int H, int Hkv, int S, float scale_log2, float scale, int group) {
+                  int H, int Hkv, int S, float scale_log2, float scale, int group, const int* __restrict__ DE) {
     using Gm = Geo<D>;
     constexpr int RB = Gm::RB, TILE = Gm::TILE, KS = Gm::KS, ND = Gm::ND, CPT = Gm::CPT;
     static_assert(D == 64 || !ROPE_IN, "D = 128: Q / K are rotated before the kernels");
+    static_assert(!DOC || (CAUSAL && !ROPE_IN), "document mask: causal, Q / K pre-rotated or no RoPE");
     constexpr int NT = NW * 64, KB = 32 * NW;
     // queries per Q / dO tile (one barrier each): 128 with LDS-DMA staging (two 64-row images side by side), 64
     // with register staging (ROPE_IN: Q is rotated on its way to LDS) and at D = 128
@@ -409,7 +435,19 @@ fa_bwd_dkv_kernel(const __bf16* __restrict__ Q, const __bf16* __restrict__ K, co
         }
     }
     const int m_start = CAUSAL ? kb0 : 0;  // kb0 is a multiple of 64
-    const int nqt = m_start < S ? (S - m_start + QT - 1) / QT : 0;
+    // DOC: one past the last query any key of the block is seen by (its last valid key's doc_end, the block's
+    // largest), the wave's smallest / largest doc_end (scalars) and the lane's own; each clamped to [key + 1, S]
+    int q_end = S, de_lo = S, de_hi = S, de_k = S;
+    if constexpr (DOC) {
+        const int* deb = DE + (long)b * S;
+        const int wv = __builtin_amdgcn_readfirstlane(w);
+        const int kl = min(kb0 + KB - 1, S - 1), kwf = min(kb0 + 32 * wv, S - 1), kwl = min(kb0 + 32 * wv + 31, S - 1);
+        q_end = __builtin_amdgcn_readfirstlane(max(min(deb[kl], S), kl + 1));
+        de_lo = __builtin_amdgcn_readfirstlane(max(min(deb[kwf], S), kwf + 1));
+        de_hi = __builtin_amdgcn_readfirstlane(max(min(deb[kwl], S), kwl + 1));
+        de_k = max(min(deb[kpos], S), (int)kpos + 1);
+    }
+    const int nqt = m_start < S ? ((DOC ? q_end : S) - m_start + QT - 1) / QT : 0;  // q_end > m_start: >= 1 tile
     const int nsteps = GL * nqt;  // (query head, query tile) steps, head-major
     // step j: query head h + j / nqt, query tile j % nqt
     auto q_of = [&](int j) { return Q + (long)b * S * ld_q + (long)(h + j / nqt) * D; };
@@ -510,7 +548,8 @@ fa_bwd_dkv_kernel(const __bf16* __restrict__ Q, const __bf16* __restrict__ K, co
     const int trow = 4 * hh + ((l & 15) >> 2);
     const int tcol = 16 * ((l >> 4) & 1) + 4 * (l & 3);
     const int klim = CAUSAL ? (key_ok ? key : S) : (key_ok ? 0 : S);
-    const unsigned span = (unsigned)(S - klim);  // valid query q: (unsigned)(q - klim) < span
+    // valid query q: (unsigned)(q - klim) < span; DOC: the key's document ends at de_k <= S
+    const unsigned span = (unsigned)((DOC && key_ok ? de_k : S) - klim);
     for (int it = 0; it < nsteps; ++it) {
         const int cur = it & 1, m0 = m0_of(it);
         if (it + 1 == nsteps) FA_STAMP(32768, 2, 0);
@@ -532,14 +571,16 @@ fa_bwd_dkv_kernel(const __bf16* __restrict__ Q, const __bf16* __restrict__ K, co
             }
             const float* lc = lseS + cur * QT;
             const float* dc = dltS + cur * QT;
-            if (!CAUSAL || m0 + QT - 1 >= kw0) {
+            if ((!CAUSAL || m0 + QT - 1 >= kw0) && (!DOC || m0 < de_hi)) {
 #pragma unroll
                 for (int qq = 0; qq < QT / 32; ++qq) {
                     if (CAUSAL && m0 + 32 * qq + 31 < kw0) continue;  // every query of this step precedes every key
+                    if (DOC && m0 + 32 * qq >= de_hi) continue;       // ... or lies past every key's document
                     // masked only where a query of the step can precede a key of the wave (the diagonal 32 x 32
                     // step) or at the sequence end: the other steps of a diagonal tile take the unmasked path
-                    const bool need_mask =
-                        (CAUSAL && m0 + 32 * qq < kw0 + 31) || (m0 + 32 * qq + 32 > S) || (kw0 + 32 > S);
+                    // (DOC: or a document of the wave ends before the step's last query)
+                    const bool need_mask = (CAUSAL && m0 + 32 * qq < kw0 + 31) || (m0 + 32 * qq + 32 > S) ||
+                                           (kw0 + 32 > S) || (DOC && m0 + 32 * qq + 32 > de_lo);
                     // step qq: image qq / 2 of the tile, its 32-query half qt
                     char* Qh = Qc + (qq >> 1) * TILE;
                     char* Oh = Oc + (qq >> 1) * TILE;
@@ -659,21 +700,21 @@ int fa_bwd_config(int mode) {
     return prev;
 }
 
-template <int D, bool C, bool R, bool RIN>
+template <int D, bool C, bool R, bool RIN, bool DOC = false>
 static void split_launch(const FaArgs& a, hipStream_t s) {
     constexpr int NSUB = (RIN || D == 128) ? 1 : 2;  // 64-row images per LDS buffer (128-row tiles with LDS-DMA)
     constexpr int TILE = split::Geo<D>::TILE;
     const int nblk = (a.S + 32 * split::NW - 1) / (32 * split::NW);
     // the 16-queries-per-wave dQ kernel when selected (fa_dq_config; D = 64 without in-kernel RoPE)
-    if (!launch_fa_bwd_dq16(a, s))
-        split::fa_bwd_dq_kernel<D, C, R, RIN><<<nblk * a.B * a.H, split::NW * 64, 4 * TILE * NSUB, s>>>(
+    if (DOC || !launch_fa_bwd_dq16(a, s))
+        split::fa_bwd_dq_kernel<D, C, R, RIN, DOC><<<nblk * a.B * a.H, split::NW * 64, 4 * TILE * NSUB, s>>>(
             a.q, a.k, a.v, a.ld_q, a.ld_kv, a.o, a.ld_o, a.dout, a.ld_do, a.lse, a.delta, a.dq, a.ld_dq, a.cos,
-            a.sin, a.B, a.H, a.Hkv, a.S, a.scale * LOG2E, a.scale, fa_group(a.B * a.H));
+            a.sin, a.B, a.H, a.Hkv, a.S, a.scale * LOG2E, a.scale, fa_group(a.B * a.H), a.doc_start);
     // Q / dO buffers + the -lse / -delta rows
     const int lds = 4 * TILE * NSUB + 16 * 64 * NSUB;
-    split::fa_bwd_dkv_kernel<D, C, R, RIN><<<nblk * a.B * a.Hkv, split::NW * 64, lds, s>>>(
+    split::fa_bwd_dkv_kernel<D, C, R, RIN, DOC><<<nblk * a.B * a.Hkv, split::NW * 64, lds, s>>>(
         a.q, a.k, a.v, a.ld_q, a.ld_kv, a.dout, a.ld_do, a.lse, a.delta, a.dk, a.dv, a.ld_dkv, a.cos,
-        a.sin, a.B, a.H, a.Hkv, a.S, a.scale * LOG2E, a.scale, fa_group(a.B * a.Hkv));
+        a.sin, a.B, a.H, a.Hkv, a.S, a.scale * LOG2E, a.scale, fa_group(a.B * a.Hkv), a.doc_end);
 }
 
 // whether a GQA backward of head size D needs the fp32 dK / dV partials buffer (FaArgs::dkv_part): only the fused
@@ -693,6 +734,18 @@ bool fa_read_stamps(long long* host, int n) {
     (void)n;
     return false;
 #endif
+}
+
+// The document-masked backward: always the two 32-row split kernels above, whatever fa_bwd_config / fa_dq_config
+// select (no dq16, no fused-atomics form, no fp32 dQ accumulator); causal, rope 0 or 2 (the bindings check).
+void launch_fa_bwd_doc(const FaArgs& a, hipStream_t s) {
+    if (a.D == 128) {
+        if (a.rope == 2) split_launch<128, true, true, false, true>(a, s);
+        else split_launch<128, true, false, false, true>(a, s);
+    } else {
+        if (a.rope == 2) split_launch<64, true, true, false, true>(a, s);
+        else split_launch<64, true, false, false, true>(a, s);
+    }
 }
 
 bool launch_fa_bwd_split(const FaArgs& a, hipStream_t s) {

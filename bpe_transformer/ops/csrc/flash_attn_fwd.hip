@@ -34,6 +34,13 @@
 //   * Work order: heaviest causal blocks first; the blocks of one (batch,
 //     head) are 8-aligned apart in launch order so they share an XCD L2 under
 //     round-robin dispatch (speed only).
+//   * Document mask (DOC, causal only, Q / K pre-rotated or no RoPE): query i sees keys doc_start[b, i] <= j <= i.
+//     doc_start is non-decreasing along a row, so the block's first query has the block's smallest bound: the key
+//     loop starts at that bound's tile, a wave skips tiles wholly below its first query's bound, and the masked
+//     branch is also taken while a tile starts below the wave's last query's bound.  The two wave bounds are scalars
+//     (uniform-address loads); the lane's own bound is loaded once.  Every bound is clamped to [0, query], so any
+//     int32 contents give in-range tile indices.  A query's first processed tile can be fully masked: m_run stays
+//     -inf, mu = 0, p = exp2(-inf) = 0, alpha = 1.
 #include "fa_common.h"
 #include "kernels.h"
 
@@ -46,12 +53,13 @@ namespace fa {
 constexpr float RESCALE_THRESHOLD = 8.0f;
 
 
-template <int D, bool CAUSAL, bool ROPE>
+template <int D, bool CAUSAL, bool ROPE, bool DOC = false>
 __global__ void __launch_bounds__(256, 2)
 fa_fwd_kernel(const __bf16* __restrict__ Q, const __bf16* __restrict__ K, const __bf16* __restrict__ Vv, long ld_q,
               long ld_kv, __bf16* __restrict__ O, long ld_o, float* __restrict__ LSE, const float* __restrict__ cosT,
               const float* __restrict__ sinT, int B, int H, int Hkv, int S, float scale_log2, int group,
-              float* __restrict__ DQZ) {
+              float* __restrict__ DQZ, const int* __restrict__ DS) {
+    static_assert(!DOC || (CAUSAL && !ROPE), "document mask: causal, Q / K pre-rotated or no RoPE");
     constexpr int RB = D * 2;            // bytes per LDS row
     constexpr int CPR = D / 8;           // 16-byte chunks per row
     constexpr int TILE = 64 * RB;        // bytes per 64-row tile
@@ -151,15 +159,28 @@ fa_fwd_kernel(const __bf16* __restrict__ Q, const __bf16* __restrict__ K, const 
     const int trow = 4 * hh + ((l & 15) >> 2);          // tr-read row inside a 16-key step
     const int tcol = 16 * ((l >> 4) & 1) + 4 * (l & 3);  // tr-read column inside a 32-wide d tile
 
-    load_tile(0);
-    write_tile(0, 0);
+    // DOC: first key tile of the block, the wave's smallest / largest bound (scalars), the lane's own bound
+    int t0 = 0, ds_lo = 0, ds_hi = 0, ds_q = 0;
+    if constexpr (DOC) {
+        const int* dsb = DS + (long)b * S;
+        const int wu = __builtin_amdgcn_readfirstlane(w);
+        const int qf0 = min(q0, S - 1), qwf = min(q0 + 32 * wu, S - 1), qwl = min(q0 + 32 * wu + 31, S - 1);
+        t0 = __builtin_amdgcn_readfirstlane(min(max(dsb[qf0], 0), qf0)) >> 6;  // <= qf0 / 64 < ntiles
+        ds_lo = __builtin_amdgcn_readfirstlane(min(max(dsb[qwf], 0), qwf));
+        ds_hi = __builtin_amdgcn_readfirstlane(min(max(dsb[qwl], 0), qwl));
+        const int ql = min(qrow, S - 1);
+        ds_q = min(max(dsb[ql], 0), ql);
+    }
+
+    load_tile(t0);
+    write_tile(t0, t0 & 1);
     __syncthreads();
 
-    for (int t = 0; t < ntiles; ++t) {
+    for (int t = t0; t < ntiles; ++t) {
         const int cur = t & 1;
         if (t + 1 < ntiles) load_tile(t + 1);
         const int n0 = t * 64;
-        const bool active = !CAUSAL || (n0 <= qw0 + 31);
+        const bool active = (!CAUSAL || (n0 <= qw0 + 31)) && (!DOC || n0 + 63 >= ds_lo);
         if (active) {
             const char* Kc = Ks + cur * TILE;
             char* Vc = Vs + cur * TILE;
@@ -172,13 +193,13 @@ fa_fwd_kernel(const __bf16* __restrict__ Q, const __bf16* __restrict__ K, const 
                 for (int ks = 0; ks < KS; ++ks)
                     s[kt] = mfma(lds_row16(Kc, swz<RB>(kt * 32 + l31, 2 * ks + hh)), qf[ks], s[kt]);
             }
-            if ((CAUSAL && n0 + 63 > qw0) || (n0 + 64 > S)) {
+            if ((CAUSAL && n0 + 63 > qw0) || (n0 + 64 > S) || (DOC && n0 < ds_hi)) {
 #pragma unroll
                 for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int key = n0 + kt * 32 + acc_row(r, hh);
-                        if ((CAUSAL && key > qrow) || key >= S) s[kt][r] = -INFINITY;
+                        if ((CAUSAL && key > qrow) || key >= S || (DOC && key < ds_q)) s[kt][r] = -INFINITY;
                     }
             }
             float mt = s[0][0];
@@ -271,15 +292,21 @@ using namespace bpe::fa;
 
 size_t fa_fwd_lds_bytes(int D) { return (size_t)4 * 64 * D * 2; }
 
-template <int D, bool C, bool R>
+template <int D, bool C, bool R, bool DOC = false>
 static void fwd_launch(const FaArgs& a, hipStream_t s) {
     const int nqb = (a.S + 127) / 128;
-    fa_fwd_kernel<D, C, R><<<nqb * a.B * a.H, 256, fa_fwd_lds_bytes(D), s>>>(
+    fa_fwd_kernel<D, C, R, DOC><<<nqb * a.B * a.H, 256, fa_fwd_lds_bytes(D), s>>>(
         a.q, a.k, a.v, a.ld_q, a.ld_kv, a.o, a.ld_o, a.lse, a.cos, a.sin, a.B, a.H, a.Hkv, a.S, a.scale * LOG2E, fa_group(a.B * a.H),
-        a.dq_acc);
+        a.dq_acc, a.doc_start);
 }
 
 void launch_fa_fwd(const FaArgs& a, hipStream_t s) {
+    // document mask: always this file's kernel (whatever fa_fwd_config says), causal, rope 0 / 2 (the bindings check)
+    if (a.doc_start != nullptr) {
+        if (a.D == 64) fwd_launch<64, true, false, true>(a, s);
+        else fwd_launch<128, true, false, true>(a, s);
+        return;
+    }
     if (launch_fa_fwd_v4(a, s)) return;  // D = 64 without in-kernel RoPE (flash_attn_fwd_v4.hip)
     // rope 2 = Q / K already rotated: no RoPE inside the kernel
     const bool r = a.rope == 1;

@@ -144,6 +144,11 @@ struct FaArgs {
     __bf16* dv;
     long ld_dkv;
     float* dkv_part;  // GQA only: [B*S][H][2][D] fp32 per-query-head dK / dV partials
+    // document mask (both null: plain causal / full attention): int32 [B, S]; query i sees keys doc_start[b, i] <= j
+    // <= i, key j is seen by queries j <= i < doc_end[b, j].  Causal, rope 0 / 2 only; the launchers then always take
+    // fa_fwd_kernel and the split backward's 32-row kernels (no v8 forward, no dq16, no fused-atomics backward).
+    const int* doc_start;
+    const int* doc_end;
 };
 // decode_attn.hip (KV-cache serving path; `pos` = device int32 position of the first new token)
 int decode_attn_splits(int Lmax);

@@ -858,10 +858,22 @@ void check_dq_acc(const at::Tensor& t, const at::Tensor& q, int64_t B, int64_t S
                 "flash attention: dq_acc must be a contiguous fp32 [B * round_up(S, 64), H * D] tensor on q's device");
 }
 
-std::tuple<at::Tensor, at::Tensor> fa_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+// Document bounds of the masked attention ops: int32 [B, S], contiguous, on q's device.  Only the metadata is
+// checked -- no value is read on the host (no sync; the ops stay capturable in a graph) -- and the kernels clamp
+// every bound, so wrong values give wrong numbers, never an out-of-range access.
+const int* check_doc_bounds(const at::Tensor& t, const at::Tensor& q, int64_t B, int64_t S, const char* name) {
+    TORCH_CHECK(t.is_cuda() && t.device() == q.device(), "flash attention: ", name, " must be on q's device");
+    TORCH_CHECK(t.scalar_type() == at::kInt, "flash attention: ", name, " must be int32");
+    TORCH_CHECK(t.dim() == 2 && t.size(0) == B && t.size(1) == S && t.is_contiguous(), "flash attention: ", name,
+                " must be a contiguous [B, S] tensor");
+    return t.data_ptr<int>();
+}
+
+static std::tuple<at::Tensor, at::Tensor> fa_fwd_impl(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                                           const at::Tensor& cos, const at::Tensor& sin, int64_t B, int64_t S, int64_t H,
                                           int64_t Hkv, int64_t D, bool causal, bool use_rope, double scale,
-                                          bool prerotated, const c10::optional<at::Tensor>& dq_acc) {
+                                          bool prerotated, const c10::optional<at::Tensor>& dq_acc,
+                                          const at::Tensor* doc_start, const at::Tensor* doc_end) {
     TORCH_CHECK(D == 64 || D == 128, "flash attention: head dim must be 64 or 128");
     TORCH_CHECK(H % Hkv == 0, "flash attention: H must be a multiple of Hkv");
     check_qkv(q, B * S, H * D, "q");
@@ -886,8 +898,32 @@ std::tuple<at::Tensor, at::Tensor> fa_fwd(const at::Tensor& q, const at::Tensor&
         check_dq_acc(*dq_acc, q, B, S, H, D);
         a.dq_acc = dq_acc->data_ptr<float>();
     }
+    if (doc_start != nullptr) {
+        TORCH_CHECK(causal, "flash attention: document masking requires causal=True");
+        TORCH_CHECK(a.rope != 1, "flash attention: document masking takes pre-rotated Q / K (rope_qk_) or no RoPE");
+        a.doc_start = check_doc_bounds(*doc_start, q, B, S, "doc_start");
+        a.doc_end = check_doc_bounds(*doc_end, q, B, S, "doc_end");
+    }
     launch_fa_fwd(a, cur_stream());
     return {o, lse};
+}
+
+std::tuple<at::Tensor, at::Tensor> fa_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                                          const at::Tensor& cos, const at::Tensor& sin, int64_t B, int64_t S, int64_t H,
+                                          int64_t Hkv, int64_t D, bool causal, bool use_rope, double scale,
+                                          bool prerotated, const c10::optional<at::Tensor>& dq_acc) {
+    return fa_fwd_impl(q, k, v, cos, sin, B, S, H, Hkv, D, causal, use_rope, scale, prerotated, dq_acc, nullptr,
+                       nullptr);
+}
+
+// The document-masked forward: query i of row b sees keys doc_start[b, i] <= j <= i (ops/attention.py doc_bounds).
+// Q / K arrive pre-rotated (`rotated`) or without RoPE; always fa_fwd_kernel's DOC variant.
+std::tuple<at::Tensor, at::Tensor> fa_fwd_doc(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                                              const at::Tensor& doc_start, const at::Tensor& doc_end, int64_t B,
+                                              int64_t S, int64_t H, int64_t Hkv, int64_t D, bool causal, bool rotated,
+                                              double scale) {
+    return fa_fwd_impl(q, k, v, q, q, B, S, H, Hkv, D, causal, rotated, scale, true, c10::nullopt, &doc_start,
+                       &doc_end);
 }
 
 // whether fa_bwd uses (and fa_fwd should zero) the fp32 dQ accumulator for head dim D
@@ -920,10 +956,17 @@ at::Tensor gpp_stamps_op(int64_t n) {
 
 
 // Returns dqkv = [B*S, (H + 2*Hkv) * D]: dq | dk | dv in the fused QKV-projection layout.
-at::Tensor fa_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+static at::Tensor fa_bwd_impl(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                   const at::Tensor& o, const at::Tensor& lse, const at::Tensor& cos, const at::Tensor& sin, int64_t B,
                   int64_t S, int64_t H, int64_t Hkv, int64_t D, bool causal, bool use_rope, double scale,
-                  bool prerotated, const c10::optional<at::Tensor>& dq_acc_in) {
+                  bool prerotated, const c10::optional<at::Tensor>& dq_acc_in, const at::Tensor* doc_start,
+                  const at::Tensor* doc_end) {
+    const bool doc = doc_start != nullptr;
+    if (doc) {
+        TORCH_CHECK(causal, "flash attention: document masking requires causal=True");
+        TORCH_CHECK(!use_rope || prerotated,
+                    "flash attention: document masking takes pre-rotated Q / K (rope_qk_) or no RoPE");
+    }
     TORCH_CHECK(D == 64 || D == 128, "flash attention: head dim must be 64 or 128");
     TORCH_CHECK(Hkv > 0 && H % Hkv == 0, "flash attention: H must be a multiple of Hkv");
     if (use_rope)
@@ -957,14 +1000,16 @@ at::Tensor fa_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor&
         rope = 2;
     }
     // rows padded to 64 per batch; zeroed by the forward when it was handed this buffer (fa_fwd dq_acc)
-    const bool split = fa_bwd_split_active((int)D, rope);  // the split form needs no fp32 dQ accumulator
+    // the split form needs no fp32 dQ accumulator (the document path is always split)
+    const bool split = doc || fa_bwd_split_active((int)D, rope);
     const bool pre_zeroed = !split && dq_acc_in.has_value() && dq_acc_in->defined();
     if (pre_zeroed) check_dq_acc(*dq_acc_in, q, B, S, H, D);
     at::Tensor dq_acc;
     if (!split)
         dq_acc = pre_zeroed ? *dq_acc_in : at::empty({B * ((S + 63) / 64 * 64), H * D}, q.options().dtype(at::kFloat));
     at::Tensor dkv_part;
-    const bool need_part = Hkv < H && fa_dkv_partials_needed((int)D, rope);  // GQA per-query-head partials (+ reduce)
+    // GQA per-query-head partials (+ reduce)
+    const bool need_part = !doc && Hkv < H && fa_dkv_partials_needed((int)D, rope);
     if (need_part) dkv_part = at::empty({B * S, H * 2 * D}, q.options().dtype(at::kFloat));
     FaArgs a{};
     a.q = qp; a.k = kp; a.v = vp;
@@ -980,8 +1025,30 @@ at::Tensor fa_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor&
     a.dq = base; a.ld_dq = W;
     a.dk = base + H * D; a.dv = base + (H + Hkv) * D; a.ld_dkv = W;
     a.dkv_part = need_part ? dkv_part.data_ptr<float>() : nullptr;
+    if (doc) {
+        a.doc_start = check_doc_bounds(*doc_start, q, B, S, "doc_start");
+        a.doc_end = check_doc_bounds(*doc_end, q, B, S, "doc_end");
+    }
     launch_fa_bwd(a, cur_stream());
     return dqkv;
+}
+
+at::Tensor fa_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                  const at::Tensor& o, const at::Tensor& lse, const at::Tensor& cos, const at::Tensor& sin, int64_t B,
+                  int64_t S, int64_t H, int64_t Hkv, int64_t D, bool causal, bool use_rope, double scale,
+                  bool prerotated, const c10::optional<at::Tensor>& dq_acc_in) {
+    return fa_bwd_impl(dout, q, k, v, o, lse, cos, sin, B, S, H, Hkv, D, causal, use_rope, scale, prerotated,
+                       dq_acc_in, nullptr, nullptr);
+}
+
+// The document-masked backward of fa_fwd_doc (cos / sin: the tables Q / K were rotated with, to rotate dQ / dK back;
+// ignored without `rotated`); always the split kernels' DOC variants.
+at::Tensor fa_bwd_doc(const at::Tensor& dout, const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
+                      const at::Tensor& o, const at::Tensor& lse, const at::Tensor& cos, const at::Tensor& sin,
+                      const at::Tensor& doc_start, const at::Tensor& doc_end, int64_t B, int64_t S, int64_t H,
+                      int64_t Hkv, int64_t D, bool causal, bool rotated, double scale) {
+    return fa_bwd_impl(dout, q, k, v, o, lse, cos, sin, B, S, H, Hkv, D, causal, rotated, scale, true, c10::nullopt,
+                       &doc_start, &doc_end);
 }
 
 // ---------------------------------------------------------------- KV-cache decode (serving)
@@ -1223,6 +1290,11 @@ TORCH_LIBRARY(bpe_hip, m) {
     m.def("fa_bwd(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor cos, Tensor sin, int B, "
           "int S, int H, int Hkv, int D, bool causal, bool rope, float scale, bool prerotated=False, "
           "Tensor? dq_acc=None) -> Tensor");
+    m.def("fa_fwd_doc(Tensor q, Tensor k, Tensor v, Tensor doc_start, Tensor doc_end, int B, int S, int H, int Hkv, "
+          "int D, bool causal, bool rotated, float scale) -> (Tensor, Tensor)");
+    m.def("fa_bwd_doc(Tensor dout, Tensor q, Tensor k, Tensor v, Tensor o, Tensor lse, Tensor cos, Tensor sin, "
+          "Tensor doc_start, Tensor doc_end, int B, int S, int H, int Hkv, int D, bool causal, bool rotated, "
+          "float scale) -> Tensor");
     m.def("rope_qk_(Tensor(a!) qkv, Tensor cos, Tensor sin, int B, int S, int H, int Hkv, int D) -> ()");
     m.def("fa_bwd_needs_dq_acc(int D) -> bool", &fa_bwd_needs_dq_acc);  // no tensors: a catch-all kernel
     m.def("fa_bwd_config(int mode=-1) -> int", &fa_bwd_config_op);
@@ -1273,6 +1345,8 @@ TORCH_LIBRARY_IMPL(bpe_hip, CUDA, m) {
     m.impl("rope", &rope);
     m.impl("fa_fwd", &fa_fwd);
     m.impl("fa_bwd", &fa_bwd);
+    m.impl("fa_fwd_doc", &fa_fwd_doc);
+    m.impl("fa_bwd_doc", &fa_bwd_doc);
     m.impl("rope_qk_", &rope_qk_);
     m.impl("kv_append", &kv_append);
     m.impl("decode_attn", &decode_attn);

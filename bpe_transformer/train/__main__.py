@@ -8,6 +8,9 @@ Examples::
     # GPT-2-small on 8 MI355X over RCCL, real tokens
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m bpe_transformer.train --preset gpt2-small \
         data.train_path=data/train.bin batch_size=32 max_iters=20000 ckpt_every=1000 resume=latest
+
+    # no attention across <|endoftext|> (GPT-2 id 50256) inside a packed training window
+    python -m bpe_transformer.train --preset gpt2-small data.train_path=data/train.bin doc_mask_token=50256
 """
 
 from __future__ import annotations

@@ -69,6 +69,9 @@ class TrainConfig:
     # lm_head_chunk rows, dh / dW formed in the forward: memory O(chunk * vocab)); lm_head_chunk 0 = default
     lm_head_mode: str = "logits"
     lm_head_chunk: int = 0
+    # document masking: the separator token id (e.g. 50256, GPT-2's <|endoftext|>); training and eval attention then
+    # stays inside each packed document (ops.doc_bounds; RoPE positions stay 0..S-1).  None = plain causal attention
+    doc_mask_token: int | None = None
 
     def resolved_grad_dtype(self, param_dtype):
         import torch

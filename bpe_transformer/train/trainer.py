@@ -65,6 +65,11 @@ class Trainer:
             raise ValueError(f"lm_head_mode must be 'logits' or 'streamed', got {cfg.lm_head_mode!r}")
         self.model.lm_head_mode = cfg.lm_head_mode
         self.model.lm_head_chunk = cfg.lm_head_chunk or None
+        if cfg.doc_mask_token is not None and not 0 <= int(cfg.doc_mask_token) < cfg.model.vocab_size:
+            raise ValueError(f"doc_mask_token must be a token id in [0, {cfg.model.vocab_size}), got "
+                             f"{cfg.doc_mask_token!r}")
+        # document-masked attention in training and eval (model.loss computes the bounds per micro-batch)
+        self.model.doc_mask_token = None if cfg.doc_mask_token is None else int(cfg.doc_mask_token)
         o = cfg.optim
         self.engine = TrainEngine(self.model, self.info, lr=o.lr, betas=o.betas, eps=o.eps,
                                   weight_decay=o.weight_decay, max_grad_norm=o.max_grad_norm,

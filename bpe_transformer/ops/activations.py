@@ -46,9 +46,10 @@ class _ActFn(torch.autograd.Function):
 
 def swiglu_gate(gu: Tensor) -> Tensor:
     """``silu(gu[..., :F]) * gu[..., F:]`` for the fused [W1; W3] projection output."""
-    if gu.is_cuda:
-        return _SwiGLUFn.apply(gu)
     f = gu.shape[-1] // 2
+    if gu.is_cuda and gu.dtype in (torch.float32, torch.bfloat16) and gu.shape[-1] == 2 * f and (
+            f % (8 if gu.dtype == torch.bfloat16 else 4) == 0):
+        return _SwiGLUFn.apply(gu)
     return F.silu(gu[..., :f]) * gu[..., f:]
 
 

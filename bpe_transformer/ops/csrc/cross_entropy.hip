@@ -50,6 +50,7 @@ __global__ void __launch_bounds__(256) ce_fwd_bwd_kernel(T* __restrict__ logits,
         float vm = a.v[0];
 #pragma unroll
         for (int j = 1; j < VN; ++j) vm = fmaxf(vm, a.v[j]);
+        if (vm == -INFINITY) continue;  // a fully masked vector adds nothing (exp(-inf - -inf) would be NaN)
         float vs = 0.f;
 #pragma unroll
         for (int j = 0; j < VN; ++j) vs += __expf(a.v[j] - vm);
@@ -98,7 +99,7 @@ __global__ void __launch_bounds__(256) ce_fwd_bwd_kernel(T* __restrict__ logits,
     }
 }
 
-// Register-resident variant (the default when a row fits: V <= 512 threads x MAXV vectors): one 512-thread
+// Register-resident variant (the default when a row fits: V < 512 threads x MAXV vectors x VN): one 512-thread
 // block per row loads the row ONCE into registers (16-byte vectors, <= MAXV per thread), then block max ->
 // block sum of exp(x - max) -> writes (softmax - onehot) * scale from the registers.  One HBM read and one
 // write per element (the two-pass kernel above re-reads the row, which at 8 blocks/CU x 100 KB rows falls
@@ -208,7 +209,7 @@ void launch_ce_fwd_bwd(int dtype, void* logits, long ld, const int64_t* targets,
     if (M == 0) return;
     constexpr int MAXV = 16;
     const int vn = dtype == DT_BF16 ? 8 : 4;
-    if ((V + vn) / vn <= 512 * MAXV) {  // row fits in registers (V <= 65528 bf16 / 32760 fp32)
+    if ((V + vn) / vn <= 512 * MAXV) {  // row fits in registers with any head / tail split (V <= 65535 bf16 / 32767 fp32)
         if (dtype == DT_BF16)
             ce_fwd_bwd_reg_kernel<__bf16, MAXV><<<M, 512, 0, s>>>((__bf16*)logits, ld, targets, loss, lse, nvalid, V,
                                                                   ignore_index, write_grad);

@@ -20,8 +20,8 @@ __global__ void __launch_bounds__(256) softmax_fwd_kernel(const T* __restrict__ 
     for (int i = threadIdx.x; i < N; i += 256) {
         const float v = ld1<T>(xr + i);
         const float mn = fmaxf(m, v);
-        s = s * __expf(m - mn) + __expf(v - mn);
-        m = mn;
+        // -inf so far and a -inf element: m - mn would be NaN; (m, s) stays (-inf, 0), as in the merges below
+        if (mn != -INFINITY) { s = s * __expf(m - mn) + __expf(v - mn); m = mn; }
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {

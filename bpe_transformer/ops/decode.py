@@ -7,7 +7,9 @@ whole prefix for every new token.
 * :func:`kv_append` takes the fused QKV projection of ``T`` new tokens per
   sequence, applies RoPE at their absolute positions (``pos .. pos+T-1``, with
   ``pos`` a device int32 tensor), writes K (roped) and V into the caches
-  ``[B, Hkv, Lmax, D]``, and returns the roped queries ``[B*T, H*D]``.
+  ``[B, Hkv, Lmax, D]``, and returns the roped queries ``[B*T, H*D]``.  A token whose position is at or past
+  ``Lmax`` is dropped: nothing is written to the caches for it, and its query rows in the result are unspecified
+  (the GPU kernel leaves them uninitialised, the CPU oracle fills them in).
 * :func:`decode_gemv` / :func:`decode_qkv` are the M <= 8 skinny projections of
   the decode step with RMSNorm / residual-add prologues and SwiGLU / RoPE +
   cache-write epilogues (``csrc/decode_gemv.hip``).
@@ -85,7 +87,8 @@ def decode_attention_reference(q, k_cache, v_cache, pos, n_heads, scale=None, n_
 def decode_attention_partials(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, n_heads: int,
                               scale: float | None = None) -> Tensor:
     """Split-K decode attention without the combine: fp32 ``[B, H, nsplit, D + 2]`` = (o, m, l) per 256-key chunk
-    (natural-log units; empty chunks have ``m = -inf``), consumed by :func:`decode_attn_proj`."""
+    (natural-log units), consumed by :func:`decode_attn_proj`.  A chunk past the valid length has ``m = -inf`` and
+    ``l = 0``; its ``o`` part is unspecified (the GPU kernel leaves it unwritten) and every consumer skips it."""
     D = k_cache.shape[-1]
     scale = 1.0 / math.sqrt(D) if scale is None else scale
     if q.is_cuda:
@@ -126,7 +129,9 @@ def decode_attn_proj(part: Tensor, w: Tensor) -> Tensor:
     m = part[..., D]
     mx = m.amax(-1, keepdim=True)
     c = torch.where(torch.isinf(m), torch.zeros_like(m), torch.exp(m - mx))
-    o = (c[..., None] * part[..., :D]).sum(2) / (c * part[..., D + 1]).sum(-1, keepdim=True).clamp_min(1e-30)
+    # the o part of an empty chunk (m = -inf) is unspecified (the kernel leaves it unwritten): skipped, not scaled by 0
+    po = torch.where(torch.isinf(m)[..., None], torch.zeros_like(part[..., :D]), part[..., :D])
+    o = (c[..., None] * po).sum(2) / (c * part[..., D + 1]).sum(-1, keepdim=True).clamp_min(1e-30)
     x = o.reshape(B, H * D).to(w.dtype)
     return (x.float() @ w.float().t()).to(w.dtype)
 

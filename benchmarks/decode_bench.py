@@ -3,6 +3,8 @@
 For each batch size: prefill a prompt, then time ``--tokens`` decode steps (HIP-graph replay by default,
 ``--no-graph`` for eager launches), and the decode-attention kernel alone at the final cache length (HBM
 bandwidth of the K/V read).  ``--recompute`` also times the cache-less baseline (full prefix re-run per token).
+``--ragged`` adds the same loop on a ragged session (one cache position per sequence) whose prompt lengths are
+spread over ``[prompt / 4, prompt]`` with a fixed seed: ms/step and tok/s beside the uniform figures.
 Random-init weights, synthetic prompts; one JSON line per configuration.
 
     python benchmarks/decode_bench.py --model gpt2-small --batch 1 8 64 --prompt 128 --tokens 256
@@ -33,6 +35,27 @@ def time_decode(sess, ids, prompt_len, tokens):
     return (time.perf_counter() - t0) / tokens
 
 
+def ragged_lengths(batch, prompt):
+    """Prompt lengths over [prompt / 4, prompt], fixed seed; the longest is ``prompt`` itself."""
+    g = torch.Generator().manual_seed(1234)
+    n = torch.randint(max(1, prompt // 4), prompt + 1, (batch,), generator=g).tolist()
+    n[0] = prompt
+    return n
+
+
+def time_decode_ragged(sess, ids, lengths, tokens):
+    sess.reset()
+    sess.prefill(ids[:, : max(lengths)], lengths)
+    nxt = ids[:, -1]
+    sess.decode(nxt)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(tokens):
+        sess.decode(nxt)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / tokens
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="gpt2-small")
@@ -41,6 +64,8 @@ def main():
     ap.add_argument("--tokens", type=int, default=256)
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--recompute", action="store_true")
+    ap.add_argument("--ragged", action="store_true",
+                    help="also time a ragged session: prompt lengths spread over [prompt/4, prompt]")
     a = ap.parse_args()
     cfg = get_preset(a.model)
     torch.manual_seed(0)
@@ -88,6 +113,14 @@ def main():
                 "attn_kv_GBps": round(kv_bytes / t_attn / 1e9, 1),
                 "cache_len": L,
             }
+            if a.ragged:
+                lengths = ragged_lengths(B, a.prompt)
+                rs = DecodeSession(model, B, max_len=max_len, use_graph=not a.no_graph, ragged=True)
+                t_rag = time_decode_ragged(rs, ids, lengths, a.tokens)
+                out["ragged_prompt_min_mean_max"] = [min(lengths), round(sum(lengths) / B, 1), max(lengths)]
+                out["ragged_decode_ms_per_step"] = round(t_rag * 1e3, 4)
+                out["ragged_decode_tok_s"] = round(B / t_rag, 1)
+                del rs
             if a.recompute:
                 n = 16
                 ctx = ids[:, : a.prompt]

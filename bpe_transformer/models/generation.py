@@ -29,6 +29,29 @@ sequence, so a 288 GB MI355X holds thousands of sequences.
 
 On the CPU, in fp32, or with the reference ablations (post-norm, no RMSNorm,
 non-SwiGLU FFN) the same session runs the oracle math over the same cache.
+
+**Ragged batches** (``DecodeSession(..., ragged=True)``): the position is one
+int32 per sequence (``cache.pos [B]``, host mirror ``cache.lengths``), and every
+kernel above places, rotates and attends sequence ``b`` from ``pos[b]``.  So
+
+* ``prefill(ids, lengths)`` takes right-padded prompts of different lengths and
+  returns each sequence's logits after its own last token.  On an empty cache
+  it is still one causal flash prefill over the padded window plus one
+  ``kv_append`` (right padding under a causal mask cannot reach a valid token),
+  with the hidden rows gathered at ``lengths - 1`` before the LM head.
+* ``decode(ids, active)`` advances only the active sequences: inside the
+  captured graph the step is ``pos += step`` with ``step`` a static device
+  int32 ``[B]`` filled before the replay, so the graph is still captured once.
+* ``reset_slot(b)`` / ``prefill_slot(b, ids)`` give one slot to a new request
+  while the others go on: the single-sequence prefill runs on the views
+  ``cache.k[:, b:b+1]``, ``cache.v[:, b:b+1]``, ``cache.pos[b:b+1]`` (contiguous
+  slabs in the layout above, same addresses, so the graph stays valid).
+* ``generate`` takes a list of 1-D prompts and returns a list of 1-D tensors,
+  each ending with its first EOS; a finished sequence becomes inactive.
+
+Cache rows at and past ``pos[b]`` may hold pad-token (or inactive-step) values.
+They are never visible -- every read of sequence ``b`` stops at ``pos[b]`` plus
+its own new tokens -- and are overwritten as the sequence grows.
 """
 
 from __future__ import annotations
@@ -59,21 +82,32 @@ def _gemv_ok(m: int, k: int) -> bool:
 
 
 class KVCache:
-    """Per-layer K/V caches ``[L, B, Hkv, Lmax, D]`` plus the device-side fill position."""
+    """Per-layer K/V caches ``[L, B, Hkv, Lmax, D]`` plus the device-side fill position: one int32 shared by the
+    batch, or with ``ragged`` one per sequence (``pos [B]``, host mirror ``lengths``)."""
 
     def __init__(self, num_layers: int, batch: int, num_kv_heads: int, max_len: int, head_dim: int, device=None,
-                 dtype=torch.bfloat16):
+                 dtype=torch.bfloat16, ragged: bool = False):
         shape = (num_layers, batch, num_kv_heads, max_len, head_dim)
         self.k = torch.zeros(shape, device=device, dtype=dtype)
         self.v = torch.zeros(shape, device=device, dtype=dtype)
-        self.pos = torch.zeros(1, device=device, dtype=torch.int32)  # tokens already cached
-        self.length = 0  # host mirror of pos (the host never reads pos back)
+        self.ragged = ragged
+        self.pos = torch.zeros(batch if ragged else 1, device=device, dtype=torch.int32)  # tokens already cached
+        self.length = 0  # host mirror of pos (the host never reads pos back); ragged: the longest sequence
+        self.lengths = [0] * batch if ragged else None  # ragged: host mirror of pos, per sequence
         self.max_len = max_len
         self.batch = batch
 
     def reset(self) -> None:
         self.pos.zero_()
         self.length = 0
+        if self.ragged:
+            self.lengths = [0] * self.batch
+
+    def advance(self, rows, steps) -> None:
+        """Ragged host mirror: sequence ``rows[i]`` grew by ``steps[i]`` tokens."""
+        for r, n in zip(rows, steps):
+            self.lengths[r] += int(n)
+        self.length = max(self.lengths)
 
     def nbytes(self) -> int:
         return 2 * self.k.numel() * self.k.element_size()
@@ -99,10 +133,15 @@ class DecodeSession:
 
     ``prefill(ids [B, T])`` and ``decode(ids [B])`` return the next-token logits ``[B, V]`` of the last position.
     With ``use_graph`` (GPU only) the decode step is captured into a HIP graph on first use and replayed after.
+
+    With ``ragged`` every sequence has its own position: ``prefill`` takes right-padded ``ids`` with host ``lengths``,
+    ``decode`` an ``active`` mask, ``reset_slot`` / ``prefill_slot`` hand one slot to a new request, and ``generate``
+    takes a list of prompts of different lengths (module docstring).
     """
 
-    def __init__(self, model, batch: int, max_len: int | None = None, use_graph: bool = True):
+    def __init__(self, model, batch: int, max_len: int | None = None, use_graph: bool = True, ragged: bool = False):
         self.model = model
+        self.ragged = ragged
         cfg = model.config
         self.batch = batch
         self.max_len = max_len or model.context_length
@@ -115,7 +154,10 @@ class DecodeSession:
             assert self.max_len <= attn.rope.max_seq_len, "KV cache longer than the RoPE table (context_length)"
         p = model.lm_head.weight
         self.device = p.device
-        self.cache = KVCache(len(model.layers), batch, self.Hkv, self.max_len, self.D, self.device, p.dtype)
+        self.cache = KVCache(len(model.layers), batch, self.Hkv, self.max_len, self.D, self.device, p.dtype, ragged)
+        # ragged: per-sequence advance of the decode step (1 = active), static so that the captured graph reads it
+        self._step = torch.ones(batch, device=self.device, dtype=torch.int32) if ragged else None
+        self._step_host = [1] * batch  # what _step holds
         self.fast = self._fast_ok()
         self.use_graph = use_graph and self.fast
         self._graph = None
@@ -161,11 +203,20 @@ class DecodeSession:
 
     # ------------------------------------------------------------------ public API
     @torch.no_grad()
-    def prefill(self, ids: Tensor) -> Tensor:
-        """Append ``ids [B, T]`` to the cache; returns the logits ``[B, V]`` after the last token."""
+    def prefill(self, ids: Tensor, lengths=None) -> Tensor:
+        """Append ``ids [B, T]`` to the cache; returns the logits ``[B, V]`` after the last token.
+
+        Ragged sessions: ``ids`` is right-padded and ``lengths [B]`` (host ints, ``1 <= lengths[b] <= T``, default
+        ``T``) says how many tokens of each row count; row ``b`` of the result are the logits after token
+        ``lengths[b] - 1``."""
         ids = ids.to(self.device)
         B, T = ids.shape
         assert B == self.batch, f"session batch is {self.batch}, got {B}"
+        if self.ragged:
+            n = [T] * B if lengths is None else [int(x) for x in lengths]
+            assert len(n) == B and all(1 <= x <= T for x in n), "lengths: one int in [1, T] per sequence"
+            return self._append(ids, n, list(range(B)))
+        assert lengths is None, "per-sequence lengths need DecodeSession(..., ragged=True)"
         assert self.cache.length + T <= self.max_len, "KV cache full"
         if self.fast and self.cache.length == 0 and T > 1:
             out = self._forward_fast(ids, prefill=True)
@@ -182,8 +233,14 @@ class DecodeSession:
         return out
 
     @torch.no_grad()
-    def decode(self, ids: Tensor) -> Tensor:
-        """Append one token per sequence (``ids [B]``); returns the next logits ``[B, V]``."""
+    def decode(self, ids: Tensor, active=None) -> Tensor:
+        """Append one token per sequence (``ids [B]``); returns the next logits ``[B, V]``.
+
+        Ragged sessions: ``active`` (bool ``[B]``, default all) -- an inactive sequence is fed as usual, but its
+        position does not advance and its logits are unspecified."""
+        if self.ragged:
+            return self._decode_ragged(ids, active)
+        assert active is None, "an active mask needs DecodeSession(..., ragged=True)"
         assert self.cache.length + 1 <= self.max_len, "KV cache full"
         ids = ids.reshape(self.batch, 1).to(self.device)
         if not self.use_graph:
@@ -197,10 +254,98 @@ class DecodeSession:
         self.cache.length += 1
         return out
 
+    def _decode_ragged(self, ids: Tensor, active) -> Tensor:
+        B = self.batch
+        act = [True] * B if active is None else [bool(a) for a in torch.as_tensor(active).reshape(-1).tolist()]
+        assert len(act) == B, "active: one flag per sequence"
+        rows = list(range(B))
+        step = [int(a) for a in act]
+        assert all(self.cache.lengths[b] + step[b] <= self.max_len for b in rows), "KV cache full"
+        ids = ids.reshape(B, 1).to(self.device)
+        if not self.fast:
+            out = self._forward_reference_ragged(ids, step, rows)
+        else:
+            if step != self._step_host:  # (the mask changes only when a sequence finishes or a slot is refilled)
+                self._step.copy_(torch.tensor(step, dtype=torch.int32))
+                self._step_host = step
+            if not self.use_graph:
+                out = self._forward_fast(ids, prefill=False, step=self._step)
+            else:
+                if self._graph is None:
+                    self._capture()
+                self._static_ids.copy_(ids)
+                self._graph.replay()
+                out = self._static_logits.clone()
+        self.cache.advance(rows, step)
+        return out
+
     @torch.no_grad()
-    def generate(self, prompt: Tensor, max_new_tokens: int, temperature: float = 1.0, top_p: float | None = None,
-                 eos_token_id: int | None = None, generator: torch.Generator | None = None) -> Tensor:
-        """``prompt [B, S]`` -> ``[B, S + n]`` (stops early once every row emitted ``eos_token_id``)."""
+    def reset_slot(self, b: int) -> None:
+        """Ragged sessions: empty slot ``b`` for a new request; the other sequences are untouched."""
+        assert self.ragged, "slots need DecodeSession(..., ragged=True)"
+        self.cache.pos[b : b + 1].zero_()
+        self.cache.lengths[b] = 0
+        self.cache.length = max(self.cache.lengths)
+
+    @torch.no_grad()
+    def prefill_slot(self, b: int, ids: Tensor) -> Tensor:
+        """Ragged sessions: append ``ids [T]`` to sequence ``b`` alone (the single-sequence prefill on that slot's
+        slabs of the cache); returns its logits ``[1, V]``.  Positions and cache rows of the other slots do not
+        change, and neither do any addresses, so a captured decode graph stays valid."""
+        assert self.ragged, "slots need DecodeSession(..., ragged=True)"
+        ids = ids.reshape(1, -1).to(self.device)
+        return self._append(ids, [ids.shape[1]], [b])
+
+    def _append(self, ids: Tensor, n: list[int], rows: list[int]) -> Tensor:
+        """Ragged prefill: the first ``n[i]`` tokens of ``ids[i]`` (right-padded) go to sequence ``rows[i]`` -- the
+        whole batch, or one slot.  Returns every sequence's logits after its last valid token."""
+        cur = [self.cache.lengths[r] for r in rows]
+        assert all(c + x <= self.max_len for c, x in zip(cur, n)), "KV cache full"
+        ids = ids[:, : max(n)]
+        B, T = ids.shape
+        if not self.fast:
+            out = self._forward_reference_ragged(ids, n, rows)
+        else:
+            c = self.cache
+            kv = (c.k, c.v, c.pos) if len(rows) == self.batch else \
+                (c.k[:, rows[0] : rows[0] + 1], c.v[:, rows[0] : rows[0] + 1], c.pos[rows[0] : rows[0] + 1])
+            dev_i32 = lambda v: torch.tensor(v, dtype=torch.int32).to(self.device)  # noqa: E731
+            if max(cur) == 0 and T > 1:
+                # empty cache: causal flash prefill over the padded window + one kv_append; a pad token sits to the
+                # right of every valid one, so no valid token sees it, and its cache rows lie at or past pos[b]
+                last = torch.tensor([x - 1 for x in n]).to(self.device)
+                out = self._forward_fast(ids, prefill=True, step=dev_i32(n), last=last, kv=kv)
+            else:
+                # filled cache: chunks of up to 8 / G tokens; sequence b advances by the part of its remaining
+                # length that falls in the chunk, and its logits come from the chunk holding its last valid token
+                out = None
+                chunk = max(1, 8 // (self.H // self.Hkv))
+                for t0 in range(0, T, chunk):
+                    w = min(chunk, T - t0)
+                    part = [min(max(x - t0, 0), w) for x in n]
+                    last = torch.tensor([max(p - 1, 0) for p in part]).to(self.device)
+                    lg = self._forward_fast(ids[:, t0 : t0 + w], prefill=False, step=dev_i32(part), last=last, kv=kv)
+                    if out is None:
+                        out = lg
+                    else:
+                        here = [i for i, x in enumerate(n) if t0 < x]  # sequences with a valid token in this chunk
+                        if len(here) == B:
+                            out = lg
+                        else:
+                            out[here] = lg[here]
+        self.cache.advance(rows, n)
+        return out
+
+    @torch.no_grad()
+    def generate(self, prompt, max_new_tokens: int, temperature: float = 1.0, top_p: float | None = None,
+                 eos_token_id: int | None = None, generator: torch.Generator | None = None):
+        """``prompt [B, S]`` -> ``[B, S + n]`` (stops early once every row emitted ``eos_token_id``).
+
+        Ragged sessions also take a list of ``B`` 1-D prompts of different lengths and return a list of 1-D tensors:
+        each prompt plus its continuation, ending with the first ``eos_token_id`` if one was emitted.  A sequence
+        that has emitted EOS becomes inactive; the loop ends when all are done or at ``max_new_tokens``."""
+        if isinstance(prompt, (list, tuple)):
+            return self._generate_ragged(prompt, max_new_tokens, temperature, top_p, eos_token_id, generator)
         self.reset()
         logits = self.prefill(prompt)
         outs = [prompt.to(self.device)]
@@ -217,6 +362,34 @@ class DecodeSession:
                 logits = self.decode(nxt)
         return torch.cat(outs, 1)
 
+    def _generate_ragged(self, prompts, max_new_tokens, temperature, top_p, eos_token_id, generator) -> list[Tensor]:
+        assert self.ragged, "a list of prompts needs DecodeSession(..., ragged=True)"
+        B = self.batch
+        assert len(prompts) == B, f"session batch is {B}, got {len(prompts)} prompts"
+        prompts = [p.reshape(-1).to(self.device) for p in prompts]
+        n = [int(p.numel()) for p in prompts]
+        assert min(n) >= 1, "empty prompt"
+        ids = torch.zeros(B, max(n), dtype=torch.long, device=self.device)  # right-padded (the pad id is never seen)
+        for b, p in enumerate(prompts):
+            ids[b, : n[b]] = p
+        self.reset()
+        logits = self.prefill(ids, n)
+        new: list[list[int]] = [[] for _ in range(B)]
+        done = [False] * B
+        for i in range(max_new_tokens):
+            nxt = _sample(logits, temperature, top_p, generator)
+            for b, tok in enumerate(nxt.tolist()):
+                if not done[b]:
+                    new[b].append(tok)
+                    done[b] = eos_token_id is not None and tok == eos_token_id
+            if all(done):
+                break
+            if i + 1 < max_new_tokens:
+                logits = self.decode(nxt, active=[not d for d in done])
+                if any(done):  # an inactive row's logits are unspecified: keep the sampler's input finite
+                    logits[[b for b in range(B) if done[b]]] = 0.0
+        return [torch.cat([p, torch.tensor(t, dtype=p.dtype, device=self.device)]) for p, t in zip(prompts, new)]
+
     # ------------------------------------------------------------------ HIP path
     def _capture(self) -> None:
         """Capture one decode step (all layers + LM head) into a HIP graph.  The warm-up run writes the cache at
@@ -226,18 +399,22 @@ class DecodeSession:
         s = torch.cuda.Stream(device=self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):
-            self._forward_fast(self._static_ids, prefill=False)
+            self._forward_fast(self._static_ids, prefill=False, step=self._step)
         torch.cuda.current_stream(self.device).wait_stream(s)
         self.cache.pos.copy_(pos0)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self._static_logits = self._forward_fast(self._static_ids, prefill=False)
+            self._static_logits = self._forward_fast(self._static_ids, prefill=False, step=self._step)
         self.cache.pos.copy_(pos0)  # capture does not execute, but keep the invariant explicit
         self._graph = g
 
-    def _forward_fast(self, ids: Tensor, prefill: bool) -> Tensor:
+    def _forward_fast(self, ids: Tensor, prefill: bool, step: Tensor | None = None, last: Tensor | None = None,
+                      kv=None) -> Tensor:
+        """``step`` (ragged): device int32 advance per sequence instead of ``T``; ``last`` (ragged): index of the
+        token whose logits each sequence returns instead of ``T - 1``; ``kv``: the (k, v, pos) to run on -- the
+        session's cache, or one slot's views of it."""
         if not prefill and ids.shape[1] == 1 and ids.shape[0] <= _GEMV_MAX_BATCH and self._gemv_fits(ids.shape[0]):
-            return self._decode_gemv(ids)
+            return self._decode_gemv(ids, step, kv)
         from ..ops._ext import ops as hip
 
         h = hip()
@@ -245,7 +422,7 @@ class DecodeSession:
         B, T = ids.shape
         H, Hkv, D = self.H, self.Hkv, self.D
         scale = 1.0 / math.sqrt(D)
-        kc, vc, pos = self.cache.k, self.cache.v, self.cache.pos
+        kc, vc, pos = kv if kv is not None else (self.cache.k, self.cache.v, self.cache.pos)
         use_rope = self._cos is not None
         cos = self._cos if use_rope else kc.new_empty(0, dtype=torch.float32)
         sin = self._sin if use_rope else kc.new_empty(0, dtype=torch.float32)
@@ -268,20 +445,24 @@ class DecodeSession:
             xr, h2, _ = h.add_rmsnorm_fwd(xr, g1, ln2, eps)
             a = h.swiglu_fwd(torch.matmul(h2, w13.t()))
             xd = torch.matmul(a, w2.t())
-        if T > 1:  # only the last position's logits are needed
+        if T > 1 and last is not None:  # ragged: each sequence's own last valid token
+            rows = torch.arange(B, device=last.device)
+            xr = xr.view(B, T, -1)[rows, last].contiguous()
+            xd = xd.view(B, T, -1)[rows, last].contiguous()
+        elif T > 1:  # only the last position's logits are needed
             xr = xr.view(B, T, -1)[:, -1].contiguous()
             xd = xd.view(B, T, -1)[:, -1].contiguous()
         fin = m.ln_final
         _, hf, _ = h.add_rmsnorm_fwd(xr, xd, fin.weight, fin.eps)
         logits = torch.matmul(hf, m.lm_head.weight.t())
-        pos.add_(T)
+        pos.add_(T if step is None else step)
         return logits
 
     def _gemv_fits(self, m: int) -> bool:
         cfg = self.model.config
         return all(_gemv_ok(m, k) for k in (cfg.d_model, self.H * self.D, self._w[0][5].shape[1]))
 
-    def _decode_gemv(self, ids: Tensor) -> Tensor:
+    def _decode_gemv(self, ids: Tensor, step: Tensor | None = None, kv=None) -> Tensor:
         """Decode step for batch <= 16 on the fused skinny-GEMM kernels (``csrc/decode_gemv.hip``): per layer
         qkv (+RMSNorm, +RoPE, +cache write) -> split-K decode attention -> Wo (+ the split combine) -> [W1; W3]
         (+residual add, +RMSNorm, +SwiGLU) -> W2; the residual add of W2's output is folded into the next layer's
@@ -292,7 +473,7 @@ class DecodeSession:
         m = self.model
         H = self.H
         scale = 1.0 / math.sqrt(self.D)
-        kc, vc, pos = self.cache.k, self.cache.v, self.cache.pos
+        kc, vc, pos = kv if kv is not None else (self.cache.k, self.cache.v, self.cache.pos)
         use_rope = self._cos is not None
         cos = self._cos if use_rope else kc.new_empty(0, dtype=torch.float32)
         sin = self._sin if use_rope else kc.new_empty(0, dtype=torch.float32)
@@ -308,7 +489,7 @@ class DecodeSession:
             xd, _ = h.decode_gemv(a, None, None, 0.0, w2, 0)
         fin = m.ln_final
         logits, _ = h.decode_gemv(xr, xd, fin.weight, fin.eps, m.lm_head.weight, 0)
-        pos.add_(1)
+        pos.add_(1 if step is None else step)
         return logits
 
     # ------------------------------------------------------------------ oracle path
@@ -349,4 +530,54 @@ class DecodeSession:
                 x = x + layer.ffn(layer.ln2(x))
         logits = m.lm_head(m.ln_final(x[:, -1]))
         self.cache.pos.add_(T)
+        return logits
+
+    def _forward_reference_ragged(self, ids: Tensor, n: list[int], rows: list[int]) -> Tensor:
+        """The oracle math with per-sequence positions: ``ids [len(rows), T]`` (right-padded), of which the first
+        ``n[i]`` tokens are appended to sequence ``rows[i]`` at its own position (RoPE positions and visibility per
+        sequence).  Returns the logits after each sequence's last valid token (token 0 where ``n[i] == 0``: an
+        inactive decode step, unspecified).  Pad tokens are written at and past the new position, where nothing
+        reads them, or dropped at the end of the cache."""
+        m = self.model
+        R, T = ids.shape
+        H, Hkv, D, Lmax = self.H, self.Hkv, self.D, self.max_len
+        dev = ids.device
+        cur = [self.cache.lengths[r] for r in rows]
+        p0 = torch.tensor(cur, device=dev)
+        Lk = min(max(cur) + T, Lmax)
+        tp = p0[:, None] + torch.arange(T, device=dev)[None, :]  # [R, T] absolute positions
+        mask = (torch.arange(Lk, device=dev)[None, None, :] <= tp[:, :, None])[:, None]  # [R, 1, T, Lk]
+        tpr = tp.clamp(max=Lmax - 1)[:, None, :]  # (a pad token past the cache has no table row; it is dropped)
+        x = m.token_embeddings(ids)
+        for li, layer in enumerate(m.layers):
+            attn = layer.attn
+
+            def attend(z: Tensor) -> Tensor:
+                q = attn.q_proj(z).view(R, T, H, D).transpose(1, 2)
+                k = attn.k_proj(z).view(R, T, Hkv, D).transpose(1, 2)
+                v = attn.v_proj(z).view(R, T, Hkv, D).transpose(1, 2)
+                if attn.rope is not None:
+                    q = attn.rope(q, tpr)
+                    k = attn.rope(k, tpr)
+                for i, r in enumerate(rows):
+                    w = max(0, min(T, Lmax - cur[i]))
+                    self.cache.k[li, r, :, cur[i] : cur[i] + w] = k[i, :, :w].to(self.cache.k.dtype)
+                    self.cache.v[li, r, :, cur[i] : cur[i] + w] = v[i, :, :w].to(self.cache.v.dtype)
+                kk = self.cache.k[li, rows, :, :Lk].to(q.dtype)
+                vv = self.cache.v[li, rows, :, :Lk].to(q.dtype)
+                if Hkv != H:
+                    kk = kk.repeat_interleave(H // Hkv, dim=1)
+                    vv = vv.repeat_interleave(H // Hkv, dim=1)
+                o = F.scaled_dot_product_attention(q, kk, vv, mask)
+                return attn.output_proj(o.transpose(1, 2).reshape(R, T, H * D))
+
+            if layer.use_post_norm:
+                x = layer.ln1(x + attend(x))
+                x = layer.ln2(x + layer.ffn(x))
+            else:
+                x = x + attend(layer.ln1(x))
+                x = x + layer.ffn(layer.ln2(x))
+        last = torch.tensor([max(c - 1, 0) for c in n], device=dev)
+        logits = m.lm_head(m.ln_final(x[torch.arange(R, device=dev), last]))
+        self.cache.pos[rows] += torch.tensor(n, dtype=torch.int32, device=dev)
         return logits

@@ -190,7 +190,22 @@ class TransformerLM(nn.Module):
         With ``use_cache`` (and prompt + new tokens within ``context_length``) decoding runs through a KV-cache
         :class:`~bpe_transformer.models.generation.DecodeSession` (HIP-graph-captured decode step on the GPU);
         otherwise every step re-runs the model on the last ``context_length`` tokens.
+
+        A list of 1-D prompts of different lengths is served as one ragged batch (every sequence at its own cache
+        position) and returns a list of 1-D tensors, each its prompt plus its continuation up to and including its
+        first ``eos_token_id``.
         """
+        if isinstance(prompt, (list, tuple)):
+            self._fence(self)
+            longest = max(int(p.numel()) for p in prompt)
+            if use_cache and longest + max_new_tokens <= self.context_length and max_new_tokens > 0:
+                from .generation import DecodeSession
+
+                sess = DecodeSession(self, len(prompt), max_len=longest + max_new_tokens, ragged=True)
+                return sess.generate(list(prompt), max_new_tokens, temperature, top_p, eos_token_id, generator)
+            # without the cache: one sequence at a time through the loop below (which stops at its EOS)
+            return [self.generate(p.reshape(-1), max_new_tokens, temperature, top_p, eos_token_id, generator, use_cache)
+                    for p in prompt]
         squeeze = prompt.dim() == 1
         ids = prompt.unsqueeze(0) if squeeze else prompt
         self._fence(self)  # the decode session packs / reads every weight up front

@@ -39,8 +39,8 @@ constexpr int CH = 256;  // keys per chunk (= threads per workgroup)
 template <int D, int MR>
 __global__ void __launch_bounds__(256) decode_attn_kernel(const __bf16* __restrict__ q, const __bf16* __restrict__ Kc,
                                                           const __bf16* __restrict__ Vc, float* __restrict__ part,
-                                                          const int* __restrict__ pos, int H, int Hkv, int Lmax,
-                                                          int nsplit, float scale, int T) {
+                                                          const int* __restrict__ pos, int pstride, int H, int Hkv,
+                                                          int Lmax, int nsplit, float scale, int T) {
     constexpr int DV = D / 8;     // 16-byte vectors per row
     constexpr int KP = 256 / DV;  // key partitions of the P.V step
     __shared__ float qs[MR][D];
@@ -51,7 +51,7 @@ __global__ void __launch_bounds__(256) decode_attn_kernel(const __bf16* __restri
     const int bk = blockIdx.x / nsplit, split = blockIdx.x % nsplit;  // bk = b * Hkv + hk
     const int b = bk / Hkv, hk = bk % Hkv;
     const int G = H / Hkv, R = G * T;
-    const int p0 = pos[0];
+    const int p0 = pos[b * pstride];  // pstride 0: one position for the batch, 1: one per sequence (uniform: one b)
     const int L = min(p0 + T, Lmax);  // keys any row of this workgroup may see
     const int s0 = split * CH;
     // partial slot of row r: part[(((b * T + t) * H + h) * nsplit + split) * (D + 2)]
@@ -205,13 +205,15 @@ __global__ void __launch_bounds__(256) kv_append_kernel(const __bf16* __restrict
                                                         __bf16* __restrict__ qo, __bf16* __restrict__ Kc,
                                                         __bf16* __restrict__ Vc, const float* __restrict__ cosT,
                                                         const float* __restrict__ sinT, const int* __restrict__ pos,
-                                                        int T, int H, int Hkv, int D, int Lmax, long total) {
+                                                        int pstride, int T, int H, int Hkv, int D, int Lmax,
+                                                        long total) {
     const int dv = D / 8, W = (H + 2 * Hkv) * dv;
-    const int p0 = pos[0];
+    const int pshared = pos[0];
     for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
         const long r = idx / W;
         const int c = (int)(idx % W), hh = c / dv, d0 = (c % dv) * 8;
-        const int b = (int)(r / T), p = p0 + (int)(r % T);
+        const int b = (int)(r / T);
+        const int p = (pstride ? pos[b] : pshared) + (int)(r % T);  // per sequence, and so is the drop below
         if (p >= Lmax) continue;  // cache full: nothing is written past the end
         u16x8 x = *reinterpret_cast<const u16x8*>(qkv + r * ld + (long)hh * D + d0);
         if (hh < H + Hkv && cosT != nullptr) {
@@ -246,14 +248,14 @@ bool decode_attn_ok(int H, int Hkv, int D, int T) {
 }
 
 template <int D>
-static void launch_d(const void* q, const void* k, const void* v, float* part, void* out, const int* pos, int B,
-                     int T, int H, int Hkv, int Lmax, float scale, hipStream_t s) {
+static void launch_d(const void* q, const void* k, const void* v, float* part, void* out, const int* pos,
+                     int pstride, int B, int T, int H, int Hkv, int Lmax, float scale, hipStream_t s) {
     const int ns = decode_attn_splits(Lmax);
     const int grid = B * Hkv * ns;
     const int R = (H / Hkv) * T;
 #define DEC(MR)                                                                                                   \
     decode_attn_kernel<D, MR><<<grid, 256, 0, s>>>((const __bf16*)q, (const __bf16*)k, (const __bf16*)v, part, pos, \
-                                                   H, Hkv, Lmax, ns, scale, T)
+                                                   pstride, H, Hkv, Lmax, ns, scale, T)
     if (R <= 1) DEC(1);
     else if (R <= 2) DEC(2);
     else if (R <= 4) DEC(4);
@@ -262,17 +264,17 @@ static void launch_d(const void* q, const void* k, const void* v, float* part, v
     if (out != nullptr) decode_combine_kernel<D><<<B * T * H, D, 0, s>>>(part, (__bf16*)out, ns);
 }
 
-void launch_decode_attn(const void* q, const void* k, const void* v, float* part, void* out, const int* pos, int B,
-                        int T, int H, int Hkv, int D, int Lmax, float scale, hipStream_t s) {
-    if (D == 64) launch_d<64>(q, k, v, part, out, pos, B, T, H, Hkv, Lmax, scale, s);
-    else launch_d<128>(q, k, v, part, out, pos, B, T, H, Hkv, Lmax, scale, s);
+void launch_decode_attn(const void* q, const void* k, const void* v, float* part, void* out, const int* pos,
+                        int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax, float scale, hipStream_t s) {
+    if (D == 64) launch_d<64>(q, k, v, part, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, s);
+    else launch_d<128>(q, k, v, part, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, s);
 }
 
 void launch_kv_append(const void* qkv, long ld, void* qo, void* Kc, void* Vc, const float* cosT, const float* sinT,
-                      const int* pos, int B, int T, int H, int Hkv, int D, int Lmax, hipStream_t s) {
+                      const int* pos, int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax, hipStream_t s) {
     const long total = (long)B * T * (H + 2 * Hkv) * (D / 8);
     const long want = (total + 255) / 256;
     const int grid = (int)(want < 8192 ? want : 8192);
     kv_append_kernel<<<grid, 256, 0, s>>>((const __bf16*)qkv, ld, (__bf16*)qo, (__bf16*)Kc, (__bf16*)Vc, cosT, sinT,
-                                          pos, T, H, Hkv, D, Lmax, total);
+                                          pos, pos_stride, T, H, Hkv, D, Lmax, total);
 }

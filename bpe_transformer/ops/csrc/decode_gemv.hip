@@ -8,7 +8,8 @@
 //   epilogue  0: y = h W^T                                   (output projection, W2, LM head)
 //             1: y[:, j] = silu(g_j) * u_j over [W1; W3]    (SwiGLU; rows j and F + j in one wave)
 //             2: fused-QKV with RoPE at the device-side position and the K / V cache write (rows n, n + 1 of
-//                a rotation pair in one wave) -- replaces the separate kv_append launch.
+//                a rotation pair in one wave) -- replaces the separate kv_append launch.  The position is shared
+//                by the batch or one per row (GemvArgs::pos_stride; row m = sequence m).
 // Rounding matches the training kernels exactly (bf16 residual sum, (s * rstd) * g, bf16 GEMM outputs before
 // SwiGLU / RoPE), so decode logits agree with the model's forward pass.
 //
@@ -97,7 +98,9 @@ __device__ __forceinline__ void gemv_prologue_rows(const GemvArgs& a, u16* hs, i
     }
 }
 
-template <int MM, int EPI>
+// RAG (epilogue 2 only): one position per row (GemvArgs::pos_stride == 1).  A template switch, so that the
+// shared-position instantiation is the code it was before positions could differ.
+template <int MM, int EPI, bool RAG = false>
 __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
     extern __shared__ __attribute__((aligned(16))) u16 hs[];  // [MM][K] normalized input rows (bf16)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -189,8 +192,36 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
 #pragma unroll
         for (int m = 0; m < MM; ++m) other[m] = __shfl_xor(acc[m], LPR);
         const int D = a.D, H = a.H, Hkv = a.Hkv;
-        const int hh = n / D, d = n % D, p = a.pos[0];
+        const int hh = n / D, d = n % D;
         const bool rot = a.cosT != nullptr && hh < H + Hkv;
+        if constexpr (RAG) {
+            // one position per sequence (row m = sequence m): the table lookup, the cache row and the full-cache
+            // test move into the row loop (statically unrolled over the MM accumulators); the shared-position
+            // path below keeps its single c / s load per output column
+            if (valid && l16 == 0) {
+#pragma unroll
+                for (int m = 0; m < MM; ++m) {
+                    if (m >= a.M) break;
+                    const int pm = a.pos[m];
+                    const float me = bf2f(f2bf(acc[m])), pa = bf2f(f2bf(other[m]));
+                    float v = me;
+                    if (rot && pm < a.Lmax) {  // a dropped row (pm >= Lmax) may be past the table: q unspecified
+                        const float cm = a.cosT[(long)pm * (D / 2) + d / 2], sm = a.sinT[(long)pm * (D / 2) + d / 2];
+                        v = (d & 1) ? pa * sm + me * cm : me * cm - pa * sm;
+                    }
+                    const u16 o = f2bf(v);
+                    if (hh < H) reinterpret_cast<u16*>(a.y)[(long)m * a.ldy + n] = o;
+                    else if (pm < a.Lmax) {
+                        const bool isk = hh < H + Hkv;
+                        const int hk = isk ? hh - H : hh - H - Hkv;
+                        u16* cache = reinterpret_cast<u16*>(isk ? a.kc : a.vc);
+                        cache[(((long)m * Hkv + hk) * a.Lmax + pm) * D + d] = o;
+                    }
+                }
+            }
+            return;
+        }
+        const int p = a.pos[0];
         float c = 1.f, s = 0.f;
         if (rot && valid) {
             c = a.cosT[(long)p * (D / 2) + d / 2];
@@ -224,7 +255,7 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
 // tokens at one k would otherwise hit the same banks).
 constexpr int MF_PF = 8;  // k-steps (32 each) of W in flight per wave
 
-template <int EPI>
+template <int EPI, bool RAG = false>
 __global__ void __launch_bounds__(256) gemv_mfma_kernel(const GemvArgs a) {
     extern __shared__ __attribute__((aligned(16))) u16 hs[];  // [M][K + 8] input rows, then float red[4][16][17]
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -307,10 +338,12 @@ __global__ void __launch_bounds__(256) gemv_mfma_kernel(const GemvArgs a) {
         const int nn = blockIdx.x * 16 + r;
         if (nn >= a.N) return;
         const int D = a.D, H = a.H, Hkv = a.Hkv;
-        const int hh = nn / D, d = nn % D, p = a.pos[0];
+        const int hh = nn / D, d = nn % D;
+        const int p = RAG ? a.pos[m] : a.pos[0];  // token column m is sequence m
         const float me = bf2f(f2bf(c)), pa = bf2f(f2bf(cp));
         float v = me;
-        if (a.cosT != nullptr && hh < H + Hkv) {
+        // (with one position per sequence a row at p >= Lmax is dropped and may be past the table: q unspecified)
+        if (a.cosT != nullptr && hh < H + Hkv && (!RAG || p < a.Lmax)) {
             const float cs = a.cosT[(long)p * (D / 2) + d / 2], sn = a.sinT[(long)p * (D / 2) + d / 2];
             v = (d & 1) ? pa * sn + me * cs : me * cs - pa * sn;
         }
@@ -346,20 +379,20 @@ bool gemv_ok(int M, int K) {
     return gemv_lds_bytes(M, K) <= 160 * 1024 || mfma_fits(M, K);
 }
 
-template <int MM, int EPI>
+template <int MM, int EPI, bool RAG>
 static void launch_mm(const GemvArgs& a, int grid, size_t lds, hipStream_t s) {
     if (lds > 64 * 1024)
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_kernel<MM, EPI>),
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_kernel<MM, EPI, RAG>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    gemv_kernel<MM, EPI><<<grid, 256, lds, s>>>(a);
+    gemv_kernel<MM, EPI, RAG><<<grid, 256, lds, s>>>(a);
 }
 
-template <int EPI>
+template <int EPI, bool RAG = false>
 static void launch_epi(const GemvArgs& a, int grid, size_t lds, hipStream_t s) {
-    if (a.M <= 1) launch_mm<1, EPI>(a, grid, lds, s);
-    else if (a.M <= 2) launch_mm<2, EPI>(a, grid, lds, s);
-    else if (a.M <= 4) launch_mm<4, EPI>(a, grid, lds, s);
-    else launch_mm<8, EPI>(a, grid, lds, s);
+    if (a.M <= 1) launch_mm<1, EPI, RAG>(a, grid, lds, s);
+    else if (a.M <= 2) launch_mm<2, EPI, RAG>(a, grid, lds, s);
+    else if (a.M <= 4) launch_mm<4, EPI, RAG>(a, grid, lds, s);
+    else launch_mm<8, EPI, RAG>(a, grid, lds, s);
 }
 
 // decode rows from which the MFMA variant runs (BPE_GEMV_MFMA_MIN_M, default 2)
@@ -371,24 +404,26 @@ static int mfma_min_m() {
     return v;
 }
 
-template <int EPI>
+template <int EPI, bool RAG = false>
 static void launch_mfma(const GemvArgs& a, int grid, hipStream_t s) {
     const size_t lds = gemv_mfma_lds_bytes(a.M, a.K);
     if (lds > 64 * 1024)
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_mfma_kernel<EPI>),
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_mfma_kernel<EPI, RAG>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    gemv_mfma_kernel<EPI><<<grid, 256, lds, s>>>(a);
+    gemv_mfma_kernel<EPI, RAG><<<grid, 256, lds, s>>>(a);
 }
 
 void launch_gemv(const GemvArgs& a, int epi, hipStream_t s) {
     if ((a.M >= mfma_min_m() || a.M > 8 || gemv_lds_bytes(a.M, a.K) > 160 * 1024) && mfma_fits(a.M, a.K)) {
         if (epi == 1) launch_mfma<1>(a, (a.N / 2 + 7) / 8, s);
+        else if (epi == 2 && a.pos_stride != 0) launch_mfma<2, true>(a, (a.N + 15) / 16, s);
         else if (epi == 2) launch_mfma<2>(a, (a.N + 15) / 16, s);
         else launch_mfma<0>(a, (a.N + 15) / 16, s);
         return;
     }
     const size_t lds = gemv_lds_bytes(a.M, a.K);
     if (epi == 1) launch_epi<1>(a, (a.N / 2 + 7) / 8, lds, s);
+    else if (epi == 2 && a.pos_stride != 0) launch_epi<2, true>(a, (a.N + 15) / 16, lds, s);
     else if (epi == 2) launch_epi<2>(a, (a.N + 15) / 16, lds, s);
     else launch_epi<0>(a, (a.N + 15) / 16, lds, s);
 }

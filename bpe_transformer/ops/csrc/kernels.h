@@ -150,13 +150,14 @@ struct FaArgs {
     const int* doc_start;
     const int* doc_end;
 };
-// decode_attn.hip (KV-cache serving path; `pos` = device int32 position of the first new token)
+// decode_attn.hip (KV-cache serving path; `pos` = device int32 position of the first new token: sequence b reads
+// pos[b * pos_stride], i.e. pos_stride 0 = one position shared by the batch, 1 = one per sequence)
 int decode_attn_splits(int Lmax);
 bool decode_attn_ok(int H, int Hkv, int D, int T);
-void launch_decode_attn(const void* q, const void* k, const void* v, float* part, void* out, const int* pos, int B,
-                        int T, int H, int Hkv, int D, int Lmax, float scale, hipStream_t s);
+void launch_decode_attn(const void* q, const void* k, const void* v, float* part, void* out, const int* pos,
+                        int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax, float scale, hipStream_t s);
 void launch_kv_append(const void* qkv, long ld, void* qo, void* Kc, void* Vc, const float* cosT, const float* sinT,
-                      const int* pos, int B, int T, int H, int Hkv, int D, int Lmax, hipStream_t s);
+                      const int* pos, int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax, hipStream_t s);
 
 // decode_gemv.hip (M <= 16 token rows; epi 0 plain, 1 SwiGLU over [W1; W3], 2 fused QKV + RoPE + KV-cache write)
 struct GemvArgs {
@@ -175,6 +176,7 @@ struct GemvArgs {
     const float* cosT;
     const float* sinT;
     const int* pos;
+    int pos_stride;    // row m is at pos[m * pos_stride] (0: shared position, 1: one per sequence)
     __bf16* kc;
     __bf16* vc;
     const float* part;  // optional prologue: x = merged decode-attention partials [M][H][nsplit][D + 2] (H, D)

@@ -1060,9 +1060,12 @@ void check_cache(const at::Tensor& c, int64_t B, int64_t Hkv, const char* name) 
     check_aligned(c, name);
 }
 
-void check_pos(const at::Tensor& pos) {
+// One position shared by the batch or one per sequence; returns the element stride between sequences (0 or 1).
+int check_pos(const at::Tensor& pos, int64_t B) {
     check_cuda(pos, "pos");
-    TORCH_CHECK(pos.scalar_type() == at::kInt && pos.numel() == 1, "kv cache: pos must be one device int32");
+    TORCH_CHECK(pos.scalar_type() == at::kInt && pos.is_contiguous() && (pos.numel() == 1 || pos.numel() == B),
+                "kv cache: pos must be a contiguous device int32 tensor of 1 or B (", B, ") elements");
+    return pos.numel() == 1 ? 0 : 1;
 }
 
 // qkv [B*T, (H + 2*Hkv)*D] rows of T new tokens at positions *pos.. -> roped q [B*T, H*D]; K (roped) and V are
@@ -1075,7 +1078,7 @@ at::Tensor kv_append(const at::Tensor& qkv, at::Tensor kc, at::Tensor vc, const 
     check_cache(kc, B, Hkv, "k_cache");
     check_cache(vc, B, Hkv, "v_cache");
     TORCH_CHECK(vc.sizes() == kc.sizes(), "kv_append: k / v cache shapes differ");
-    check_pos(pos);
+    const int pstride = check_pos(pos, B);
     if (use_rope)
         TORCH_CHECK(cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
                         sin.is_contiguous() && cos.size(0) >= Lmax && cos.size(1) == D / 2 && sin.sizes() == cos.sizes(),
@@ -1084,7 +1087,7 @@ at::Tensor kv_append(const at::Tensor& qkv, at::Tensor kc, at::Tensor vc, const 
     auto q = at::empty({B * T, H * D}, qkv.options());
     launch_kv_append(qkv.data_ptr(), qkv.stride(0), q.data_ptr(), kc.data_ptr(), vc.data_ptr(),
                      use_rope ? cos.data_ptr<float>() : nullptr, use_rope ? sin.data_ptr<float>() : nullptr,
-                     pos.data_ptr<int>(), (int)B, (int)T, (int)H, (int)Hkv, (int)D, (int)Lmax, cur_stream());
+                     pos.data_ptr<int>(), pstride, (int)B, (int)T, (int)H, (int)Hkv, (int)D, (int)Lmax, cur_stream());
     return q;
 }
 
@@ -1102,14 +1105,14 @@ at::Tensor decode_attn(const at::Tensor& q, const at::Tensor& kc, const at::Tens
     check_cache(kc, B, Hkv, "k_cache");
     check_cache(vc, B, Hkv, "v_cache");
     TORCH_CHECK(vc.sizes() == kc.sizes(), "decode_attn: k / v cache shapes differ");
-    check_pos(pos);
+    const int pstride = check_pos(pos, B);
     DevGuard g(q.device());
     const int ns = decode_attn_splits((int)Lmax);
     auto part = at::empty({B * T, H, ns, D + 2}, q.options().dtype(at::kFloat));
     auto out = combine ? at::empty({B * T, H * D}, q.options()) : at::Tensor();
     launch_decode_attn(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), part.data_ptr<float>(),
-                       combine ? out.data_ptr() : nullptr, pos.data_ptr<int>(), (int)B, (int)T, (int)H, (int)Hkv,
-                       (int)D, (int)Lmax, (float)scale, cur_stream());
+                       combine ? out.data_ptr() : nullptr, pos.data_ptr<int>(), pstride, (int)B, (int)T, (int)H,
+                       (int)Hkv, (int)D, (int)Lmax, (float)scale, cur_stream());
     return combine ? out : part;
 }
 
@@ -1207,7 +1210,7 @@ std::tuple<at::Tensor, at::Tensor> decode_qkv(const at::Tensor& x, const c10::op
     check_cache(vc, B, Hkv, "v_cache");
     TORCH_CHECK(vc.sizes() == kc.sizes(), "decode_qkv: k / v cache shapes differ");
     TORCH_CHECK(a.N == (H + 2 * Hkv) * D && D % 2 == 0, "decode_qkv: weight rows must be (H + 2*Hkv) * D");
-    check_pos(pos);
+    const int pstride = check_pos(pos, B);
     if (use_rope)
         TORCH_CHECK(cos.scalar_type() == at::kFloat && cos.is_contiguous() && sin.is_contiguous() &&
                         cos.size(0) >= Lmax && cos.size(1) == D / 2 && sin.sizes() == cos.sizes(),
@@ -1223,6 +1226,7 @@ std::tuple<at::Tensor, at::Tensor> decode_qkv(const at::Tensor& x, const c10::op
     a.cosT = use_rope ? cos.data_ptr<float>() : nullptr;
     a.sinT = use_rope ? sin.data_ptr<float>() : nullptr;
     a.pos = pos.data_ptr<int>();
+    a.pos_stride = pstride;
     a.kc = (__bf16*)kc.data_ptr();
     a.vc = (__bf16*)vc.data_ptr();
     launch_gemv(a, 2, cur_stream());

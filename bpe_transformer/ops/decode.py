@@ -18,6 +18,11 @@ whole prefix for every new token.
 
 Both read the position from device memory, so a decode step is shape-static and
 can be captured in a HIP graph.  The CPU versions are the oracle.
+
+``pos`` holds one int32 (a position shared by the batch) or one per sequence
+(``[B]``: ragged batches, every sequence at its own length).  With ``[B]``
+everything above holds per sequence: sequence ``b`` is placed, rotated, dropped
+at ``Lmax`` and attended from ``pos[b]``.
 """
 
 from __future__ import annotations
@@ -41,7 +46,17 @@ def kv_append(qkv: Tensor, k_cache: Tensor, v_cache: Tensor, cos: Tensor | None,
     return kv_append_reference(qkv, k_cache, v_cache, cos, sin, pos, batch, n_new, n_heads)
 
 
+def _per_sequence(pos: Tensor) -> bool:
+    """``pos`` is ``[B]`` (one position per sequence) rather than one shared element."""
+    return pos.numel() > 1
+
+
 def kv_append_reference(qkv, k_cache, v_cache, cos, sin, pos, batch, n_new, n_heads) -> Tensor:
+    if _per_sequence(pos):  # one sequence at a time on its slab of the caches (views: written in place)
+        assert pos.numel() == batch
+        rows = qkv.view(batch, n_new, -1)
+        return torch.cat([kv_append_reference(rows[b], k_cache[b : b + 1], v_cache[b : b + 1], cos, sin,
+                                              pos.reshape(-1)[b : b + 1], 1, n_new, n_heads) for b in range(batch)])
     _, Hkv, Lmax, D = k_cache.shape
     H = n_heads
     p0 = int(pos.reshape(-1)[0])
@@ -71,6 +86,11 @@ def decode_attention(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, n
 def decode_attention_reference(q, k_cache, v_cache, pos, n_heads, scale=None, n_new: int = 1) -> Tensor:
     B, Hkv, Lmax, D = k_cache.shape
     H, T = n_heads, n_new
+    if _per_sequence(pos):
+        assert pos.numel() == B
+        qr = q.view(B, T, -1)
+        return torch.cat([decode_attention_reference(qr[b], k_cache[b : b + 1], v_cache[b : b + 1],
+                                                     pos.reshape(-1)[b : b + 1], H, scale, T) for b in range(B)])
     p0 = int(pos.reshape(-1)[0])
     L = min(p0 + T, Lmax)
     scale = 1.0 / math.sqrt(D) if scale is None else scale
@@ -99,6 +119,10 @@ def decode_attention_partials(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: 
 def decode_partials_reference(q, k_cache, v_cache, pos, n_heads, scale=None, chunk: int = 256) -> Tensor:
     B, Hkv, Lmax, D = k_cache.shape
     H = n_heads
+    if _per_sequence(pos):
+        assert pos.numel() == B
+        return torch.cat([decode_partials_reference(q[b : b + 1], k_cache[b : b + 1], v_cache[b : b + 1],
+                                                    pos.reshape(-1)[b : b + 1], H, scale, chunk) for b in range(B)])
     L = min(int(pos.reshape(-1)[0]) + 1, Lmax)
     scale = 1.0 / math.sqrt(D) if scale is None else scale
     ns = (Lmax + chunk - 1) // chunk
@@ -164,7 +188,9 @@ def decode_qkv(x: Tensor, w: Tensor, k_cache: Tensor, v_cache: Tensor, cos: Tens
                pos: Tensor, n_heads: int, xd: Tensor | None = None, ln: Tensor | None = None,
                eps: float = 1e-5) -> tuple[Tensor, Tensor | None]:
     """Fused decode QKV: ``qkv = RMSNorm(x + xd) W^T`` for one new token per sequence, RoPE at the device-side
-    position, K / V written into the caches; returns ``(q [M, H*D], x + xd)``."""
+    position, K / V written into the caches; returns ``(q [M, H*D], x + xd)``.  With ``pos [M]`` row ``m`` is
+    sequence ``m`` at ``pos[m]``; a row at ``Lmax`` or past it writes nothing, and its query row is unspecified
+    (as for :func:`kv_append`)."""
     if x.is_cuda:
         use_rope = cos is not None
         c = cos if use_rope else x.new_empty(0, dtype=torch.float32)

@@ -30,9 +30,17 @@ sequence, so a 288 GB MI355X holds thousands of sequences.
 On the CPU, in fp32, or with the reference ablations (post-norm, no RMSNorm,
 non-SwiGLU FFN) the same session runs the oracle math over the same cache.
 
-**Ragged batches** (``DecodeSession(..., ragged=True)``): the position is one
-int32 per sequence (``cache.pos [B]``, host mirror ``cache.lengths``), and every
-kernel above places, rotates and attends sequence ``b`` from ``pos[b]``.  So
+**One engine, two position layouts.**  The host side is written once, as "the
+first ``n[i]`` tokens of ``ids[i]`` go to sequence ``rows[i]``", and every
+kernel above places, rotates and attends sequence ``b`` from ``pos[b * stride]``.
+The default session keeps one int32 for the whole batch (``cache.pos [1]``,
+stride 0) and always appends whole windows: ``n[i] == T``.  A step in which
+every sequence takes the whole window ends in ``pos += T`` and reads the logits
+of the last token, whatever the layout; only a step whose lengths really differ
+builds a device ``step`` / ``last`` pair.
+
+**Ragged batches** (``DecodeSession(..., ragged=True)``) keep one int32 per
+sequence (``cache.pos [B]``, stride 1, host mirror ``cache.lengths``).  So
 
 * ``prefill(ids, lengths)`` takes right-padded prompts of different lengths and
   returns each sequence's logits after its own last token.  On an empty cache
@@ -92,22 +100,28 @@ class KVCache:
         self.v = torch.zeros(shape, device=device, dtype=dtype)
         self.ragged = ragged
         self.pos = torch.zeros(batch if ragged else 1, device=device, dtype=torch.int32)  # tokens already cached
-        self.length = 0  # host mirror of pos (the host never reads pos back); ragged: the longest sequence
-        self.lengths = [0] * batch if ragged else None  # ragged: host mirror of pos, per sequence
+        self._len = [0] * batch  # host mirror of pos (never read back), per sequence: all equal unless ragged
         self.max_len = max_len
         self.batch = batch
 
+    @property
+    def length(self) -> int:
+        """Tokens cached; ragged: of the longest sequence."""
+        return max(self._len)
+
+    @property
+    def lengths(self) -> list[int] | None:
+        """Ragged: tokens cached per sequence (the live list); otherwise ``None``."""
+        return self._len if self.ragged else None
+
     def reset(self) -> None:
         self.pos.zero_()
-        self.length = 0
-        if self.ragged:
-            self.lengths = [0] * self.batch
+        self._len = [0] * self.batch
 
     def advance(self, rows, steps) -> None:
-        """Ragged host mirror: sequence ``rows[i]`` grew by ``steps[i]`` tokens."""
+        """Host mirror: sequence ``rows[i]`` grew by ``steps[i]`` tokens."""
         for r, n in zip(rows, steps):
-            self.lengths[r] += int(n)
-        self.length = max(self.lengths)
+            self._len[r] += int(n)
 
     def nbytes(self) -> int:
         return 2 * self.k.numel() * self.k.element_size()
@@ -134,9 +148,11 @@ class DecodeSession:
     ``prefill(ids [B, T])`` and ``decode(ids [B])`` return the next-token logits ``[B, V]`` of the last position.
     With ``use_graph`` (GPU only) the decode step is captured into a HIP graph on first use and replayed after.
 
-    With ``ragged`` every sequence has its own position: ``prefill`` takes right-padded ``ids`` with host ``lengths``,
-    ``decode`` an ``active`` mask, ``reset_slot`` / ``prefill_slot`` hand one slot to a new request, and ``generate``
-    takes a list of prompts of different lengths (module docstring).
+    One engine serves both position layouts: ``_append`` and ``decode`` work per sequence, and the default session is
+    the caller whose sequences all take the whole window.  With ``ragged`` every sequence has its own position:
+    ``prefill`` takes right-padded ``ids`` with host ``lengths``, ``decode`` an ``active`` mask, ``reset_slot`` /
+    ``prefill_slot`` hand one slot to a new request, and ``generate`` takes a list of prompts of different lengths
+    (module docstring).
     """
 
     def __init__(self, model, batch: int, max_len: int | None = None, use_graph: bool = True, ragged: bool = False):
@@ -155,11 +171,11 @@ class DecodeSession:
         p = model.lm_head.weight
         self.device = p.device
         self.cache = KVCache(len(model.layers), batch, self.Hkv, self.max_len, self.D, self.device, p.dtype, ragged)
-        # ragged: per-sequence advance of the decode step (1 = active), static so that the captured graph reads it
-        self._step = torch.ones(batch, device=self.device, dtype=torch.int32) if ragged else None
-        self._step_host = [1] * batch  # what _step holds
         self.fast = self._fast_ok()
         self.use_graph = use_graph and self.fast
+        # ragged: per-sequence advance of the decode step (1 = active), static so that the captured graph reads it
+        self._step = torch.ones(batch, device=self.device, dtype=torch.int32) if ragged and self.fast else None
+        self._step_host = [1] * batch  # what _step holds
         self._graph = None
         if self.fast:
             self._prepare_weights()
@@ -191,8 +207,8 @@ class DecodeSession:
         rope = self.model.layers[0].attn.rope
         if rope is not None:
             self._cos, self._sin = rope.cos.float().contiguous(), rope.sin.float().contiguous()
-        else:
-            self._cos = self._sin = None
+        else:  # the kernels take empty tables and use_rope = False
+            self._cos = self._sin = torch.empty(0, device=self.device, dtype=torch.float32)
 
     def reset(self) -> None:
         self.cache.reset()
@@ -212,25 +228,10 @@ class DecodeSession:
         ids = ids.to(self.device)
         B, T = ids.shape
         assert B == self.batch, f"session batch is {self.batch}, got {B}"
-        if self.ragged:
-            n = [T] * B if lengths is None else [int(x) for x in lengths]
-            assert len(n) == B and all(1 <= x <= T for x in n), "lengths: one int in [1, T] per sequence"
-            return self._append(ids, n, list(range(B)))
-        assert lengths is None, "per-sequence lengths need DecodeSession(..., ragged=True)"
-        assert self.cache.length + T <= self.max_len, "KV cache full"
-        if self.fast and self.cache.length == 0 and T > 1:
-            out = self._forward_fast(ids, prefill=True)
-        elif self.fast:
-            # appending to a filled cache (multi-turn serving, speculative verification): chunks of up to
-            # 8 / G tokens per step, each attending the cache plus its own causal prefix in one decode_attn
-            out = None
-            step = max(1, 8 // (self.H // self.Hkv))
-            for t in range(0, T, step):
-                out = self._forward_fast(ids[:, t : t + step], prefill=False)
-        else:
-            out = self._forward_reference(ids)
-        self.cache.length += T
-        return out
+        assert lengths is None or self.ragged, "per-sequence lengths need DecodeSession(..., ragged=True)"
+        n = [T] * B if lengths is None else [int(x) for x in lengths]
+        assert len(n) == B and all(1 <= x <= T for x in n), "lengths: one int in [1, T] per sequence"
+        return self._append(ids, n, list(range(B)))
 
     @torch.no_grad()
     def decode(self, ids: Tensor, active=None) -> Tensor:
@@ -238,44 +239,27 @@ class DecodeSession:
 
         Ragged sessions: ``active`` (bool ``[B]``, default all) -- an inactive sequence is fed as usual, but its
         position does not advance and its logits are unspecified."""
-        if self.ragged:
-            return self._decode_ragged(ids, active)
-        assert active is None, "an active mask needs DecodeSession(..., ragged=True)"
-        assert self.cache.length + 1 <= self.max_len, "KV cache full"
-        ids = ids.reshape(self.batch, 1).to(self.device)
-        if not self.use_graph:
-            out = self._forward_fast(ids, prefill=False) if self.fast else self._forward_reference(ids)
+        B = self.batch
+        assert active is None or self.ragged, "an active mask needs DecodeSession(..., ragged=True)"
+        step = [1] * B if active is None else [int(bool(a)) for a in torch.as_tensor(active).reshape(-1).tolist()]
+        assert len(step) == B, "active: one flag per sequence"
+        rows = list(range(B))
+        assert all(c + s <= self.max_len for c, s in zip(self.cache._len, step)), "KV cache full"
+        ids = ids.reshape(B, 1).to(self.device)
+        if self._step is not None and step != self._step_host:
+            # (the mask changes only when a sequence finishes or a slot is refilled)
+            self._step.copy_(torch.tensor(step, dtype=torch.int32))
+            self._step_host = step
+        if not self.fast:
+            out = self._forward_reference(ids, step, rows)
+        elif not self.use_graph:
+            out = self._forward_fast(ids, prefill=False, step=self._step)
         else:
             if self._graph is None:
                 self._capture()
             self._static_ids.copy_(ids)
             self._graph.replay()
             out = self._static_logits.clone()  # the graph's output buffer is rewritten by the next replay
-        self.cache.length += 1
-        return out
-
-    def _decode_ragged(self, ids: Tensor, active) -> Tensor:
-        B = self.batch
-        act = [True] * B if active is None else [bool(a) for a in torch.as_tensor(active).reshape(-1).tolist()]
-        assert len(act) == B, "active: one flag per sequence"
-        rows = list(range(B))
-        step = [int(a) for a in act]
-        assert all(self.cache.lengths[b] + step[b] <= self.max_len for b in rows), "KV cache full"
-        ids = ids.reshape(B, 1).to(self.device)
-        if not self.fast:
-            out = self._forward_reference_ragged(ids, step, rows)
-        else:
-            if step != self._step_host:  # (the mask changes only when a sequence finishes or a slot is refilled)
-                self._step.copy_(torch.tensor(step, dtype=torch.int32))
-                self._step_host = step
-            if not self.use_graph:
-                out = self._forward_fast(ids, prefill=False, step=self._step)
-            else:
-                if self._graph is None:
-                    self._capture()
-                self._static_ids.copy_(ids)
-                self._graph.replay()
-                out = self._static_logits.clone()
         self.cache.advance(rows, step)
         return out
 
@@ -285,7 +269,6 @@ class DecodeSession:
         assert self.ragged, "slots need DecodeSession(..., ragged=True)"
         self.cache.pos[b : b + 1].zero_()
         self.cache.lengths[b] = 0
-        self.cache.length = max(self.cache.lengths)
 
     @torch.no_grad()
     def prefill_slot(self, b: int, ids: Tensor) -> Tensor:
@@ -297,43 +280,41 @@ class DecodeSession:
         return self._append(ids, [ids.shape[1]], [b])
 
     def _append(self, ids: Tensor, n: list[int], rows: list[int]) -> Tensor:
-        """Ragged prefill: the first ``n[i]`` tokens of ``ids[i]`` (right-padded) go to sequence ``rows[i]`` -- the
+        """Every prefill: the first ``n[i]`` tokens of ``ids[i]`` (right-padded) go to sequence ``rows[i]`` -- the
         whole batch, or one slot.  Returns every sequence's logits after its last valid token."""
-        cur = [self.cache.lengths[r] for r in rows]
-        assert all(c + x <= self.max_len for c, x in zip(cur, n)), "KV cache full"
+        c = self.cache
+        cur = [c._len[r] for r in rows]
+        assert all(p + x <= self.max_len for p, x in zip(cur, n)), "KV cache full"
         ids = ids[:, : max(n)]
         B, T = ids.shape
         if not self.fast:
-            out = self._forward_reference_ragged(ids, n, rows)
+            out = self._forward_reference(ids, n, rows)
         else:
-            c = self.cache
-            kv = (c.k, c.v, c.pos) if len(rows) == self.batch else \
-                (c.k[:, rows[0] : rows[0] + 1], c.v[:, rows[0] : rows[0] + 1], c.pos[rows[0] : rows[0] + 1])
-            dev_i32 = lambda v: torch.tensor(v, dtype=torch.int32).to(self.device)  # noqa: E731
-            if max(cur) == 0 and T > 1:
-                # empty cache: causal flash prefill over the padded window + one kv_append; a pad token sits to the
-                # right of every valid one, so no valid token sees it, and its cache rows lie at or past pos[b]
-                last = torch.tensor([x - 1 for x in n]).to(self.device)
-                out = self._forward_fast(ids, prefill=True, step=dev_i32(n), last=last, kv=kv)
-            else:
-                # filled cache: chunks of up to 8 / G tokens; sequence b advances by the part of its remaining
-                # length that falls in the chunk, and its logits come from the chunk holding its last valid token
-                out = None
-                chunk = max(1, 8 // (self.H // self.Hkv))
-                for t0 in range(0, T, chunk):
-                    w = min(chunk, T - t0)
-                    part = [min(max(x - t0, 0), w) for x in n]
+            b = rows[0]
+            kv = None if B == self.batch else (c.k[:, b : b + 1], c.v[:, b : b + 1], c.pos[b : b + 1])
+            # empty cache: one causal flash prefill over the (padded) window + one kv_append; a pad token sits to the
+            # right of every valid one, so no valid token sees it, and its cache rows lie at or past pos[b].
+            # Filled cache (multi-turn serving, speculative verification): chunks of up to 8 / G tokens, each
+            # attending the cache plus its own causal prefix in one decode_attn
+            flash = max(cur) == 0 and T > 1
+            chunk = T if flash else max(1, 8 // (self.H // self.Hkv))
+            out = None
+            for t0 in range(0, T, chunk):
+                w = min(chunk, T - t0)
+                # sequence i advances by the part of its length that falls in the chunk, and its logits come from
+                # the chunk holding its last valid token; the device step / last exist only where the parts differ
+                part = [min(max(x - t0, 0), w) for x in n]
+                step = last = None
+                if min(part) < w:
+                    step = torch.tensor(part, dtype=torch.int32).to(self.device)
                     last = torch.tensor([max(p - 1, 0) for p in part]).to(self.device)
-                    lg = self._forward_fast(ids[:, t0 : t0 + w], prefill=False, step=dev_i32(part), last=last, kv=kv)
-                    if out is None:
-                        out = lg
-                    else:
-                        here = [i for i, x in enumerate(n) if t0 < x]  # sequences with a valid token in this chunk
-                        if len(here) == B:
-                            out = lg
-                        else:
-                            out[here] = lg[here]
-        self.cache.advance(rows, n)
+                lg = self._forward_fast(ids[:, t0 : t0 + w], prefill=flash, step=step, last=last, kv=kv)
+                here = [i for i, p in enumerate(part) if p]  # sequences with a valid token in this chunk
+                if len(here) == B:
+                    out = lg
+                else:
+                    out[here] = lg[here]
+        c.advance(rows, n)
         return out
 
     @torch.no_grad()
@@ -408,24 +389,25 @@ class DecodeSession:
         self.cache.pos.copy_(pos0)  # capture does not execute, but keep the invariant explicit
         self._graph = g
 
-    def _forward_fast(self, ids: Tensor, prefill: bool, step: Tensor | None = None, last: Tensor | None = None,
-                      kv=None) -> Tensor:
-        """``step`` (ragged): device int32 advance per sequence instead of ``T``; ``last`` (ragged): index of the
-        token whose logits each sequence returns instead of ``T - 1``; ``kv``: the (k, v, pos) to run on -- the
-        session's cache, or one slot's views of it."""
-        if not prefill and ids.shape[1] == 1 and ids.shape[0] <= _GEMV_MAX_BATCH and self._gemv_fits(ids.shape[0]):
-            return self._decode_gemv(ids, step, kv)
+    def _operands(self, kv):
+        """What both fast forwards run on: the HIP ops, (k, v, pos) -- ``kv`` or the whole cache -- and RoPE tables."""
         from ..ops._ext import ops as hip
 
-        h = hip()
+        c = self.cache
+        return (hip(), *(kv or (c.k, c.v, c.pos)), self._cos, self._sin, self._cos.numel() > 0)
+
+    def _forward_fast(self, ids: Tensor, prefill: bool, step: Tensor | None = None, last: Tensor | None = None,
+                      kv=None) -> Tensor:
+        """``step``: device int32 advance per sequence instead of ``T``; ``last``: index of the token whose logits
+        each sequence returns instead of ``T - 1`` (both only where the sequences differ); ``kv``: the (k, v, pos)
+        to run on -- one slot's views of the cache instead of the whole."""
+        if not prefill and ids.shape[1] == 1 and ids.shape[0] <= _GEMV_MAX_BATCH and self._gemv_fits(ids.shape[0]):
+            return self._decode_gemv(ids, step, kv)
+        h, kc, vc, pos, cos, sin, use_rope = self._operands(kv)
         m = self.model
         B, T = ids.shape
         H, Hkv, D = self.H, self.Hkv, self.D
         scale = 1.0 / math.sqrt(D)
-        kc, vc, pos = kv if kv is not None else (self.cache.k, self.cache.v, self.cache.pos)
-        use_rope = self._cos is not None
-        cos = self._cos if use_rope else kc.new_empty(0, dtype=torch.float32)
-        sin = self._sin if use_rope else kc.new_empty(0, dtype=torch.float32)
         xr = m.token_embeddings(ids).reshape(B * T, -1)
         xd = None
         for li, (ln1, wqkv, wo, ln2, w13, w2, eps) in enumerate(self._w):
@@ -467,16 +449,10 @@ class DecodeSession:
         qkv (+RMSNorm, +RoPE, +cache write) -> split-K decode attention -> Wo (+ the split combine) -> [W1; W3]
         (+residual add, +RMSNorm, +SwiGLU) -> W2; the residual add of W2's output is folded into the next layer's
         QKV prologue: 5 launches per layer."""
-        from ..ops._ext import ops as hip
-
-        h = hip()
+        h, kc, vc, pos, cos, sin, use_rope = self._operands(kv)
         m = self.model
         H = self.H
         scale = 1.0 / math.sqrt(self.D)
-        kc, vc, pos = kv if kv is not None else (self.cache.k, self.cache.v, self.cache.pos)
-        use_rope = self._cos is not None
-        cos = self._cos if use_rope else kc.new_empty(0, dtype=torch.float32)
-        sin = self._sin if use_rope else kc.new_empty(0, dtype=torch.float32)
         xr = m.token_embeddings(ids).reshape(ids.shape[0], -1)
         xd = None
         for li, (ln1, wqkv, wo, ln2, w13, w2, eps) in enumerate(self._w):
@@ -493,56 +469,18 @@ class DecodeSession:
         return logits
 
     # ------------------------------------------------------------------ oracle path
-    def _forward_reference(self, ids: Tensor) -> Tensor:
-        """Plain-PyTorch math over the same cache (any dtype / device / ablation)."""
-        m = self.model
-        B, T = ids.shape
-        p0 = self.cache.length
-        H, Hkv, D = self.H, self.Hkv, self.D
-        x = m.token_embeddings(ids)
-        tp = torch.arange(p0, p0 + T, device=ids.device)
-        mask = F.causal_mask(T, p0 + T, device=ids.device)
-        for li, layer in enumerate(m.layers):
-            attn = layer.attn
-
-            def attend(z: Tensor) -> Tensor:
-                q = attn.q_proj(z).view(B, T, H, D).transpose(1, 2)
-                k = attn.k_proj(z).view(B, T, Hkv, D).transpose(1, 2)
-                v = attn.v_proj(z).view(B, T, Hkv, D).transpose(1, 2)
-                if attn.rope is not None:
-                    q = attn.rope(q, tp)
-                    k = attn.rope(k, tp)
-                self.cache.k[li, :, :, p0 : p0 + T] = k.to(self.cache.k.dtype)
-                self.cache.v[li, :, :, p0 : p0 + T] = v.to(self.cache.v.dtype)
-                kk = self.cache.k[li, :, :, : p0 + T].to(q.dtype)
-                vv = self.cache.v[li, :, :, : p0 + T].to(q.dtype)
-                if Hkv != H:
-                    kk = kk.repeat_interleave(H // Hkv, dim=1)
-                    vv = vv.repeat_interleave(H // Hkv, dim=1)
-                o = F.scaled_dot_product_attention(q, kk, vv, mask)
-                return attn.output_proj(o.transpose(1, 2).reshape(B, T, H * D))
-
-            if layer.use_post_norm:
-                x = layer.ln1(x + attend(x))
-                x = layer.ln2(x + layer.ffn(x))
-            else:
-                x = x + attend(layer.ln1(x))
-                x = x + layer.ffn(layer.ln2(x))
-        logits = m.lm_head(m.ln_final(x[:, -1]))
-        self.cache.pos.add_(T)
-        return logits
-
-    def _forward_reference_ragged(self, ids: Tensor, n: list[int], rows: list[int]) -> Tensor:
-        """The oracle math with per-sequence positions: ``ids [len(rows), T]`` (right-padded), of which the first
-        ``n[i]`` tokens are appended to sequence ``rows[i]`` at its own position (RoPE positions and visibility per
-        sequence).  Returns the logits after each sequence's last valid token (token 0 where ``n[i] == 0``: an
-        inactive decode step, unspecified).  Pad tokens are written at and past the new position, where nothing
-        reads them, or dropped at the end of the cache."""
+    def _forward_reference(self, ids: Tensor, n: list[int], rows: list[int]) -> Tensor:
+        """Plain-PyTorch math over the same cache (any dtype / device / ablation): ``ids [len(rows), T]``
+        (right-padded), of which the first ``n[i]`` tokens are appended to sequence ``rows[i]`` at its own position
+        (RoPE positions and visibility per sequence; with one shared position they all agree).  Returns the logits
+        after each sequence's last valid token (token 0 where ``n[i] == 0``: an inactive decode step, unspecified).
+        Pad tokens are written at and past the new position, where nothing reads them, or dropped at the end of the
+        cache."""
         m = self.model
         R, T = ids.shape
         H, Hkv, D, Lmax = self.H, self.Hkv, self.D, self.max_len
         dev = ids.device
-        cur = [self.cache.lengths[r] for r in rows]
+        cur = [self.cache._len[r] for r in rows]
         p0 = torch.tensor(cur, device=dev)
         Lk = min(max(cur) + T, Lmax)
         tp = p0[:, None] + torch.arange(T, device=dev)[None, :]  # [R, T] absolute positions
@@ -579,5 +517,8 @@ class DecodeSession:
                 x = x + layer.ffn(layer.ln2(x))
         last = torch.tensor([max(c - 1, 0) for c in n], device=dev)
         logits = m.lm_head(m.ln_final(x[torch.arange(R, device=dev), last]))
-        self.cache.pos[rows] += torch.tensor(n, dtype=torch.int32, device=dev)
+        if self.ragged:
+            self.cache.pos[rows] += torch.tensor(n, dtype=torch.int32, device=dev)
+        else:  # one shared position: every sequence took the whole window
+            self.cache.pos.add_(T)
         return logits

@@ -84,10 +84,29 @@ def test_ragged_prefill_decode_and_slot_replacement(kw):
             assert rel(lg[b], full[b][lens[b] + t]) <= TOL, (t, b)
 
 
-def test_ragged_append_to_filled_cache():
-    """``lengths`` on a filled cache: a second ragged turn on top of a ragged first one."""
+@pytest.mark.parametrize("kw", [{}, {"use_post_norm": True}, {"remove_rope": True}])
+def test_uniform_session_equals_ragged_with_equal_lengths(kw):
+    """One engine: the shared position is the per-sequence one with equal lengths, bit for bit -- through the
+    empty-cache prefill, a prefill onto the filled cache (5 tokens: with G = 2 a chunk of 4 and a tail of 1 where
+    the session chunks) and decode steps."""
+    model = _model(**kw)
+    g = torch.Generator().manual_seed(4)
+    uni = DecodeSession(model, 3, max_len=32)
+    rag = DecodeSession(model, 3, max_len=32, ragged=True)
+    ids = torch.randint(0, 97, (3, 6), generator=g)
+    assert torch.equal(uni.prefill(ids), rag.prefill(ids, [6, 6, 6]))
+    ids = torch.randint(0, 97, (3, 5), generator=g)
+    assert torch.equal(uni.prefill(ids), rag.prefill(ids))
+    for _ in range(3):
+        ids = torch.randint(0, 97, (3,), generator=g)
+        assert torch.equal(uni.decode(ids), rag.decode(ids))
+    assert uni.length == rag.length == 14 and uni.cache.pos.tolist() == [14] and rag.cache.pos.tolist() == [14] * 3
+    assert torch.equal(uni.cache.k, rag.cache.k) and torch.equal(uni.cache.v, rag.cache.v)
+
+
+def _append_to_filled_cache(second):
     model = _model()
-    first, second = [5, 12, 3], [7, 1, 4]
+    first = [5, 12, 3]
     seqs = _seqs([a + b for a, b in zip(first, second)], 2)
     full = _full(model, seqs)
     sess = DecodeSession(model, 3, max_len=32, ragged=True)
@@ -100,6 +119,17 @@ def test_ragged_append_to_filled_cache():
     lg = sess.decode(torch.stack([s[n] for s, n in zip(seqs, tot)]))
     for b in range(3):
         assert rel(lg[b], full[b][tot[b]]) <= TOL, b
+
+
+def test_ragged_append_to_filled_cache():
+    """``lengths`` on a filled cache: a second ragged turn on top of a ragged first one."""
+    _append_to_filled_cache([7, 1, 4])
+
+
+def test_ragged_append_chunk_tail():
+    """A second turn of 5 tokens at most, which a session that chunks by 8 / G = 4 cuts into 4 + 1: the sequences
+    end at the first token, at the chunk's last token and in the tail."""
+    _append_to_filled_cache([5, 1, 4])
 
 
 def test_inactive_sequence_stands_still():

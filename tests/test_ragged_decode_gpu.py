@@ -278,6 +278,38 @@ def test_ragged_session_matches_full_forward(gpu_device, gqa, use_graph, B):
             assert r < 3e-2, (t, b, r)
 
 
+@pytest.mark.parametrize("use_graph", [True, False])
+@pytest.mark.parametrize("B", [3, 9])
+def test_both_position_layouts_match_full_forward(gpu_device, use_graph, B):
+    """The shared-position session and a ragged one with equal lengths run the same engine: empty-cache prefill
+    (T = 6), filled-cache prefill (T = 5; G = 2: a chunk of 4 and a tail of 1) and 3 decode steps (B = 3: the fused
+    skinny-GEMM step, B = 9: the library-GEMM step), each against the full forward under the bound of
+    ``test_ragged_session_matches_full_forward``; both end at the same host length, in their own position layout."""
+    dev = gpu_device
+    model = _bf16_model(dev, True)
+    L = 6 + 5 + 3
+    seqs = torch.randint(0, 1000, (B, L), generator=torch.Generator().manual_seed(200 + B)).to(dev)
+    with torch.no_grad():
+        full = model(seqs).float()
+    ends = []
+    for ragged in (False, True):
+        sess = DecodeSession(model, B, max_len=64, use_graph=use_graph, ragged=ragged)
+        assert sess.fast and sess.cache.pos.numel() == (B if ragged else 1)
+        got = {5: sess.prefill(seqs[:, :6], [6] * B) if ragged else sess.prefill(seqs[:, :6])}
+        got[10] = sess.prefill(seqs[:, 6:11])
+        for t in range(11, L):
+            got[t] = sess.decode(seqs[:, t])
+        torch.cuda.synchronize()
+        assert sess.cache.pos.tolist() == ([L] * B if ragged else [L])
+        assert sess.cache.lengths == ([L] * B if ragged else None)
+        ends.append(sess.length)
+        for t, lg in got.items():
+            for b in range(B):
+                r = rel(lg[b], full[b, t])
+                assert r < 3e-2, (ragged, t, b, r)
+    assert ends == [L, L]
+
+
 @pytest.mark.parametrize("B", [3, 12])
 def test_ragged_graph_replay_equals_eager(gpu_device, B):
     model = _bf16_model(gpu_device, False)

@@ -10,10 +10,18 @@ instead:
   RMSNorm, the fused [Wq;Wk;Wv] GEMM, flash attention with fused RoPE -- plus
   ``kv_append``, which writes the roped K and the V of all ``T`` tokens into
   the cache in one launch;
-* **append** to a filled cache (a new turn of a conversation, draft tokens to
-  verify): steps of up to ``8 / G`` tokens per sequence, each a multi-token
-  ``kv_append`` + ``decode_attn`` in which token ``t`` sees the cache and its
-  own causal prefix (``pos + t``), instead of one decode step per token;
+* **append** to a filled cache (a new turn of a conversation, a slot that keeps
+  a shared prefix, a chunk of a long prompt): one pass over the layers for the
+  whole window, each layer a multi-token ``kv_append`` + ``cache_attn``
+  (``csrc/flash_attn_cache.hip``: MFMA flash attention whose keys are the cache
+  slabs and in which token ``t`` sees the cache and its own causal prefix,
+  ``pos + t``).  A window of at most ``8 / G`` tokens (draft tokens to verify)
+  is one ``kv_append`` + ``decode_attn`` step instead, the VALU kernel of the
+  decode step, which takes up to 8 query rows per KV head;
+* **chunked prefill** (``prefill_chunk=c``): every prefill or append is cut into
+  chunks of at most ``c`` tokens -- on an empty cache the first through the
+  flash path, the later ones through ``cache_attn`` -- so activation memory is
+  bounded by ``B * c`` rows whatever the prompt length;
 * **decode** (one token per sequence): ``kv_append`` (RoPE at the device-side
   position, cache write, roped q) -> ``decode_attn`` (split-K flash-decoding
   over the cache) for every layer, residual adds fused into the next RMSNorm,
@@ -76,6 +84,38 @@ from ..ops import reference as F
 # column block -- but every workgroup re-normalises all rows in its prologue, so past ~12 rows the library
 # GEMMs (hipBLASLt) win: GPT-2-small at 16 sequences 0.737 vs 0.699 ms, at 8 0.499 vs 0.672)
 _GEMV_MAX_BATCH = int(os.environ.get("BPE_DECODE_GEMV_MAX_BATCH", "8"))
+
+
+# A window appended to a filled cache runs on cache_attn (one pass over the layers) from this many query rows per KV
+# head (G * T) on; below it, on decode_attn steps of 8 // G tokens.  decode_attn takes at most 8 rows, so 9 sends
+# it exactly the windows it serves in one step (speculative verification), bit for bit as before cache_attn.
+# Measured at 9 rows, the first window that needs two decode_attn steps (profiles/bench/append_prefill.log, 512
+# tokens cached): GPT-2-small 2.167 -> 1.738 ms at batch 1, 2.108 -> 1.441 at batch 8; no shape lost, so 9 it is.
+_CACHE_ATTN_MIN_ROWS = 9
+
+
+def _chunks(T: int, prefill_chunk: int | None) -> list[tuple[int, int]]:
+    """``(t0, w)`` pieces of a ``T``-token window, each of at most ``prefill_chunk`` tokens (``None``: the whole)."""
+    c = T if prefill_chunk is None else max(1, min(prefill_chunk, T))
+    return [(t0, min(c, T - t0)) for t0 in range(0, T, c)]
+
+
+def _append_plan(T: int, G: int, filled: bool, prefill_chunk: int | None = None) -> list[tuple[int, int, str]]:
+    """Steps ``(t0, w, kind)`` in which a window of ``T`` tokens is appended: tokens ``t0 .. t0 + w - 1`` in one pass
+    over the layers whose attention is ``kind``: ``"flash"`` (empty cache: the training kernel, causal inside the
+    window), ``"cache"`` (``cache_attn`` over the cache) or ``"decode"`` (``decode_attn``, ``G * w <= 8``).
+    ``filled``: some sequence already holds tokens.  ``prefill_chunk`` bounds ``w``."""
+    assert T >= 1 and G >= 1
+    plan = []
+    for t0, w in _chunks(T, prefill_chunk):
+        if t0 == 0 and not filled and w > 1:
+            plan.append((t0, w, "flash"))
+        elif G * w >= _CACHE_ATTN_MIN_ROWS:
+            plan.append((t0, w, "cache"))
+        else:
+            d = max(1, 8 // G)
+            plan += [(t0 + u, min(d, w - u), "decode") for u in range(0, w, d)]
+    return plan
 
 
 def _gemv_ok(m: int, k: int) -> bool:
@@ -153,11 +193,19 @@ class DecodeSession:
     ``prefill`` takes right-padded ``ids`` with host ``lengths``, ``decode`` an ``active`` mask, ``reset_slot`` /
     ``prefill_slot`` hand one slot to a new request, and ``generate`` takes a list of prompts of different lengths
     (module docstring).
+
+    ``prefill`` / ``prefill_slot`` on a cache that already holds tokens (a second turn, a slot with a kept prefix)
+    is one pass over the layers for the whole window (``cache_attn``), as on an empty cache.  ``prefill_chunk=c``
+    cuts every prefill or append, ragged or not, into chunks of at most ``c`` tokens, which bounds activation memory
+    by ``B * c`` rows.
     """
 
-    def __init__(self, model, batch: int, max_len: int | None = None, use_graph: bool = True, ragged: bool = False):
+    def __init__(self, model, batch: int, max_len: int | None = None, use_graph: bool = True, ragged: bool = False,
+                 prefill_chunk: int | None = None):
+        assert prefill_chunk is None or prefill_chunk >= 1, "prefill_chunk: a positive number of tokens, or None"
         self.model = model
         self.ragged = ragged
+        self.prefill_chunk = prefill_chunk
         cfg = model.config
         self.batch = batch
         self.max_len = max_len or model.context_length
@@ -287,34 +335,40 @@ class DecodeSession:
         assert all(p + x <= self.max_len for p, x in zip(cur, n)), "KV cache full"
         ids = ids[:, : max(n)]
         B, T = ids.shape
-        if not self.fast:
-            out = self._forward_reference(ids, n, rows)
+        G = self.H // self.Hkv
+        if not self.fast:  # the oracle math reads the host lengths, which therefore move chunk by chunk
+            plan = [(t0, w, "reference") for t0, w in _chunks(T, self.prefill_chunk)]
         else:
-            b = rows[0]
-            kv = None if B == self.batch else (c.k[:, b : b + 1], c.v[:, b : b + 1], c.pos[b : b + 1])
             # empty cache: one causal flash prefill over the (padded) window + one kv_append; a pad token sits to the
             # right of every valid one, so no valid token sees it, and its cache rows lie at or past pos[b].
-            # Filled cache (multi-turn serving, speculative verification): chunks of up to 8 / G tokens, each
-            # attending the cache plus its own causal prefix in one decode_attn
-            flash = max(cur) == 0 and T > 1
-            chunk = T if flash else max(1, 8 // (self.H // self.Hkv))
-            out = None
-            for t0 in range(0, T, chunk):
-                w = min(chunk, T - t0)
-                # sequence i advances by the part of its length that falls in the chunk, and its logits come from
-                # the chunk holding its last valid token; the device step / last exist only where the parts differ
-                part = [min(max(x - t0, 0), w) for x in n]
+            # Filled cache (multi-turn serving, a chunk of a long prompt): kv_append + cache_attn over the whole
+            # window, every token attending the cache plus its own causal prefix; a window of up to 8 / G tokens
+            # (speculative verification) is one decode_attn step (_append_plan)
+            plan = _append_plan(T, G, max(cur) > 0, self.prefill_chunk)
+            b = rows[0]
+            kv = None if B == self.batch else (c.k[:, b : b + 1], c.v[:, b : b + 1], c.pos[b : b + 1])
+        out = None
+        for t0, w, kind in plan:
+            # sequence i advances by the part of its length that falls in the chunk, and its logits come from
+            # the chunk holding its last valid token; the device step / last exist only where the parts differ
+            part = [min(max(x - t0, 0), w) for x in n]
+            if kind == "reference":
+                lg = self._forward_reference(ids[:, t0 : t0 + w], part, rows)
+                c.advance(rows, part)
+            else:
                 step = last = None
                 if min(part) < w:
                     step = torch.tensor(part, dtype=torch.int32).to(self.device)
                     last = torch.tensor([max(p - 1, 0) for p in part]).to(self.device)
-                lg = self._forward_fast(ids[:, t0 : t0 + w], prefill=flash, step=step, last=last, kv=kv)
-                here = [i for i, p in enumerate(part) if p]  # sequences with a valid token in this chunk
-                if len(here) == B:
-                    out = lg
-                else:
-                    out[here] = lg[here]
-        c.advance(rows, n)
+                lg = self._forward_fast(ids[:, t0 : t0 + w], prefill=kind == "flash", step=step, last=last, kv=kv,
+                                        cache=kind == "cache")
+            here = [i for i, p in enumerate(part) if p]  # sequences with a valid token in this chunk
+            if len(here) == B:
+                out = lg
+            else:
+                out[here] = lg[here]
+        if self.fast:
+            c.advance(rows, n)
         return out
 
     @torch.no_grad()
@@ -397,8 +451,9 @@ class DecodeSession:
         return (hip(), *(kv or (c.k, c.v, c.pos)), self._cos, self._sin, self._cos.numel() > 0)
 
     def _forward_fast(self, ids: Tensor, prefill: bool, step: Tensor | None = None, last: Tensor | None = None,
-                      kv=None) -> Tensor:
-        """``step``: device int32 advance per sequence instead of ``T``; ``last``: index of the token whose logits
+                      kv=None, cache: bool = False) -> Tensor:
+        """``prefill``: flash attention inside the window (empty cache); ``cache``: ``cache_attn`` over the cache
+        instead of ``decode_attn`` (a window of more than ``8 / G`` tokens); ``step``: device int32 advance per sequence instead of ``T``; ``last``: index of the token whose logits
         each sequence returns instead of ``T - 1`` (both only where the sequences differ); ``kv``: the (k, v, pos)
         to run on -- one slot's views of the cache instead of the whole."""
         if not prefill and ids.shape[1] == 1 and ids.shape[0] <= _GEMV_MAX_BATCH and self._gemv_fits(ids.shape[0]):
@@ -422,7 +477,10 @@ class DecodeSession:
                 h.kv_append(qkv, kc[li], vc[li], cos, sin, pos, B, T, H, use_rope)
             else:
                 q = h.kv_append(qkv, kc[li], vc[li], cos, sin, pos, B, T, H, use_rope)
-                o = h.decode_attn(q, kc[li], vc[li], pos, H, scale, True, T)
+                if cache:
+                    o = h.cache_attn(q, kc[li], vc[li], pos, H, scale, T)
+                else:
+                    o = h.decode_attn(q, kc[li], vc[li], pos, H, scale, True, T)
             g1 = torch.matmul(o, wo.t())
             xr, h2, _ = h.add_rmsnorm_fwd(xr, g1, ln2, eps)
             a = h.swiglu_fwd(torch.matmul(h2, w13.t()))

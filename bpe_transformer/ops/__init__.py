@@ -12,7 +12,7 @@ from ._ext import is_built, library_path, load
 from .activations import gelu, silu, swiglu_gate
 from .attention import (attention_qkv_reference, doc_bounds, flash_attention_qkv, flash_supported,
                         scaled_dot_product_attention)
-from .decode import decode_attention, kv_append
+from .decode import decode_attention, kv_append, prefill_attention
 from .embedding import embedding
 from .loss import IGNORE_INDEX, cross_entropy, lm_head_cross_entropy
 from .norm import rmsnorm
@@ -39,6 +39,7 @@ __all__ = [
     "library_path",
     "lm_head_cross_entropy",
     "load",
+    "prefill_attention",
     "rmsnorm",
     "scaled_dot_product_attention",
     "silu",

@@ -4,8 +4,9 @@
 //
 //   q [B, H, D] (RoPE already applied), cache K / V [B, Hkv, Lmax, D] (roped K), valid length L = *pos + 1:
 //   out[b, h] = softmax(q . K[b, h / G, :L]^T * scale) . V[b, h / G, :L]          (G = H / Hkv)
-// (T > 1 new tokens per sequence -- chunked prefill into a filled cache, speculative verification -- is the same
-// with one query row per (token, head) and token t limited to L = *pos + t + 1.)
+// (T > 1 new tokens per sequence, G * T <= 8 -- speculative verification -- is the same with one query row per
+// (token, head) and token t limited to L = *pos + t + 1.  Longer windows -- a second turn, chunked prefill into a
+// filled cache -- run on the MFMA kernel of flash_attn_cache.hip.)
 //
 // The position lives in device memory (int32), so one decode step -- append + attention for every layer -- is
 // shape-static and is captured once into a HIP graph (the host never passes the growing length).

@@ -158,6 +158,10 @@ void launch_decode_attn(const void* q, const void* k, const void* v, float* part
                         int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax, float scale, hipStream_t s);
 void launch_kv_append(const void* qkv, long ld, void* qo, void* Kc, void* Vc, const float* cosT, const float* sinT,
                       const int* pos, int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax, hipStream_t s);
+// flash_attn_cache.hip (flash prefill over the cache: T new tokens per sequence, any T; `pos` as above)
+bool cache_attn_ok(int H, int Hkv, int D, int T, int Lmax);
+void launch_cache_attn(const void* q, const void* k, const void* v, void* out, const int* pos, int pos_stride, int B,
+                       int T, int H, int Hkv, int D, int Lmax, float scale, hipStream_t s);
 
 // decode_gemv.hip (M <= 16 token rows; epi 0 plain, 1 SwiGLU over [W1; W3], 2 fused QKV + RoPE + KV-cache write)
 struct GemvArgs {

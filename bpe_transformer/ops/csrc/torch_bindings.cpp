@@ -1116,6 +1116,30 @@ at::Tensor decode_attn(const at::Tensor& q, const at::Tensor& kc, const at::Tens
     return combine ? out : part;
 }
 
+// Flash prefill over the cache (flash_attn_cache.hip): q [B*T, H*D] (roped, rows b * T + t, already appended at
+// positions *pos .. *pos + T - 1) -> [B*T, H*D]; token t sees keys 0 .. min(*pos + t, Lmax - 1).  Any T.
+at::Tensor cache_attn(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc, const at::Tensor& pos,
+                      int64_t H, double scale, int64_t T) {
+    TORCH_CHECK(kc.dim() == 4, "cache_attn: k_cache must be [B, Hkv, Lmax, D]");
+    const int64_t B = kc.size(0), Hkv = kc.size(1), Lmax = kc.size(2), D = kc.size(3);
+    TORCH_CHECK(H > 0 && T > 0 && H < (1 << 16) && T < (1 << 24) && Lmax < (1LL << 31) &&
+                    cache_attn_ok((int)H, (int)Hkv, (int)D, (int)T, (int)Lmax),
+                "cache_attn: head dim 64/128, H a multiple of Hkv with H / Hkv <= 8, T >= 1 and a cache slab below "
+                "2 GiB required");
+    check_cuda(q, "q");
+    TORCH_CHECK(q.scalar_type() == at::kBFloat16 && q.is_contiguous() && q.numel() == B * T * H * D,
+                "cache_attn: q must be contiguous bf16 [B*T, H*D]");
+    check_cache(kc, B, Hkv, "k_cache");
+    check_cache(vc, B, Hkv, "v_cache");
+    TORCH_CHECK(vc.sizes() == kc.sizes(), "cache_attn: k / v cache shapes differ");
+    const int pstride = check_pos(pos, B);
+    DevGuard g(q.device());
+    auto out = at::empty({B * T, H * D}, q.options());
+    launch_cache_attn(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(), pos.data_ptr<int>(), pstride, (int)B,
+                      (int)T, (int)H, (int)Hkv, (int)D, (int)Lmax, (float)scale, cur_stream());
+    return out;
+}
+
 // Skinny-GEMM prologue / shape checks shared by decode_gemv and decode_qkv; returns the residual-sum output
 at::Tensor gemv_setup(GemvArgs& a, const at::Tensor& x, const c10::optional<at::Tensor>& xd,
                       const c10::optional<at::Tensor>& ln, double eps, const at::Tensor& w) {
@@ -1244,6 +1268,7 @@ TORCH_LIBRARY(bpe_hip, m) {
     m.def("decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor pos, int H, float scale, "
           "bool combine=True, int T=1) -> Tensor");
     m.def("decode_attn_proj(Tensor part, Tensor w) -> Tensor");
+    m.def("cache_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor pos, int H, float scale, int T) -> Tensor");
     m.def("rmsnorm_fwd(Tensor x, Tensor w, float eps) -> (Tensor, Tensor)");
     m.def("add_rmsnorm_fwd(Tensor x, Tensor d, Tensor w, float eps) -> (Tensor, Tensor, Tensor)");
     m.def("rmsnorm_bwd(Tensor dy, Tensor x, Tensor w, Tensor rstd, Tensor? dres=None, Tensor(a!)? dw_acc=None) -> "
@@ -1354,6 +1379,7 @@ TORCH_LIBRARY_IMPL(bpe_hip, CUDA, m) {
     m.impl("rope_qk_", &rope_qk_);
     m.impl("kv_append", &kv_append);
     m.impl("decode_attn", &decode_attn);
+    m.impl("cache_attn", &cache_attn);
     m.impl("decode_gemv", &decode_gemv);
     m.impl("decode_qkv", &decode_qkv);
     m.impl("decode_attn_proj", &decode_attn_proj);

@@ -15,8 +15,11 @@ whole prefix for every new token.
   cache-write epilogues (``csrc/decode_gemv.hip``).
 * :func:`decode_attention` is single-token attention of ``q [B, H*D]`` over the
   first ``pos + 1`` cache rows (split-K "flash-decoding" with a combine pass).
+* :func:`prefill_attention` is the attention of any number of new tokens per
+  sequence over the cache (``csrc/flash_attn_cache.hip``: MFMA flash attention
+  whose keys are the cache slabs and whose causal diagonal starts at ``pos``).
 
-Both read the position from device memory, so a decode step is shape-static and
+All read the position from device memory, so a decode step is shape-static and
 can be captured in a HIP graph.  The CPU versions are the oracle.
 
 ``pos`` holds one int32 (a position shared by the batch) or one per sequence
@@ -102,6 +105,19 @@ def decode_attention_reference(q, k_cache, v_cache, pos, n_heads, scale=None, n_
     s = s.masked_fill(~visible[None, :, None, None, :], float("-inf"))
     o = torch.einsum("bthgl,bhld->bthgd", F.softmax(s, -1), v)
     return o.reshape(B * T, H * D).to(q.dtype)
+
+
+def prefill_attention(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, n_heads: int,
+                      scale: float | None = None, n_new: int = 1) -> Tensor:
+    """Flash prefill over the cache (``csrc/flash_attn_cache.hip``): the contract of :func:`decode_attention` --
+    ``q [B*n_new, H*D]`` already appended at ``pos .. pos + n_new - 1``, token t sees keys ``0 .. pos + t`` -- for
+    any ``n_new`` (MFMA flash attention whose keys are the cache slabs), where ``decode_attention`` takes at most
+    ``8 / G`` tokens.  The row of a token at or past ``Lmax`` is unspecified."""
+    D = k_cache.shape[-1]
+    scale = 1.0 / math.sqrt(D) if scale is None else scale
+    if q.is_cuda:
+        return ops().cache_attn(q.contiguous(), k_cache, v_cache, pos, n_heads, scale, n_new)
+    return decode_attention_reference(q, k_cache, v_cache, pos, n_heads, scale, n_new)
 
 
 def decode_attention_partials(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, n_heads: int,

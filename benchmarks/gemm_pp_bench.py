@@ -131,8 +131,8 @@ def main():
             if a.only and name not in a.only.split(","):
                 continue
             fn = run_quick if a.quick else run_shape
-            print(json.dumps({"model": m, "variant": os.environ.get("BPE_HIP_VARIANT"),
-                              "diag": os.environ.get("BPE_GPP_DIAG"), **fn(name, n, k, t, dev)}), flush=True)
+            print(json.dumps({"model": m, "variant": os.environ.get("BPE_HIP_VARIANT"), **fn(name, n, k, t, dev)}),
+                  flush=True)
 
 
 if __name__ == "__main__":

@@ -28,16 +28,21 @@
 // Staging: two 64 KiB stages (A image 32 KiB + B image 32 KiB), filled by
 // global_load_lds_dwordx4 (LDS-DMA).  K-major images are [256][64] (128-byte
 // rows, 16-byte chunk c of row r at c ^ ((r >> 1) & 7): conflict-free for the
-// 16x16x32 ds_read_b128 lane groups); MN-major images are [64][256] (512-byte
-// rows, chunk c at c ^ sig(r), read with ds_read_b64_tr_b16).  The DMA image
-// is lane-linear, so the swizzle is applied to the SOURCE address.  K-tile
-// kt+1 is DMA'd during phases 0-1 of kt (group 0 the first halves of A and B,
-// group 1 the second halves), retired by each issuing wave's vmcnt(0) in
-// phase 3 before the barrier that precedes the first read of kt+1.  WAR: the
-// buffer refilled in phase 0 of kt was last read in phase 3 of kt-1, whose
-// reads retire (lgkmcnt(0)) before that phase's closing barrier.  Raw
-// s_barrier only: __syncthreads() would drain the DMA (guide §5 "Pipelining
-// across barriers").
+// 16x16x32 ds_read_b128 lane groups); MN-major images are cut into [64 k]
+// sub-images whose column sets are whole 1-KiB DMA pieces -- eight of 32
+// columns for B (sub_off), four of 64 columns for A (sub64_off) -- and read
+// with ds_read_b64_tr_b16.  The DMA image is lane-linear, so the swizzle is
+// applied to the SOURCE address.
+//
+// Pipelining: K-tile kt+1 is DMA'd during kt, each wave two 1-KiB pieces in
+// every one of the four load sections, in the order the phases of kt+1 read
+// them; a section's wait leaves the newest pieces in flight and retires a
+// piece before the barrier that precedes its first read (ktile_spread; when
+// both operands are MN-major, the weight gradient, the second piece of a pair
+// is issued inside the MFMA section).  WAR: a region of the other stage is
+// refilled at least one barrier after its last read of kt-1.  Raw s_barrier
+// only: __syncthreads() would drain the DMA (guide §5 "Pipelining across
+// barriers").
 //
 // Split-K (weight gradients: R = all tokens) writes fp32 partial tiles to a
 // slab reduced by splitk_reduce_kernel (gemm.hip) in a fixed order.
@@ -66,18 +71,11 @@ typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) void gbl_void;
 
 __device__ __forceinline__ int fk(int r) { return (r >> 1) & 7; }
-__device__ __forceinline__ int sig(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
 
-// Source offset (elements, relative to the tile origin) of 16-byte image chunk e (0..2047).
-template <bool KM>
-__device__ __forceinline__ int src_off(int e, int ld) {
-    if constexpr (KM) {
-        const int row = e >> 3, lc = (e & 7) ^ fk(row);
-        return row * ld + lc * 8;
-    } else {
-        const int row = e >> 5, lc = (e & 31) ^ sig(row);
-        return row * ld + lc * 8;
-    }
+// Source offset (elements, relative to the tile origin) of 16-byte chunk e (0..2047) of a K-major image.
+__device__ __forceinline__ int src_off_km(int e, int ld) {
+    const int row = e >> 3, lc = (e & 7) ^ fk(row);
+    return row * ld + lc * 8;
 }
 
 // Tile origin of an operand for K-tile starting at k0 (t0 = first output row/column of the tile).
@@ -86,15 +84,7 @@ __device__ __forceinline__ const __bf16* tile_ptr(const __bf16* P, long ld, int 
     return KM ? P + (long)t0 * ld + k0 : P + k0 * ld + t0;
 }
 
-// DMA half h (= the issuing group) of one operand image: 4 wave-instructions of 1 KiB.
-__device__ __forceinline__ void dma_half(const __bf16* tile0, const int (&off)[4], char* img, int g, int wl) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        __builtin_amdgcn_global_load_lds((gbl_void*)(tile0 + off[j]),
-                                         (lds_void*)(img + (g * 1024 + (wl * 4 + j) * 64) * 16), 16, 0, 0);
-}
-
-// MN-major image of the spread schedule: eight [64 k][32 col] sub-images of 4 KiB (64-byte rows), so that
+// MN-major image: eight [64 k][32 col] sub-images of 4 KiB (64-byte rows), so that
 // every set of columns the phases read (a 64-column A block, the 32-column halves of the B blocks) is a whole
 // number of 1-KiB DMA pieces.  The 32-byte halves of a row are swapped on odd 8-row groups, which keeps the
 // ds_read_b64_tr_b16 reads conflict-free (the 8 rows a 32-lane group reads, r0..r0+3 and r0+8..r0+11, land
@@ -113,22 +103,19 @@ __device__ __forceinline__ int src_off_sub(int e, int ld) {
     return row * ld + 32 * s + 8 * ql;
 }
 
-// A64 (build define, default on): the MN-major A operand of the spread schedule (the weight gradient's dY) in four
+// The MN-major A operand (the weight gradient's dY) sits in four
 // [64 k][64 col] sub-images of 8 KiB with 128-byte rows instead of eight [64 k][32 col] ones: a 1-KiB DMA piece is
 // then 8 whole 128-byte lines of 8 token rows instead of 16 half lines of 16 rows (the A pieces the schedule issues
 // are whole 64-column blocks either way, so the schedule is unchanged; B keeps the 32-column halves it needs).  The
 // 32-byte segment of a row is swizzled by a64_f(row), which keeps the ds_read_b64_tr_b16 fragment reads
 // conflict-free (each 32-lane group reads rows {r0..r0+3, r0+8..r0+11} x one 32-byte segment: 8 distinct bank
 // groups; checked exhaustively on the host when the layout was written).
-#ifndef BPE_GPP_A64
-#define BPE_GPP_A64 1
-#endif
 __device__ __forceinline__ int a64_f(int r) { return ((r >> 1) & 1) | (((r >> 3) & 1) << 1); }
-__device__ __forceinline__ int sub64_off(int r, int c) {  // byte offset of (k-row r, column c) in the A64 image
+__device__ __forceinline__ int sub64_off(int r, int c) {  // byte offset of (k-row r, column c) in that image
     const int cc = c & 63;
     return (c >> 6) * 8192 + r * 128 + (((cc >> 4) ^ a64_f(r)) << 5) + ((cc & 15) << 1);
 }
-// source offset (elements from the tile origin) of 16-byte image chunk e (0..2047) of the A64 image: sub-image
+// source offset (elements from the tile origin) of 16-byte image chunk e (0..2047) of that image: sub-image
 // e >> 9, piece (8 k-rows) (e >> 6) & 7, lane e & 63 -> k-row 8 piece + lane / 8, physical chunk lane & 7
 __device__ __forceinline__ int src_off_sub64(int e, int ld) {
     const int s = e >> 9, q = (e >> 6) & 7, ln = e & 63;
@@ -143,23 +130,17 @@ __device__ __forceinline__ bf16x8 frag_a64(char* img, int tb, int ks, int l) {
 }
 
 // MFMA operand fragment of 16-row/col block tb, k-step ks: lane l gets X[t = 16 tb + (l & 15)][k = 32 ks + 8 (l >> 4) + j].
-// SUB: MN-major operands use the sub-image layout above (spread schedule) instead of [64][256] 512-byte rows.
-template <bool KM, bool SUB = false>
+// KM: a K-major image; otherwise the 32-column sub-images (the MN-major A operand reads frag_a64 instead).
+template <bool KM>
 __device__ __forceinline__ bf16x8 frag(char* img, int tb, int ks, int l) {
     if constexpr (KM) {
         const int row = tb * 16 + (l & 15);
         const int ch = (4 * ks + (l >> 4)) ^ fk(l & 15);
         return fa::lds_row16(img, row * 128 + (ch << 4));
-    } else if constexpr (SUB) {
-        const int r = 32 * ks + 8 * (l >> 4) + ((l & 15) >> 2);
-        const int c = tb * 16 + 4 * (l & 3);
-        return fa::lds_tr_pair(img, sub_off(r, c), sub_off(r + 4, c));
     } else {
         const int r = 32 * ks + 8 * (l >> 4) + ((l & 15) >> 2);
         const int c = tb * 16 + 4 * (l & 3);
-        const int o0 = r * 512 + (((c >> 3) ^ sig(r)) << 4) + ((c & 7) << 1);
-        const int o1 = (r + 4) * 512 + (((c >> 3) ^ sig(r + 4)) << 4) + ((c & 7) << 1);
-        return fa::lds_tr_pair(img, o0, o1);
+        return fa::lds_tr_pair(img, sub_off(r, c), sub_off(r + 4, c));
     }
 }
 
@@ -203,7 +184,7 @@ __device__ __forceinline__ void bar() {
 
 // Per-wave phase stamps (a diagnostic variant build: ops.build --variant pstamps -D BPE_GPP_PHASE_STAMPS; read by
 // benchmarks/gemm_phase_stamps.py): every wave records s_memtime at four events of each phase of K-tiles
-// PST_KT0 .. PST_KT0 + PST_NKT - 1 of the one-tile kernel's spread schedule -- 0 section start (before its
+// PST_KT0 .. PST_KT0 + PST_NKT - 1 of the one-tile kernel's K-tile loop -- 0 section start (before its
 // fragment reads), 1 after its wait (reads / DMA retired), 2 after the barrier (MFMA section start), 3 after the
 // MFMA issue (before the closing barrier) -- into LDS above the two stages (no VMEM traffic, so the kernel's
 // vmcnt accounting is untouched), copied to g_gpp_phase at the end for workgroups 0 .. 1023.
@@ -225,22 +206,22 @@ __device__ __forceinline__ void pst(int kt, int p, int e) {
 #define PST(p, e)
 #endif
 
-template <bool AK, bool BKM, bool SUB = false>
+template <bool AK>
 __device__ __forceinline__ void load_a(Frags& f, char* img, int g, int m, int l) {
 #pragma unroll
     for (int ib = 0; ib < 4; ++ib)
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            if constexpr (!AK && SUB && BPE_GPP_A64) f.a[ib][ks] = frag_a64(img, 8 * g + 4 * m + ib, ks, l);
-            else f.a[ib][ks] = frag<AK, SUB>(img, 8 * g + 4 * m + ib, ks, l);
+            if constexpr (AK) f.a[ib][ks] = frag<true>(img, 8 * g + 4 * m + ib, ks, l);
+            else f.a[ib][ks] = frag_a64(img, 8 * g + 4 * m + ib, ks, l);
         }
 }
-template <bool AK, bool BKM, bool SUB = false>
+template <bool BKM>
 __device__ __forceinline__ void load_b(Frags& f, char* img, int wl, int n, int l) {
 #pragma unroll
     for (int jb = 0; jb < 2; ++jb)
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) f.b[jb][ks] = frag<BKM, SUB>(img, 4 * wl + 2 * n + jb, ks, l);
+        for (int ks = 0; ks < 2; ++ks) f.b[jb][ks] = frag<BKM>(img, 4 * wl + 2 * n + jb, ks, l);
 }
 
 // An empty asm "use" of the accumulators a section just issued MFMAs into (no instruction is emitted).
@@ -256,7 +237,7 @@ __device__ __forceinline__ void pin_quadrant(f32x4 (&acc)[8][4], int m, int n, i
         for (int jb = 0; jb < 2; ++jb) asm volatile("" ::"v"(acc[4 * m + ib][2 * n + jb]));
 }
 
-template <int F8 = 0>
+template <int F8>
 __device__ __forceinline__ void mma_quadrant(f32x4 (&acc)[8][4], const Frags& f, int m, int n) {
 #pragma unroll
     for (int ib = 0; ib < 4; ++ib)
@@ -274,7 +255,7 @@ __device__ __forceinline__ void mma_quadrant(f32x4 (&acc)[8][4], const Frags& f,
 }
 
 // Half of a quadrant (i-blocks 2h, 2h+1): the MFMA section can then issue one DMA piece between its halves.
-template <int F8 = 0>
+template <int F8>
 __device__ __forceinline__ void mma_half(f32x4 (&acc)[8][4], const Frags& f, int m, int n, int h) {
 #pragma unroll
     for (int ib = 2 * h; ib < 2 * h + 2; ++ib)
@@ -297,63 +278,12 @@ __device__ __forceinline__ void mma_half(f32x4 (&acc)[8][4], const Frags& f, int
 // profiles/bench/ab_r5_prea_fused.log; and issuing the barrier that ends an MFMA section before its last i-block --
 // 6-10 % slower, profiles/bench/ab_r5_earlybar_prio.log.)
 
-// One K-tile: four (load section, barrier, MFMA section, barrier) phases.  `cur` is read, `nxt` is the DMA
-// target (the __restrict__ parameters let the wait-count pass see that the fragment reads do not alias the
-// in-flight DMA; without it hipcc drains the DMA before the first read).
-// DIAG (timing diagnostics, numerically wrong): 1 = no DMA in the loop, 2 = fragment reads only in phase 0,
-// 6 = no epilogue global stores (gemm_pp_kernel),
-// 3 = no MFMA, 4 = no stagger between the groups, 5 = DMA issued but never waited for (issue cost only)
-template <bool AK, bool BKM, int DIAG>
-__device__ __forceinline__ void ktile(char* __restrict__ cur, char* __restrict__ nxt, bool dma, const __bf16* an,
-                                      const __bf16* bn, const int (&oa)[4], const int (&ob)[4], int g, int wl,
-                                      int l, f32x4 (&acc)[8][4]) {
-    Frags f;
-    char* Ac = cur;
-    char* Bc = cur + OPB;
-    // phase 0: (m0, n0)
-    load_a<AK, BKM>(f, Ac, g, 0, l);
-    load_b<AK, BKM>(f, Bc, wl, 0, l);
-    if (DIAG == 1) dma = false;
-    if (dma) dma_half(an, oa, nxt, g, wl);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    bar();
-    if (DIAG != 3) mma_quadrant(acc, f, 0, 0);
-    bar();
-    // phase 1: (m0, n1)
-    if (DIAG != 2) load_b<AK, BKM>(f, Bc, wl, 1, l);
-    if (dma) dma_half(bn, ob, nxt + OPB, g, wl);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    bar();
-    if (DIAG != 3) mma_quadrant(acc, f, 0, 1);
-    bar();
-    // phase 2: (m1, n1)
-    if (DIAG != 2) load_a<AK, BKM>(f, Ac, g, 1, l);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    bar();
-    if (DIAG != 3) mma_quadrant(acc, f, 1, 1);
-    bar();
-    // phase 3: (m1, n0); retire this wave's DMA of the next K-tile before the barrier
-    if (DIAG != 2) load_b<AK, BKM>(f, Bc, wl, 0, l);
-    if (DIAG == 5)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // DMA issued but never waited for
-    else
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    bar();
-    if (DIAG != 3) mma_quadrant(acc, f, 1, 0);
-    bar();
-    if (DIAG == 3) {  // keep the fragments live
-#pragma unroll
-        for (int ib = 0; ib < 4; ++ib) acc[ib][0][0] += (float)f.a[ib][0][0] + (float)f.b[ib & 1][1][1];
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------
-// Spread DMA schedule (both operands K-major, i.e. the forward GEMM).  A diagnostic build showed where the
-// burst schedule above loses: issuing the next K-tile's 8 LDS-DMA instructions per wave in phases 0-1 only
-// (4 per load section, each ~100-185 cycles to issue beside the fragment reads) makes those load sections
-// longer than the partner wave's 256-cycle MFMA section; with the DMA removed (DIAG 1) the same loop runs
-// 1.45-1.55x faster, and issuing it without ever waiting for it (DIAG 5) is no faster than waiting for it
-// (profiles/bench/gpp_diag_b128.log) -- issue placement, not latency.  Here every load section issues 2
+// The DMA schedule.  A K-tile is four (load section, barrier, MFMA section, barrier) phases.  Issuing the next
+// K-tile's 8 LDS-DMA instructions per wave as two bursts of 4 (an earlier form, removed) made those load sections
+// longer than the partner wave's 256-cycle MFMA section: each issue costs ~100-185 cycles beside the fragment
+// reads, and a build that issued the DMA without ever waiting for it was no faster than one that waited
+// (profiles/bench/gpp_diag_b128.log) -- issue placement, not latency.  So every load section issues 2
 // pieces, in the order the next K-tile's phases read them:
 //   phase 0: A rows [128g, +64)   (read by this group in phase 0 of kt+1)
 //   phase 1: half g of B rows {64w' + [0, 32)}   (both groups, phase 0 / 3)
@@ -364,24 +294,15 @@ __device__ __forceinline__ void ktile(char* __restrict__ cur, char* __restrict__
 // after group 0, never before the issuing wave's wait).  WAR: a region of the other buffer is refilled at
 // least one barrier after its last read of K-tile kt-1 (A rows: phases 0 / 2, B halves: phases 3 / 1).
 // Last K-tile (no issue): vmcnt(2) in phase 0 (B rows [32, 64) of this tile), vmcnt(0) afterwards.
-#ifndef BPE_GPP_RELAX  // build define: phase 2 of the spread schedule waits vmcnt(6) (1) or vmcnt(4) (0)
-#define BPE_GPP_RELAX 1
-#endif
 
 struct SpreadOff {
     int a0[2], a1[2], b0[2], b1[2];  // source offsets (elements from the K-tile origin) of this thread's pieces
     int la0, la1, lb0, lb1;          // wave-uniform LDS chunk index of each piece pair (piece j at + 64 j)
 };
 
-// Chunk e of either image kind: K-major [256][64] (A rows / B rows = output index) or the MN-major sub-image
-// layout.  The piece sets line up in both: chunks [1024 g + 512 m, +512) are output rows / columns
+// Source offset of chunk e of either image kind: K-major [256][64] (A rows / B rows = output index) or an MN-major
+// sub-image layout.  The piece sets line up in all: chunks [1024 g + 512 m, +512) are output rows / columns
 // [128 g + 64 m, +64) and chunks {512 w' + 256 h + [0, 256)} the 32-wide half h of block w'.
-template <bool KM>
-__device__ __forceinline__ int spread_src(int e, int ld) {
-    if constexpr (KM) return src_off<true>(e, ld);
-    else return src_off_sub(e, ld);
-}
-
 template <bool AK, bool BKM>
 __device__ __forceinline__ SpreadOff spread_offsets(int g, int wl, int l, int lda, int ldb) {
     SpreadOff o;
@@ -391,81 +312,62 @@ __device__ __forceinline__ SpreadOff spread_offsets(int g, int wl, int l, int ld
     o.lb1 = o.lb0 + 256;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        if constexpr (!AK && BPE_GPP_A64) {
-            o.a0[j] = src_off_sub64(o.la0 + 64 * j + l, lda);
-            o.a1[j] = src_off_sub64(o.la1 + 64 * j + l, lda);
-        } else {
-            o.a0[j] = spread_src<AK>(o.la0 + 64 * j + l, lda);
-            o.a1[j] = spread_src<AK>(o.la1 + 64 * j + l, lda);
-        }
-        o.b0[j] = spread_src<BKM>(o.lb0 + 64 * j + l, ldb);
-        o.b1[j] = spread_src<BKM>(o.lb1 + 64 * j + l, ldb);
+        o.a0[j] = AK ? src_off_km(o.la0 + 64 * j + l, lda) : src_off_sub64(o.la0 + 64 * j + l, lda);
+        o.a1[j] = AK ? src_off_km(o.la1 + 64 * j + l, lda) : src_off_sub64(o.la1 + 64 * j + l, lda);
+        o.b0[j] = BKM ? src_off_km(o.lb0 + 64 * j + l, ldb) : src_off_sub(o.lb0 + 64 * j + l, ldb);
+        o.b1[j] = BKM ? src_off_km(o.lb1 + 64 * j + l, ldb) : src_off_sub(o.lb1 + 64 * j + l, ldb);
     }
     return o;
 }
 
-// Cache policy of the in-loop LDS-DMA loads per operand (variant builds; 0 = default, 2 = nt: the line is the first
-// evicted from the XCD's L2).  Measured and left at 0 (profiles/bench/ab_dma_policy_r6.log): nt on A (activations)
-// -2 to -3 % on the MN x MN weight-gradient GEMMs on one box, +1 to +6 % on another, and slower K-major forward /
-// QKV + RoPE / ppt LM-head GEMMs (end to end -0.6-0.9 %); nt on B (weights, re-read every round) slower everywhere.
-#ifndef BPE_GPP_DMA_POL_A
-#define BPE_GPP_DMA_POL_A 0
-#endif
-#ifndef BPE_GPP_DMA_POL_B
-#define BPE_GPP_DMA_POL_B 0
-#endif
-
-template <int POL>
-__device__ __forceinline__ void dma_ld(const __bf16* src, char* dst) {
-    __builtin_amdgcn_global_load_lds((gbl_void*)src, (lds_void*)dst, 16, 0, POL);
-}
-
-template <int POL = 0>
+// The in-loop LDS-DMA loads keep the default cache policy: nt, per operand, was measured and dropped
+// (profiles/bench/ab_dma_policy_r6.log: on A (activations) -2 to -3 % on the MN x MN weight-gradient GEMMs on one
+// box, +1 to +6 % on another, and slower K-major forward / QKV + RoPE / ppt LM-head GEMMs, end to end -0.6-0.9 %;
+// on B (weights, re-read every round) slower everywhere).
 __device__ __forceinline__ void dma_one(const __bf16* tile0, int off, char* img, int lbase) {
-    dma_ld<POL>(tile0 + off, img + lbase * 16);
+    __builtin_amdgcn_global_load_lds((gbl_void*)(tile0 + off), (lds_void*)(img + lbase * 16), 16, 0, 0);
 }
 
-template <int POL = 0>
 __device__ __forceinline__ void dma_pair(const __bf16* tile0, const int (&off)[2], char* img, int lbase) {
 #pragma unroll
-    for (int j = 0; j < 2; ++j) dma_ld<POL>(tile0 + off[j], img + (lbase + 64 * j) * 16);
+    for (int j = 0; j < 2; ++j) dma_one(tile0, off[j], img, lbase + 64 * j);
 }
 
-// SPLIT (spread mode 2, the weight-gradient layout): the second piece of each
-// pair is issued by the same wave in its MFMA section,
-// between the two halves of the quadrant, so a load section carries one piece; the waits become vmcnt(3).
+// One K-tile.  `cur` is read, `nxt` is the DMA target (the __restrict__ parameters let the wait-count pass see that
+// the fragment reads do not alias the in-flight DMA; without it hipcc drains the DMA before the first read).
+// SPLIT (both operands MN-major, the weight gradient): the second piece of each pair is issued by the same wave in
+// its MFMA section, between the two halves of the quadrant, so a load section carries one piece; the waits become
+// vmcnt(3).  Weight gradients +1-3 %, the other layouts 3 % slower that way (profiles/bench/ab_gpp_dma_split.log).
 // FIRST: K-tile 0 of a tile, whose image was retired (vmcnt(0)) before the loop.  Its phases 0-1 would only retire
 // pieces of that image, so they wait for LDS only; phases 2-3 retire the first pieces of K-tile 1 (read before any
 // wait of K-tile 1) as always.  In the persistent kernel this lets the previous tile's epilogue stores, which
 // share the vmcnt counter with the DMA, drain during the first two phases instead of before them.
-template <bool AK, bool BKM, int DIAG, bool SPLIT = false, int F8 = 0>
+template <bool AK, bool BKM, int F8>
 __device__ __forceinline__ void ktile_spread(char* __restrict__ cur, char* __restrict__ nxt, bool dma,
                                              const __bf16* an, const __bf16* bn, const SpreadOff& so, int g, int wl,
                                              int l, f32x4 (&acc)[8][4], bool first = false, int kt_idx = -1) {
     (void)kt_idx;  // phase stamps builds only
+    constexpr bool SPLIT = !AK && !BKM;
     Frags f;
     char* Ac = cur;
     char* Bc = cur + OPB;
-    constexpr int PA = BPE_GPP_DMA_POL_A, PB = BPE_GPP_DMA_POL_B;
-    if (DIAG == 1) dma = false;
     // one phase: fragment reads (done by the caller), pieces of (tile, off, img, lbase), wait, barrier, MFMAs
-    // RELAX: phase 2 (m1, n1) retires nothing that a read before phase 3's barrier needs (its own A rows of K-tile
+    // relax: phase 2 (m1, n1) retires nothing that a read before phase 3's barrier needs (its own A rows of K-tile
     // kt + 1 are first read in phase 0 of kt + 1; the group's B halves it issued are retired in phase 3 / phase 0),
     // so it waits vmcnt(6) and leaves the piece pair issued two load sections ago in flight one section longer
     auto phase = [&](const __bf16* t0, const int (&off)[2], char* img, int lb, int m, int n, bool last_nodma_wait2,
                      bool relax = false) {
-        const bool is_a = img == nxt;  // the A image sits at the stage origin, B at + OPB
         const int ph = 2 * m + (m ? 1 - n : n);  // (m0,n0) 0, (m0,n1) 1, (m1,n1) 2, (m1,n0) 3
         (void)ph;
         if (dma) {
-            if constexpr (SPLIT) is_a ? dma_one<PA>(t0, off[0], img, lb) : dma_one<PB>(t0, off[0], img, lb);
-            else is_a ? dma_pair<PA>(t0, off, img, lb) : dma_pair<PB>(t0, off, img, lb);
+            if constexpr (SPLIT) dma_one(t0, off[0], img, lb);
+            else dma_pair(t0, off, img, lb);
         }
         if (first && m == 0) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         } else if (dma) {
             if constexpr (SPLIT) asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)" ::: "memory");
-            else if (BPE_GPP_RELAX && relax) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
+            else if (relax) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
         } else if (last_nodma_wait2) {
             asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
@@ -479,7 +381,7 @@ __device__ __forceinline__ void ktile_spread(char* __restrict__ cur, char* __res
             mma_half<F8>(acc, f, m, n, 0);
             if (dma) {
                 __builtin_amdgcn_sched_barrier(0);
-                is_a ? dma_one<PA>(t0, off[1], img, lb + 64) : dma_one<PB>(t0, off[1], img, lb + 64);
+                dma_one(t0, off[1], img, lb + 64);
                 __builtin_amdgcn_sched_barrier(0);
             }
             mma_half<F8>(acc, f, m, n, 1);
@@ -491,20 +393,20 @@ __device__ __forceinline__ void ktile_spread(char* __restrict__ cur, char* __res
     };
     // phase 0: (m0, n0)
     PST(0, 0);
-    load_a<AK, BKM, true>(f, Ac, g, 0, l);
-    load_b<AK, BKM, true>(f, Bc, wl, 0, l);
+    load_a<AK>(f, Ac, g, 0, l);
+    load_b<BKM>(f, Bc, wl, 0, l);
     phase(an, so.a0, nxt, so.la0, 0, 0, true);
     // phase 1: (m0, n1)
     PST(1, 0);
-    load_b<AK, BKM, true>(f, Bc, wl, 1, l);
+    load_b<BKM>(f, Bc, wl, 1, l);
     phase(bn, so.b0, nxt + OPB, so.lb0, 0, 1, false);
     // phase 2: (m1, n1)
     PST(2, 0);
-    load_a<AK, BKM, true>(f, Ac, g, 1, l);
+    load_a<AK>(f, Ac, g, 1, l);
     phase(bn, so.b1, nxt + OPB, so.lb1, 1, 1, false, true);
     // phase 3: (m1, n0)
     PST(3, 0);
-    load_b<AK, BKM, true>(f, Bc, wl, 0, l);
+    load_b<BKM>(f, Bc, wl, 0, l);
     phase(an, so.a1, nxt, so.la1, 1, 0, false);
 }
 
@@ -558,32 +460,14 @@ enum { EPI_NONE = 0, EPI_SWIGLU_BWD = 1, EPI_SWIGLU_FWD = 2, EPI_ROPE = 3, EPI_S
 constexpr bool is_swf(int e) { return e == EPI_SWIGLU_FWD || e == EPI_SWIGLU_FWD8; }
 constexpr int A8T_STRIDE = 144;               // bytes per token row of the a8 transpose tile (conflict-free reads)
 constexpr int A8T_BYTES = 128 * A8T_STRIDE;   // one pass: 128 token rows x 128 a columns
-// 1: the SwiGLU epilogues' arithmetic on the packed fp32 VALU, two elements per instruction (common.h
-// fast_sigmoid2; bitwise the same results); 0: one element per instruction (A/B variant builds)
-#ifndef BPE_GPP_PK
-#define BPE_GPP_PK 1
-#endif
-// SwiGLU-backward epilogue timing diagnostics (variant builds only, numerically wrong): bit 0 = no g / u loads,
-// bit 1 = no dg / du stores
-#ifndef BPE_GPP_EPIDIAG
-#define BPE_GPP_EPIDIAG 0
-#endif
 // Store policy of the fused epilogues' outputs (MI355X_MICROARCH store flavours): 0 = plain (the line stays in
 // the XCD's L2), 1 = sc1 (written through and dropped from L2), 2 = nt.  The outputs are 0.6-1.1 GB streams read
 // by later kernels only; kept in L2 they evict the main loop's operand tiles.  Per output, measured per call at
 // GPT-2 B 128 (profiles/bench/ab_epilogue_store_policy_r6.log):
-#ifndef BPE_GPP_POL_SWB  // SwiGLU backward dg / du (sc1: 0.67 vs 0.70-0.71 ms per GPT-2 call)
-#define BPE_GPP_POL_SWB 1
-#endif
-#ifndef BPE_GPP_POL_SWF_GU  // SwiGLU forward gu (nt; sc1 on gu and a: 0.85 vs 0.82 ms)
-#define BPE_GPP_POL_SWF_GU 2
-#endif
-#ifndef BPE_GPP_POL_SWF_A  // SwiGLU forward a
-#define BPE_GPP_POL_SWF_A 0
-#endif
-#ifndef BPE_GPP_POL_ROPE  // QKV + RoPE output (sc1: 0.426-0.428 vs 0.433-0.434 ms)
-#define BPE_GPP_POL_ROPE 1
-#endif
+constexpr int POL_SWB = 1;     // SwiGLU backward dg / du (sc1: 0.67 vs 0.70-0.71 ms per GPT-2 call)
+constexpr int POL_SWF_GU = 2;  // SwiGLU forward gu (nt; sc1 on gu and a: 0.85 vs 0.82 ms)
+constexpr int POL_SWF_A = 0;   // SwiGLU forward a
+constexpr int POL_ROPE = 1;    // QKV + RoPE output (sc1: 0.426-0.428 vs 0.433-0.434 ms)
 
 // 16-byte store of v at byte offset off from the wave-uniform base (a buffer resource for the cache-policy forms:
 // built from uniform values, so it lives in SGPRs -- no waterfall)
@@ -647,8 +531,7 @@ __device__ __forceinline__ void tile_rc(int t, int tiles_m, int tiles_n, int gm,
 template <int EPI, int F8, int NPASS>
 __device__ __forceinline__ void epilogue_bf16(const f32x4 (&acc)[8][4], char* stg, int g, int wl, int l, int tid,
                                               int i0, int j0, int jb, __bf16* C, long ldc, float beta, const Epi& ep,
-                                              bool st_on, bool tail, int sid, char* xtra = nullptr,
-                                              float* amx = nullptr) {
+                                              bool tail, int sid, char* xtra = nullptr, float* amx = nullptr) {
     constexpr int RP = BT / NPASS;  // tile rows per pass
     float osc = 1.f;  // F8: the product of the operands' inverse scales (device-resident, one load)
     if constexpr (F8 != 0) osc = ep.sa[0] * ep.sb[0];
@@ -677,11 +560,6 @@ __device__ __forceinline__ void epilogue_bf16(const f32x4 (&acc)[8][4], char* st
 #pragma unroll
             for (int q = 0; q < NQ; ++q) {
                 const long ro = (long)(i0 + r0 + q * 16 + (tid >> 5)) * ep.ld + j0 + c * 8;
-                if (BPE_GPP_EPIDIAG & 1) {  // timing diagnostic: no g / u loads (numerically wrong)
-                    gv[q] = u16x8{(unsigned short)ro, 1, 2, 3, 4, 5, 6, 7};
-                    uv[q] = u16x8{(unsigned short)(ro >> 16), 1, 2, 3, 4, 5, 6, 7};
-                    continue;
-                }
                 gv[q] = ld_stream(reinterpret_cast<const u16x8*>(ep.gu + ro));  // read once
                 uv[q] = ld_stream(reinterpret_cast<const u16x8*>(ep.gu + ro + ep.F));
             }
@@ -697,7 +575,6 @@ __device__ __forceinline__ void epilogue_bf16(const f32x4 (&acc)[8][4], char* st
                 const u16x8 v = *reinterpret_cast<const u16x8*>(stg + i * 512 + ((c ^ (i & 15)) << 4));
                 const long ro = (long)(i0 + r0 + i) * ep.ld + j0 + c * 8;
                 u16x8 dg, du;
-#if BPE_GPP_PK
 #pragma unroll
                 for (int e = 0; e < 8; e += 2) {  // pairs on the packed fp32 VALU (same math and rounding)
                     const f32x2 gg = {bf2f(gv[q][e]), bf2f(gv[q][e + 1])}, uu = {bf2f(uv[q][e]), bf2f(uv[q][e + 1])};
@@ -709,22 +586,11 @@ __device__ __forceinline__ void epilogue_bf16(const f32x4 (&acc)[8][4], char* st
                     dg[e] = f2bf(b.x);
                     dg[e + 1] = f2bf(b.y);
                 }
-#else
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float gg = bf2f(gv[q][e]), uu = bf2f(uv[q][e]), d = bf2f(v[e]);
-                    const float sg = fast_sigmoid(gg);
-                    du[e] = f2bf(d * (gg * sg));
-                    dg[e] = f2bf(d * uu * sg * (1.f + gg * (1.f - sg)));
-                }
-#endif
-                if (st_on && (!(BPE_GPP_EPIDIAG & 2) || ep.prio == 77)) {  // EPIDIAG 2: no stores (timing)
-                    // offsets from the tile's first output element (wave-uniform base)
-                    __bf16* tb = ep.dgu + (long)(i0 + r0) * ep.ld + j0;
-                    const unsigned o = (unsigned)(((long)i * ep.ld + c * 8) * 2);
-                    st16<BPE_GPP_POL_SWB>(tb, o, dg);
-                    st16<BPE_GPP_POL_SWB>(tb, o + (unsigned)ep.F * 2, du);
-                }
+                // offsets from the tile's first output element (wave-uniform base)
+                __bf16* tb = ep.dgu + (long)(i0 + r0) * ep.ld + j0;
+                const unsigned o = (unsigned)(((long)i * ep.ld + c * 8) * 2);
+                st16<POL_SWB>(tb, o, dg);
+                st16<POL_SWB>(tb, o + (unsigned)ep.F * 2, du);
             }
         } else if constexpr (EPI == EPI_SWIGLU_FWD) {
             // row i: g = staged columns [0, 128), u = [128, 256); 16 threads x 16 bytes per 256-byte segment
@@ -738,31 +604,20 @@ __device__ __forceinline__ void epilogue_bf16(const f32x4 (&acc)[8][4], char* st
                 const u16x8 gv = *reinterpret_cast<const u16x8*>(stg + i * 512 + ((c ^ (i & 15)) << 4));
                 const u16x8 uv = *reinterpret_cast<const u16x8*>(stg + i * 512 + (((16 + c) ^ (i & 15)) << 4));
                 u16x8 av;
-#if BPE_GPP_PK
 #pragma unroll
-                for (int e = 0; e < 8; e += 2) {
+                for (int e = 0; e < 8; e += 2) {  // pairs on the packed fp32 VALU
                     const f32x2 gg = {bf2f(gv[e]), bf2f(gv[e + 1])};
                     const f32x2 a = gg * fast_sigmoid2(gg) * f32x2{bf2f(uv[e]), bf2f(uv[e + 1])};
                     av[e] = f2bf(a.x);
                     av[e + 1] = f2bf(a.y);
                 }
-#else
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const float gg = bf2f(gv[e]);
-                    av[e] = f2bf(gg * fast_sigmoid(gg) * bf2f(uv[e]));
-                }
-#endif
-                const long r = i0 + r0 + i;
                 // gu is next read by the backward, long after this step's forward: streaming stores
-                if (st_on) {
-                    __bf16* tg = ep.dgu + (long)(i0 + r0) * ep.ld + jb;
-                    const unsigned og = (unsigned)(((long)i * ep.ld + c * 8) * 2);
-                    st16<BPE_GPP_POL_SWF_GU>(tg, og, gv);
-                    st16<BPE_GPP_POL_SWF_GU>(tg, og + (unsigned)ep.F * 2, uv);
-                    st16<BPE_GPP_POL_SWF_A>(ep.act + (long)(i0 + r0) * ep.ld_act + jb,
-                                            (unsigned)(((long)i * ep.ld_act + c * 8) * 2), av);
-                }
+                __bf16* tg = ep.dgu + (long)(i0 + r0) * ep.ld + jb;
+                const unsigned og = (unsigned)(((long)i * ep.ld + c * 8) * 2);
+                st16<POL_SWF_GU>(tg, og, gv);
+                st16<POL_SWF_GU>(tg, og + (unsigned)ep.F * 2, uv);
+                st16<POL_SWF_A>(ep.act + (long)(i0 + r0) * ep.ld_act + jb, (unsigned)(((long)i * ep.ld_act + c * 8) * 2),
+                                av);
             }
         } else if constexpr (EPI == EPI_SWIGLU_BWD8) {
             // in two 64-row halves (registers: one half's g / u and e5m2 results at a time); per half, dg then du go
@@ -811,11 +666,9 @@ __device__ __forceinline__ void epilogue_bf16(const f32x4 (&acc)[8][4], char* st
                                    pack4_fp8<1>(dgv[4] * sc, dgv[5] * sc, dgv[6] * sc, dgv[7] * sc)};
                     qu[qq] = uint2{pack4_fp8<1>(duv[0] * sc, duv[1] * sc, duv[2] * sc, duv[3] * sc),
                                    pack4_fp8<1>(duv[4] * sc, duv[5] * sc, duv[6] * sc, duv[7] * sc)};
-                    if (st_on) {
-                        uint8_t* row = ep.a8 + (long)(i0 + r0 + i) * W + j0 + c * 8;
-                        *reinterpret_cast<uint2*>(row) = qg[qq];
-                        *reinterpret_cast<uint2*>(row + ep.F) = qu[qq];
-                    }
+                    uint8_t* row = ep.a8 + (long)(i0 + r0 + i) * W + j0 + c * 8;
+                    *reinterpret_cast<uint2*>(row) = qg[qq];
+                    *reinterpret_cast<uint2*>(row + ep.F) = qu[qq];
                 }
 #pragma unroll
                 for (int o = 0; o < 2; ++o) {  // dg, then du: [64 tokens][256 columns] -> [256 columns][64 tokens]
@@ -840,9 +693,8 @@ __device__ __forceinline__ void epilogue_bf16(const f32x4 (&acc)[8][4], char* st
                             lo |= ((wv[k] >> (8 * j)) & 0xffu) << (8 * k);
                             hi |= ((wv[k + 4] >> (8 * j)) & 0xffu) << (8 * k);
                         }
-                        if (st_on)
-                            *reinterpret_cast<uint2*>(ep.a8t + ((long)o * ep.F + j0 + 4 * f4 + j) * ep.ld_a8t + i0 + r0 +
-                                                      64 * b + 8 * tg) = uint2{lo, hi};
+                        *reinterpret_cast<uint2*>(ep.a8t + ((long)o * ep.F + j0 + 4 * f4 + j) * ep.ld_a8t + i0 + r0 +
+                                                  64 * b + 8 * tg) = uint2{lo, hi};
                     }
                 }
             }
@@ -872,13 +724,11 @@ __device__ __forceinline__ void epilogue_bf16(const f32x4 (&acc)[8][4], char* st
                 }
                 const uint2 q8 = {pack4_fp8<0>(v[0] * sc, v[1] * sc, v[2] * sc, v[3] * sc),
                                   pack4_fp8<0>(v[4] * sc, v[5] * sc, v[6] * sc, v[7] * sc)};
-                if (st_on) {
-                    __bf16* tg = ep.dgu + (long)(i0 + r0) * ep.ld + jb;
-                    const unsigned og = (unsigned)(((long)i * ep.ld + c * 8) * 2);
-                    st16<BPE_GPP_POL_SWF_GU>(tg, og, gv);
-                    st16<BPE_GPP_POL_SWF_GU>(tg, og + (unsigned)ep.F * 2, uv);
-                    *reinterpret_cast<uint2*>(ep.a8 + (long)(i0 + r0 + i) * ep.F + jb + c * 8) = q8;
-                }
+                __bf16* tg = ep.dgu + (long)(i0 + r0) * ep.ld + jb;
+                const unsigned og = (unsigned)(((long)i * ep.ld + c * 8) * 2);
+                st16<POL_SWF_GU>(tg, og, gv);
+                st16<POL_SWF_GU>(tg, og + (unsigned)ep.F * 2, uv);
+                *reinterpret_cast<uint2*>(ep.a8 + (long)(i0 + r0 + i) * ep.F + jb + c * 8) = q8;
                 *reinterpret_cast<uint2*>(xtra + i * A8T_STRIDE + c * 8) = q8;
             }
             *amx = am;
@@ -897,9 +747,7 @@ __device__ __forceinline__ void epilogue_bf16(const f32x4 (&acc)[8][4], char* st
                     lo |= ((wv[k] >> (8 * j)) & 0xffu) << (8 * k);
                     hi |= ((wv[k + 4] >> (8 * j)) & 0xffu) << (8 * k);
                 }
-                if (st_on)
-                    *reinterpret_cast<uint2*>(ep.a8t + (long)(jb + 4 * f4 + j) * ep.ld_a8t + i0 + r0 + 8 * tg) =
-                        uint2{lo, hi};
+                *reinterpret_cast<uint2*>(ep.a8t + (long)(jb + 4 * f4 + j) * ep.ld_a8t + i0 + r0 + 8 * tg) = uint2{lo, hi};
             }
         } else if constexpr (EPI == EPI_ROPE) {
             // this thread's 8 columns are one quarter of a pair block of one head: the cos / sin loads of its rows
@@ -933,7 +781,7 @@ __device__ __forceinline__ void epilogue_bf16(const f32x4 (&acc)[8][4], char* st
                         v[2 * j + 1] = f2bf(a * sn[q][j] + b * cs[q][j]);
                     }
                 }
-                if (st_on) st16<BPE_GPP_POL_ROPE>(C + (long)(i0 + r0) * ldc + j0, (unsigned)(((long)i * ldc + c * 8) * 2), v);
+                st16<POL_ROPE>(C + (long)(i0 + r0) * ldc + j0, (unsigned)(((long)i * ldc + c * 8) * 2), v);
             }
         } else {
             __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -949,7 +797,7 @@ __device__ __forceinline__ void epilogue_bf16(const f32x4 (&acc)[8][4], char* st
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] = f2bf(bf2f(v[e]) + beta * bf2f(o[e]));
                 }
-                if (st_on) *reinterpret_cast<u16x8*>(cp) = v;
+                *reinterpret_cast<u16x8*>(cp) = v;
             }
         }
         if (h + 1 < NPASS || tail) {  // every read of the image retired before it is rewritten
@@ -960,7 +808,7 @@ __device__ __forceinline__ void epilogue_bf16(const f32x4 (&acc)[8][4], char* st
 }
 
 
-template <bool AK, bool BKM, bool SLAB, int DIAG, int EPI = EPI_NONE, int SPREAD = 0, int F8 = 0>
+template <bool AK, bool BKM, bool SLAB, int EPI = EPI_NONE, int F8 = 0>
 __global__ void __launch_bounds__(NT, 1)
 gemm_pp_kernel(const __bf16* __restrict__ A, long lda, const __bf16* __restrict__ B, long ldb,
                float* __restrict__ slab, __bf16* __restrict__ C, long ldc, float beta, int M, int N, int R,
@@ -996,7 +844,6 @@ gemm_pp_kernel(const __bf16* __restrict__ A, long lda, const __bf16* __restrict_
     }
 #endif
 
-    constexpr bool SPR = SPREAD != 0;
     if (ep.prio && g == 1) __builtin_amdgcn_s_setprio(1);  // g is wave-uniform (readfirstlane): a scalar branch
     f32x4 acc[8][4];
 #pragma unroll
@@ -1004,68 +851,41 @@ gemm_pp_kernel(const __bf16* __restrict__ A, long lda, const __bf16* __restrict_
 #pragma unroll
         for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    if constexpr (SPR) {
-        SpreadOff so = spread_offsets<AK, BKM>(g, wl, l, (int)lda, (int)ldb);
-        if constexpr (is_swf(EPI)) {
-            // group g DMAs B rows [128 g, +128) of the tile: group 1's are the u rows, F - 128 rows further on
-            static_assert(BKM, "SwiGLU forward: B = [W1; W3] is K-major");
-            if (g == 1) {
-                const int du = (ep.F - BT / 2) * (int)ldb;
+    SpreadOff so = spread_offsets<AK, BKM>(g, wl, l, (int)lda, (int)ldb);
+    if constexpr (is_swf(EPI)) {
+        // group g DMAs B rows [128 g, +128) of the tile: group 1's are the u rows, F - 128 rows further on
+        static_assert(BKM, "SwiGLU forward: B = [W1; W3] is K-major");
+        if (g == 1) {
+            const int du = (ep.F - BT / 2) * (int)ldb;
 #pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    so.b0[j] += du;
-                    so.b1[j] += du;
-                }
+            for (int j = 0; j < 2; ++j) {
+                so.b0[j] += du;
+                so.b1[j] += du;
             }
         }
-        {  // prologue: all of K-tile 0 (this wave's 8 pieces of the schedule), retired before the first read
-            const long k0 = (long)kb * BK;
-            const __bf16* a0 = tile_ptr<AK>(A, lda, i0, k0);
-            const __bf16* b0 = tile_ptr<BKM>(B, ldb, jb, k0);
-            dma_pair<BPE_GPP_DMA_POL_A>(a0, so.a0, smem, so.la0);
-            dma_pair<BPE_GPP_DMA_POL_B>(b0, so.b0, smem + OPB, so.lb0);
-            dma_pair<BPE_GPP_DMA_POL_B>(b0, so.b1, smem + OPB, so.lb1);
-            dma_pair<BPE_GPP_DMA_POL_A>(a0, so.a1, smem, so.la1);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            bar();
-        }
-        GPP_STAMP(1);
-        if (g == 1) bar();  // the stagger
-        for (int kt = 0; kt < nk; ++kt) {
-            char* cur = smem + (kt & 1) * STAGE;
-            char* nxt = smem + ((kt + 1) & 1) * STAGE;
-            const long k1 = (long)(kb + kt + 1) * BK;
-            ktile_spread<AK, BKM, DIAG, SPREAD == 2, F8>(cur, nxt, kt + 1 < nk, tile_ptr<AK>(A, lda, i0, k1),
-                                                         tile_ptr<BKM>(B, ldb, jb, k1), so, g, wl, l, acc, false, kt);
-        }
-    } else {
-        int oa[4], ob[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int e = g * 1024 + (wl * 4 + j) * 64 + l;
-            oa[j] = src_off<AK>(e, (int)lda);
-            ob[j] = src_off<BKM>(e, (int)ldb);
-        }
-        // prologue: K-tile 0, both halves (each group its own), then retire + barrier
-        {
-            const long k0 = (long)kb * BK;
-            dma_half(tile_ptr<AK>(A, lda, i0, k0), oa, smem, g, wl);
-            dma_half(tile_ptr<BKM>(B, ldb, j0, k0), ob, smem + OPB, g, wl);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            bar();
-        }
-        if (g == 1 && DIAG != 4) bar();  // the stagger: group 1 runs one barrier interval behind group 0
-        for (int kt = 0; kt < nk; ++kt) {
-            char* cur = smem + (kt & 1) * STAGE;
-            char* nxt = smem + ((kt + 1) & 1) * STAGE;
-            const bool dma = kt + 1 < nk;
-            const long k1 = (long)(kb + kt + 1) * BK;
-            ktile<AK, BKM, DIAG>(cur, nxt, dma, tile_ptr<AK>(A, lda, i0, k1), tile_ptr<BKM>(B, ldb, j0, k1), oa, ob, g,
-                                 wl, l, acc);
-        }
+    }
+    {  // prologue: all of K-tile 0 (this wave's 8 pieces of the schedule), retired before the first read
+        const long k0 = (long)kb * BK;
+        const __bf16* a0 = tile_ptr<AK>(A, lda, i0, k0);
+        const __bf16* b0 = tile_ptr<BKM>(B, ldb, jb, k0);
+        dma_pair(a0, so.a0, smem, so.la0);
+        dma_pair(b0, so.b0, smem + OPB, so.lb0);
+        dma_pair(b0, so.b1, smem + OPB, so.lb1);
+        dma_pair(a0, so.a1, smem, so.la1);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        bar();
+    }
+    GPP_STAMP(1);
+    if (g == 1) bar();  // the stagger: group 1 runs one barrier interval behind group 0
+    for (int kt = 0; kt < nk; ++kt) {
+        char* cur = smem + (kt & 1) * STAGE;
+        char* nxt = smem + ((kt + 1) & 1) * STAGE;
+        const long k1 = (long)(kb + kt + 1) * BK;
+        ktile_spread<AK, BKM, F8>(cur, nxt, kt + 1 < nk, tile_ptr<AK>(A, lda, i0, k1), tile_ptr<BKM>(B, ldb, jb, k1),
+                                  so, g, wl, l, acc, false, kt);
     }
     GPP_STAMP(2);
-    if (g == 0 && DIAG != 4) bar();
+    if (g == 0) bar();
     // every fragment read and LDS-DMA done: the LDS is free for the epilogue.  The builtin (not inline asm)
     // tells the compiler's wait-count model that the DMA has retired; after an asm wait it still counts the
     // LDS-DMA loads as pending, a second kind of VMEM event beside the epilogue's own loads, and then waits
@@ -1074,11 +894,6 @@ gemm_pp_kernel(const __bf16* __restrict__ A, long lda, const __bf16* __restrict_
     __builtin_amdgcn_s_waitcnt(0x70);  // vmcnt(0) expcnt(7) lgkmcnt(0)
     bar();
 
-    // DIAG 6 (timing only): the epilogue's global stores are skipped (kept in the code behind a runtime test
-    // that is never true, so the MFMAs and the LDS staging stay): prices the store burst at the end of each tile
-    // DIAG 6 (timing only): the epilogue's global stores are skipped (kept in the code behind a runtime test
-    // that is never true, so the MFMAs and the LDS staging stay): prices the store burst at the end of each tile
-    const bool st_on = DIAG != 6 || ep.prio == 77;
     // accumulator (ib, jb) register r of lane l: row i = 128 g + 16 ib + (l & 15), col j = 64 wl + 16 jb + 4 (l >> 4) + r
     if constexpr (SLAB) {
         float* sp = slab + (long)split * M * N;
@@ -1090,11 +905,11 @@ gemm_pp_kernel(const __bf16* __restrict__ A, long lda, const __bf16* __restrict_
             for (int jb = 0; jb < 4; ++jb) {
                 const long i = i0 + 128 * g + 16 * ib + (l & 15);
                 const long j = j0 + 64 * wl + 16 * jb + 4 * (l >> 4);
-                if (st_on) *reinterpret_cast<f32x4*>(sp + i * N + j) = F8 != 0 ? acc[ib][jb] * osc : acc[ib][jb];
+                *reinterpret_cast<f32x4*>(sp + i * N + j) = F8 != 0 ? acc[ib][jb] * osc : acc[ib][jb];
             }
         GPP_STAMP(4);
     } else {
-        epilogue_bf16<EPI, F8, 1>(acc, smem, g, wl, l, tid, i0, j0, jb, C, ldc, beta, ep, st_on, false, blockIdx.x);
+        epilogue_bf16<EPI, F8, 1>(acc, smem, g, wl, l, tid, i0, j0, jb, C, ldc, beta, ep, false, blockIdx.x);
         GPP_STAMP(4);
     }
 #ifdef BPE_GPP_PHASE_STAMPS
@@ -1115,11 +930,10 @@ gemm_pp_kernel(const __bf16* __restrict__ A, long lda, const __bf16* __restrict_
 // LDS only); phase 2's vmcnt wait retires them.
 // (An earlier persistent form stored the accumulators from registers as 8-byte row pieces during the next tile's
 // first load section and lost to the one-tile kernel: 0.74-0.89 vs 1.0 PF/s on the K = 768 forward GEMMs.)
-template <bool AK, bool BKM, int EPI, int SPREAD, int F8 = 0>
+template <bool AK, bool BKM, int EPI, int F8 = 0>
 __global__ void __launch_bounds__(NT, 1)
 gemm_pp_persist_kernel(const __bf16* __restrict__ A, long lda, const __bf16* __restrict__ B, long ldb,
                        __bf16* __restrict__ C, long ldc, float beta, int M, int N, int R, Epi ep = Epi{}) {
-    static_assert(SPREAD != 0, "the persistent kernel runs the spread DMA schedule");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, l = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1156,10 +970,10 @@ gemm_pp_persist_kernel(const __bf16* __restrict__ A, long lda, const __bf16* __r
     {  // prologue of the first tile: all of its K-tile 0, retired before the first read
         const __bf16* a0 = tile_ptr<AK>(A, lda, i0, 0);
         const __bf16* b0 = tile_ptr<BKM>(B, ldb, jb, 0);
-        dma_pair<BPE_GPP_DMA_POL_A>(a0, so.a0, smem, so.la0);
-        dma_pair<BPE_GPP_DMA_POL_B>(b0, so.b0, smem + OPB, so.lb0);
-        dma_pair<BPE_GPP_DMA_POL_B>(b0, so.b1, smem + OPB, so.lb1);
-        dma_pair<BPE_GPP_DMA_POL_A>(a0, so.a1, smem, so.la1);
+        dma_pair(a0, so.a0, smem, so.la0);
+        dma_pair(b0, so.b0, smem + OPB, so.lb0);
+        dma_pair(b0, so.b1, smem + OPB, so.lb1);
+        dma_pair(a0, so.a1, smem, so.la1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         bar();
     }
@@ -1197,7 +1011,7 @@ gemm_pp_persist_kernel(const __bf16* __restrict__ A, long lda, const __bf16* __r
             // the next K-tile of this tile, or K-tile 0 of the next tile
             const __bf16* an = last ? tile_ptr<AK>(A, lda, i0n, 0) : tile_ptr<AK>(A, lda, i0, (long)(kt + 1) * BK);
             const __bf16* bn = last ? tile_ptr<BKM>(B, ldb, jbn, 0) : tile_ptr<BKM>(B, ldb, jb, (long)(kt + 1) * BK);
-            ktile_spread<AK, BKM, 0, SPREAD == 2, F8>(cur, nxt, !last || more, an, bn, so, g, wl, l, acc, kt == 0);
+            ktile_spread<AK, BKM, F8>(cur, nxt, !last || more, an, bn, so, g, wl, l, acc, kt == 0);
             st ^= 1;
         }
         GPP_STAMP_T(t, 2);
@@ -1209,8 +1023,8 @@ gemm_pp_persist_kernel(const __bf16* __restrict__ A, long lda, const __bf16* __r
         // staging, lane pairs swapping halves into 16-byte chunks, every g / u load issued before the first store
         // -- 0.77 vs 0.69 ms, profiles/bench/ab_swiglu_bwd_reg_epilogue_r6.log: each access instruction then covers
         // 16 rows x 2 x 32 B instead of 2 rows x 512 B.)
-        epilogue_bf16<EPI, F8, 2>(acc, smem + (st ^ 1) * STAGE, g, wl, l, tid, i0, j0, jb, C, ldc, beta, ep, true,
-                                  more, t, smem + LDS_LAUNCH, &amx);
+        epilogue_bf16<EPI, F8, 2>(acc, smem + (st ^ 1) * STAGE, g, wl, l, tid, i0, j0, jb, C, ldc, beta, ep, more,
+                                  t, smem + LDS_LAUNCH, &amx);
         GPP_STAMP_T(t, 4);
         if (!more) break;
         t = tn;
@@ -1309,18 +1123,17 @@ __global__ void __launch_bounds__(NT, 1) gemm_pp_dwg_kernel(DwGroup gp, float* _
     for (int a = 0; a < 8; ++a)
 #pragma unroll
         for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // BKM (X^T copy, B K-major): the forward GEMM's spread schedule (1); both token-major: the weight-gradient
-    // one with a DMA piece inside each MFMA section (2) -- the same choices as the single-problem routes
-    constexpr bool SPLIT = !BKM;
+    // BKM (X^T copy, B K-major): two DMA pieces per load section; both token-major: one of them inside each MFMA
+    // section (ktile_spread SPLIT) -- the same choices as the single-problem routes
     const SpreadOff so = spread_offsets<false, BKM>(g, wl, l, (int)lda, (int)ldb);
     {
         const long k0 = (long)kb * BK;
         const __bf16* a0 = tile_ptr<false>(A, lda, i0, k0);
         const __bf16* b0 = tile_ptr<BKM>(B, ldb, j0, k0);
-        dma_pair<BPE_GPP_DMA_POL_A>(a0, so.a0, smem, so.la0);
-        dma_pair<BPE_GPP_DMA_POL_B>(b0, so.b0, smem + OPB, so.lb0);
-        dma_pair<BPE_GPP_DMA_POL_B>(b0, so.b1, smem + OPB, so.lb1);
-        dma_pair<BPE_GPP_DMA_POL_A>(a0, so.a1, smem, so.la1);
+        dma_pair(a0, so.a0, smem, so.la0);
+        dma_pair(b0, so.b0, smem + OPB, so.lb0);
+        dma_pair(b0, so.b1, smem + OPB, so.lb1);
+        dma_pair(a0, so.a1, smem, so.la1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         bar();
     }
@@ -1330,8 +1143,8 @@ __global__ void __launch_bounds__(NT, 1) gemm_pp_dwg_kernel(DwGroup gp, float* _
         char* cur = smem + (kt & 1) * STAGE;
         char* nxt = smem + ((kt + 1) & 1) * STAGE;
         const long k1 = (long)(kb + kt + 1) * BK;
-        ktile_spread<false, BKM, 0, SPLIT, 0>(cur, nxt, kt + 1 < nk, tile_ptr<false>(A, lda, i0, k1),
-                                              tile_ptr<BKM>(B, ldb, j0, k1), so, g, wl, l, acc, false, kt);
+        ktile_spread<false, BKM, 0>(cur, nxt, kt + 1 < nk, tile_ptr<false>(A, lda, i0, k1),
+                                    tile_ptr<BKM>(B, ldb, j0, k1), so, g, wl, l, acc, false, kt);
     }
     GPP_STAMP(2);
     if (g == 0) bar();
@@ -1410,17 +1223,9 @@ using namespace bpe::gpp;
 // Static s_setprio 1 for the younger wave group: end to end +0.1-0.6 % (profiles/bench/ab_e2e_gpp_prio.log).
 static int prio_mode() { return 1; }
 
-// DMA schedule: 1 = the spread schedule (ktile_spread), 2 = spread with one piece per section moved into the MFMA
-// section: 2 for the weight gradient (both operands MN-major: +1-3 %), 1 for the rest (2 is 3 % slower there;
-// profiles/bench/ab_gpp_dma_split.log).  0, the burst schedule of ktile, serves the DIAG 5 build only.
-static int spread_mode(bool weight_grad = false) { return weight_grad ? 2 : 1; }
-
 // Persistent kernel (gemm_pp_persist_kernel) for the one-pass bf16 / fp8 GEMMs: 1 = on (one workgroup per CU),
 // 0 = the one-tile kernel, n >= 2 = on with at most n workgroups (tests: many tiles per workgroup on small shapes).
-#ifndef BPE_GPP_PERSIST  // build define: the default form (variant builds A/B the one-tile kernel with 0)
-#define BPE_GPP_PERSIST 1
-#endif
-static int g_persist = BPE_GPP_PERSIST;
+static int g_persist = 1;
 int gpp_persist_config(int mode) {
     const int prev = g_persist;
     if (mode >= 0) g_persist = mode;
@@ -1455,124 +1260,94 @@ static int num_cus() {
     return c;
 }
 
-// launch the persistent kernel k over ntiles tiles: one workgroup per CU
-template <typename K, typename... Args>
-static void launch_persist(K* k, int ntiles, hipStream_t s, Args... args) {
-    static_assert(sizeof...(Args) > 0, "");
-    const int cap = g_persist >= 2 ? g_persist : num_cus();  // mode >= 2: a test hook, at most `mode` workgroups
-    const int grid = ntiles < cap ? ntiles : cap;
-    k<<<grid, NT, LDS_LAUNCH, s>>>(args...);
+// Launch kernel K over `grid` workgroups with LDS_LAUNCH + `extra` bytes of dynamic LDS (more than 64 KiB: opted
+// into once per instantiation).  persist: K walks the tile list itself, so the grid is capped at one workgroup per
+// CU (g_persist >= 2: a test hook, at most that many workgroups).
+template <auto K, typename... Args>
+static void launch(bool persist, int grid, int extra, hipStream_t s, Args... args) {
+    static bool attr = false;
+    if (!attr) {
+        (void)hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LAUNCH + extra);
+        attr = true;
+    }
+    if (persist) grid = std::min(grid, g_persist >= 2 ? g_persist : num_cus());
+    K<<<grid, NT, LDS_LAUNCH + extra, s>>>(args...);
 }
 
-template <typename K>
-static void lds_attr(K* k) {  // > 64 KiB dynamic LDS must be opted into once per instantiation
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LAUNCH);
+// One-pass GEMM (no split-K) of (M / 256) x (N / 256) tiles: the persistent kernel, or under gpp_persist_config(0)
+// the one-tile kernel
+template <bool AK, bool BKM, int EPI, int F8 = 0>
+static void launch_onepass(const void* a, long lda, const void* b, long ldb, void* c, long ldc, float beta, int M,
+                           int N, int R, const Epi& ep, hipStream_t s) {
+    const int ntiles = (M / BT) * (N / BT);
+    if (g_persist)
+        launch<&gemm_pp_persist_kernel<AK, BKM, EPI, F8>>(true, ntiles, 0, s, (const __bf16*)a, lda, (const __bf16*)b,
+                                                          ldb, (__bf16*)c, ldc, beta, M, N, R, ep);
+    else
+        launch<&gemm_pp_kernel<AK, BKM, false, EPI, F8>>(false, ntiles, 0, s, (const __bf16*)a, lda, (const __bf16*)b,
+                                                         ldb, (float*)nullptr, (__bf16*)c, ldc, beta, M, N, R, 1, ep);
+}
+
+static Epi make_epi(int gm) {
+    Epi ep{};
+    ep.prio = prio_mode();
+    ep.gm = gm;
+    return ep;
 }
 
 // dgu = swiglu_bwd(dY . W2, gu): A = dY [M][R] (K-major), B = W2 [R][F] (MN-major)
 void launch_gemm_pp_swiglu_bwd(const void* dY, long ldy, const void* W2, long ldw, const void* gu, void* dgu,
                                long ldg, int M, int F, int R, hipStream_t s) {
-    static bool attr = false;
-    auto* k = &gemm_pp_kernel<true, false, false, 0, EPI_SWIGLU_BWD, 1>;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LAUNCH);
-        attr = true;
-    }
-    const int grid = (M / BT) * (F / BT);
-    Epi ep{(const __bf16*)gu, (__bf16*)dgu, ldg, F};
-    ep.prio = prio_mode();
-    ep.gm = order_for(F / BT);
-    if (g_persist) {
-        static bool pattr = false;
-        auto* kp = &gemm_pp_persist_kernel<true, false, EPI_SWIGLU_BWD, 1>;
-        if (!pattr) lds_attr(kp), pattr = true;
-        return launch_persist(kp, grid, s, (const __bf16*)dY, ldy, (const __bf16*)W2, ldw, (__bf16*)nullptr, 0L, 0.f,
-                              M, F, R, ep);
-    }
-    k<<<grid, NT, LDS_LAUNCH, s>>>((const __bf16*)dY, ldy, (const __bf16*)W2, ldw, nullptr, nullptr, 0, 0.f, M, F, R,
-                                  1, ep);
+    Epi ep = make_epi(order_for(F / BT));
+    ep.gu = (const __bf16*)gu;
+    ep.dgu = (__bf16*)dgu;
+    ep.ld = ldg;
+    ep.F = F;
+    launch_onepass<true, false, EPI_SWIGLU_BWD>(dY, ldy, W2, ldw, nullptr, 0, 0.f, M, F, R, ep, s);
 }
 
 // gu = X . [W1; W3]^T and a = silu(g) * u (EPI_SWIGLU_FWD): X [M][R], W13 [2F][R] (both K-major)
 void launch_gemm_pp_swiglu_fwd(const void* X, long ldx, const void* W13, long ldw, void* gu, long ldg, void* act,
                                long lda_, int M, int F, int R, hipStream_t s) {
-    static bool attr = false;
-    auto* k = &gemm_pp_kernel<true, true, false, 0, EPI_SWIGLU_FWD, 1>;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LAUNCH);
-        attr = true;
-    }
-    const int grid = (M / BT) * (F / (BT / 2));
-    Epi ep{nullptr, (__bf16*)gu, ldg, F, (__bf16*)act, lda_};
-    ep.prio = prio_mode();
-    ep.gm = order_for(F / (BT / 2));
-    if (g_persist) {
-        static bool pattr = false;
-        auto* kp = &gemm_pp_persist_kernel<true, true, EPI_SWIGLU_FWD, 1>;
-        if (!pattr) lds_attr(kp), pattr = true;
-        return launch_persist(kp, grid, s, (const __bf16*)X, ldx, (const __bf16*)W13, ldw, (__bf16*)nullptr, 0L, 0.f,
-                              M, 2 * F, R, ep);
-    }
-    k<<<grid, NT, LDS_LAUNCH, s>>>((const __bf16*)X, ldx, (const __bf16*)W13, ldw, nullptr, nullptr, 0, 0.f, M, 2 * F,
-                                  R, 1, ep);
+    Epi ep = make_epi(order_for(F / (BT / 2)));
+    ep.dgu = (__bf16*)gu;
+    ep.ld = ldg;
+    ep.F = F;
+    ep.act = (__bf16*)act;
+    ep.ld_act = lda_;
+    launch_onepass<true, true, EPI_SWIGLU_FWD>(X, ldx, W13, ldw, nullptr, 0, 0.f, M, 2 * F, R, ep, s);
 }
 
-// qkv = X . Wqkv^T with RoPE on columns [0, rot_cols) (EPI_ROPE): X [M][R], Wqkv [N][R] (both K-major)
-void launch_gemm_pp_rope(const void* X, long ldx, const void* W, long ldw, void* C, long ldc, int M, int N, int R,
-                         const float* cosT, const float* sinT, int S, int D, int rot_cols, hipStream_t s) {
-    Epi ep{};
-    ep.prio = prio_mode();
-    ep.gm = order_for(N / BT);
+static void set_rope(Epi& ep, const float* cosT, const float* sinT, int S, int D, int rot_cols) {
     ep.cosT = cosT;
     ep.sinT = sinT;
     ep.S = S;
     ep.D = D;
     ep.rot_cols = rot_cols;
-    const int ntiles = (M / BT) * (N / BT);
-    if (g_persist) {
-        static bool pattr = false;
-        auto* kp = &gemm_pp_persist_kernel<true, true, EPI_ROPE, 1>;
-        if (!pattr) lds_attr(kp), pattr = true;
-        return launch_persist(kp, ntiles, s, (const __bf16*)X, ldx, (const __bf16*)W, ldw, (__bf16*)C, ldc, 0.f, M,
-                              N, R, ep);
-    }
-    static bool attr = false;
-    auto* k = &gemm_pp_kernel<true, true, false, 0, EPI_ROPE, 1>;
-    if (!attr) lds_attr(k), attr = true;
-    k<<<ntiles, NT, LDS_LAUNCH, s>>>((const __bf16*)X, ldx, (const __bf16*)W, ldw, nullptr, (__bf16*)C, ldc, 0.f, M,
-                                    N, R, 1, ep);
 }
+
+// qkv = X . Wqkv^T with RoPE on columns [0, rot_cols) (EPI_ROPE): X [M][R], Wqkv [N][R] (both K-major)
+void launch_gemm_pp_rope(const void* X, long ldx, const void* W, long ldw, void* C, long ldc, int M, int N, int R,
+                         const float* cosT, const float* sinT, int S, int D, int rot_cols, hipStream_t s) {
+    Epi ep = make_epi(order_for(N / BT));
+    set_rope(ep, cosT, sinT, S, D, rot_cols);
+    launch_onepass<true, true, EPI_ROPE>(X, ldx, W, ldw, C, ldc, 0.f, M, N, R, ep, s);
+}
+
+// The fp8 launchers pass the fp8 rows as bf16 rows of half the length: R = K / 2 "bf16" elements = K / 128
+// K-tiles of 128 fp8, row strides (bytes) / 2.
 
 // C[M][N] (bf16) = (A8 . B8^T) * sa * sb with A8 [M][K], B8 [N][K] fp8 row-major (K-major), row strides in
 // bytes; fmt_a 0 = e4m3, 1 = e5m2; B is e4m3.  M, N multiples of 256, K of 128, strides of 16 bytes.
 void launch_gemm_fp8(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K,
                      int fmt_a, const float* sa, const float* sb, hipStream_t s) {
-    static bool attr1 = false, attr2 = false;
-    auto* k1 = &gemm_pp_kernel<true, true, false, 0, EPI_NONE, 1, 1>;
-    auto* k2 = &gemm_pp_kernel<true, true, false, 0, EPI_NONE, 1, 2>;
-    auto* k = fmt_a == 1 ? k2 : k1;
-    bool& attr = fmt_a == 1 ? attr2 : attr1;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LAUNCH);
-        attr = true;
-    }
-    Epi ep{};
-    ep.prio = prio_mode();
-    ep.gm = order_fp8();
+    Epi ep = make_epi(order_fp8());
     ep.sa = sa;
     ep.sb = sb;
-    // the fp8 rows as bf16 rows of half the length: R = K / 2 "bf16" elements = K / 128 K-tiles of 128 fp8
-    if (g_persist) {
-        static bool pattr1 = false, pattr2 = false;
-        auto* kp = fmt_a == 1 ? &gemm_pp_persist_kernel<true, true, EPI_NONE, 1, 2>
-                              : &gemm_pp_persist_kernel<true, true, EPI_NONE, 1, 1>;
-        bool& pa = fmt_a == 1 ? pattr2 : pattr1;
-        if (!pa) lds_attr(kp), pa = true;
-        return launch_persist(kp, (M / BT) * (N / BT), s, (const __bf16*)A, lda / 2, (const __bf16*)B, ldb / 2,
-                              (__bf16*)C, ldc, 0.f, M, N, K / 2, ep);
-    }
-    k<<<(M / BT) * (N / BT), NT, LDS_LAUNCH, s>>>((const __bf16*)A, lda / 2, (const __bf16*)B, ldb / 2, nullptr,
-                                                  (__bf16*)C, ldc, 0.f, M, N, K / 2, 1, ep);
+    if (fmt_a == 1)
+        launch_onepass<true, true, EPI_NONE, 2>(A, lda / 2, B, ldb / 2, C, ldc, 0.f, M, N, K / 2, ep, s);
+    else
+        launch_onepass<true, true, EPI_NONE, 1>(A, lda / 2, B, ldb / 2, C, ldc, 0.f, M, N, K / 2, ep, s);
 }
 
 // qkv = (X8 . Wqkv8^T) * sa * sb (e4m3 x e4m3, K-major) with RoPE on output columns [0, rot_cols) in the epilogue:
@@ -1581,28 +1356,11 @@ void launch_gemm_fp8(const void* A, long lda, const void* B, long ldb, void* C, 
 void launch_gemm_fp8_rope(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K,
                           const float* sa, const float* sb, const float* cosT, const float* sinT, int S, int D,
                           int rot_cols, hipStream_t s) {
-    Epi ep{};
-    ep.prio = prio_mode();
-    ep.gm = order_fp8();
+    Epi ep = make_epi(order_fp8());
     ep.sa = sa;
     ep.sb = sb;
-    ep.cosT = cosT;
-    ep.sinT = sinT;
-    ep.S = S;
-    ep.D = D;
-    ep.rot_cols = rot_cols;
-    if (g_persist) {
-        static bool pattr = false;
-        auto* kp = &gemm_pp_persist_kernel<true, true, EPI_ROPE, 1, 1>;
-        if (!pattr) lds_attr(kp), pattr = true;
-        return launch_persist(kp, (M / BT) * (N / BT), s, (const __bf16*)A, lda / 2, (const __bf16*)B, ldb / 2,
-                              (__bf16*)C, ldc, 0.f, M, N, K / 2, ep);
-    }
-    static bool attr = false;
-    auto* k = &gemm_pp_kernel<true, true, false, 0, EPI_ROPE, 1, 1>;
-    if (!attr) lds_attr(k), attr = true;
-    k<<<(M / BT) * (N / BT), NT, LDS_LAUNCH, s>>>((const __bf16*)A, lda / 2, (const __bf16*)B, ldb / 2, nullptr,
-                                                  (__bf16*)C, ldc, 0.f, M, N, K / 2, 1, ep);
+    set_rope(ep, cosT, sinT, S, D, rot_cols);
+    launch_onepass<true, true, EPI_ROPE, 1>(A, lda / 2, B, ldb / 2, C, ldc, 0.f, M, N, K / 2, ep, s);
 }
 
 // gu = (X8 . W13_8^T) * sa * sb (e4m3 x e4m3, K-major; W13_8 = [W1; W3] [2F][K]) with a = silu(g) u cast to e4m3
@@ -1611,10 +1369,11 @@ void launch_gemm_fp8_rope(const void* A, long lda, const void* B, long ldb, void
 void launch_gemm_fp8_swiglu(const void* A8, long lda, const void* B8, long ldb, void* gu, long ldg, void* a8,
                             void* a8t, int M, int F, int K, const float* sa, const float* sb, const float* a_scale,
                             unsigned* a_amax, hipStream_t s) {
-    Epi ep{nullptr, (__bf16*)gu, ldg, F};
-    ep.prio = prio_mode();
     // bands of 8 row blocks: the Llama fp8 W13 GEMM 1.17 vs 1.32 ms row-major (profiles/bench/fp8_gemm_orders_r6.log)
-    ep.gm = g_gm >= 0 ? g_gm : 8;
+    Epi ep = make_epi(g_gm >= 0 ? g_gm : 8);
+    ep.dgu = (__bf16*)gu;
+    ep.ld = ldg;
+    ep.F = F;
     ep.sa = sa;
     ep.sb = sb;
     ep.a8 = (uint8_t*)a8;
@@ -1622,17 +1381,9 @@ void launch_gemm_fp8_swiglu(const void* A8, long lda, const void* B8, long ldb, 
     ep.ld_a8t = M;
     ep.a_scale = a_scale;
     ep.a_amax = a_amax;
-    auto* kp = &gemm_pp_persist_kernel<true, true, EPI_SWIGLU_FWD8, 1, 1>;
-    static bool pattr = false;
-    if (!pattr) {
-        (void)hipFuncSetAttribute((const void*)kp, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LAUNCH + A8T_BYTES);
-        pattr = true;
-    }
-    const int ntiles = (M / BT) * (F / (BT / 2));
-    const int cap = g_persist >= 2 ? g_persist : num_cus();
-    kp<<<ntiles < cap ? ntiles : cap, NT, LDS_LAUNCH + A8T_BYTES, s>>>((const __bf16*)A8, lda / 2,
-                                                                       (const __bf16*)B8, ldb / 2, (__bf16*)nullptr,
-                                                                       0L, 0.f, M, 2 * F, K / 2, ep);
+    launch<&gemm_pp_persist_kernel<true, true, EPI_SWIGLU_FWD8, 1>>(
+        true, (M / BT) * (F / (BT / 2)), A8T_BYTES, s, (const __bf16*)A8, lda / 2, (const __bf16*)B8, ldb / 2,
+        (__bf16*)nullptr, 0L, 0.f, M, 2 * F, K / 2, ep);
 }
 
 // da = (G8 . W2t_8^T) * sa * sb (G8 e5m2 [M][K], W2t_8 e4m3 [F][K], both K-major) with the SwiGLU backward over gu
@@ -1641,9 +1392,10 @@ void launch_gemm_fp8_swiglu(const void* A8, long lda, const void* B8, long ldb, 
 void launch_gemm_fp8_swiglu_bwd(const void* G8, long ldg8, const void* W8, long ldw8, const void* gu, void* dgu8,
                                 void* dgu8t, int M, int F, int K, const float* sa, const float* sb,
                                 const float* d_scale, unsigned* d_amax, hipStream_t s) {
-    Epi ep{(const __bf16*)gu, nullptr, 2L * F, F};
-    ep.prio = prio_mode();
-    ep.gm = g_gm >= 0 ? g_gm : 8;
+    Epi ep = make_epi(g_gm >= 0 ? g_gm : 8);
+    ep.gu = (const __bf16*)gu;
+    ep.ld = 2L * F;
+    ep.F = F;
     ep.sa = sa;
     ep.sb = sb;
     ep.a8 = (uint8_t*)dgu8;
@@ -1651,17 +1403,9 @@ void launch_gemm_fp8_swiglu_bwd(const void* G8, long ldg8, const void* W8, long 
     ep.ld_a8t = M;
     ep.a_scale = d_scale;
     ep.a_amax = d_amax;
-    auto* kp = &gemm_pp_persist_kernel<true, true, EPI_SWIGLU_BWD8, 1, 2>;
-    static bool pattr = false;
-    if (!pattr) {
-        (void)hipFuncSetAttribute((const void*)kp, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LAUNCH + A8T_BYTES);
-        pattr = true;
-    }
-    const int ntiles = (M / BT) * (F / BT);
-    const int cap = g_persist >= 2 ? g_persist : num_cus();
-    kp<<<ntiles < cap ? ntiles : cap, NT, LDS_LAUNCH + A8T_BYTES, s>>>((const __bf16*)G8, ldg8 / 2,
-                                                                       (const __bf16*)W8, ldw8 / 2, (__bf16*)nullptr,
-                                                                       0L, 0.f, M, F, K / 2, ep);
+    launch<&gemm_pp_persist_kernel<true, true, EPI_SWIGLU_BWD8, 2>>(
+        true, (M / BT) * (F / BT), A8T_BYTES, s, (const __bf16*)G8, ldg8 / 2, (const __bf16*)W8, ldw8 / 2,
+        (__bf16*)nullptr, 0L, 0.f, M, F, K / 2, ep);
 }
 
 // C = beta * C + (A8 . B8^T) * sa * sb, split over K into `splits` fp32 partials (slab [splits][M][N]) summed in a
@@ -1669,18 +1413,18 @@ void launch_gemm_fp8_swiglu_bwd(const void* G8, long ldg8, const void* W8, long 
 void launch_gemm_fp8_splitk(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K,
                             int fmt_a, const float* sa, const float* sb, float beta, int splits, float* slab,
                             int c_f32, hipStream_t s) {
-    static bool attr1 = false, attr2 = false;
-    auto* k1 = &gemm_pp_kernel<true, true, true, 0, EPI_NONE, 1, 1>;
-    auto* k2 = &gemm_pp_kernel<true, true, true, 0, EPI_NONE, 1, 2>;
-    auto* k = fmt_a == 1 ? k2 : k1;
-    bool& attr = fmt_a == 1 ? attr2 : attr1;
-    if (!attr) lds_attr(k), attr = true;
-    Epi ep{};
-    ep.prio = prio_mode();
+    Epi ep = make_epi(0);
     ep.sa = sa;
     ep.sb = sb;
-    k<<<(M / BT) * (N / BT) * splits, NT, LDS_LAUNCH, s>>>((const __bf16*)A, lda / 2, (const __bf16*)B, ldb / 2, slab,
-                                                           nullptr, 0, 0.f, M, N, K / 2, splits, ep);
+    const int grid = (M / BT) * (N / BT) * splits;
+    if (fmt_a == 1)
+        launch<&gemm_pp_kernel<true, true, true, EPI_NONE, 2>>(false, grid, 0, s, (const __bf16*)A, lda / 2,
+                                                               (const __bf16*)B, ldb / 2, slab, (__bf16*)nullptr, 0L,
+                                                               0.f, M, N, K / 2, splits, ep);
+    else
+        launch<&gemm_pp_kernel<true, true, true, EPI_NONE, 1>>(false, grid, 0, s, (const __bf16*)A, lda / 2,
+                                                               (const __bf16*)B, ldb / 2, slab, (__bf16*)nullptr, 0L,
+                                                               0.f, M, N, K / 2, splits, ep);
     splitk_reduce(slab, C, ldc, beta, M, N, splits, c_f32, s);
 }
 
@@ -1688,49 +1432,15 @@ bool gemm_pp_shape_ok(int M, int N, int R, int splits) {
     return M % BT == 0 && N % BT == 0 && R % BK == 0 && splits >= 1 && R / BK >= splits;
 }
 
-
-template <bool AK, bool BKM, bool SLAB, int DIAG, int SPREAD>
-static void launch_pp1s(const __bf16* a, long lda, const __bf16* b, long ldb, float* slab, __bf16* c, long ldc,
-                        float beta, int M, int N, int R, int splits, hipStream_t s) {
-    static bool attr = false;  // > 64 KiB dynamic LDS must be opted into once per instantiation
-    auto* k = &gemm_pp_kernel<AK, BKM, SLAB, DIAG, EPI_NONE, SPREAD>;
-    if (!attr) {
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LAUNCH);
-        attr = true;
-    }
-    const int grid = (M / BT) * (N / BT) * splits;
-    Epi ep{};
-    ep.prio = prio_mode();
-    ep.gm = SLAB ? (g_gm >= 0 ? g_gm : 0) : order_for(N / BT);
-    if constexpr (!SLAB && DIAG == 0 && SPREAD != 0) {
-        if (g_persist) {
-            static bool pattr = false;
-            auto* kp = &gemm_pp_persist_kernel<AK, BKM, EPI_NONE, SPREAD>;
-            if (!pattr) lds_attr(kp), pattr = true;
-            return launch_persist(kp, grid, s, a, lda, b, ldb, c, ldc, beta, M, N, R, ep);
-        }
-    }
-    k<<<grid, NT, LDS_LAUNCH, s>>>(a, lda, b, ldb, slab, c, ldc, beta, M, N, R, splits, ep);
-}
-
-template <bool AK, bool BKM, bool SLAB, int DIAG>
-static void launch_pp1(const __bf16* a, long lda, const __bf16* b, long ldb, float* slab, __bf16* c, long ldc,
-                      float beta, int M, int N, int R, int splits, hipStream_t s) {
-    const int sm = DIAG == 5 ? 0 : spread_mode(!AK && !BKM);
-    if (sm == 2) return launch_pp1s<AK, BKM, SLAB, DIAG, 2>(a, lda, b, ldb, slab, c, ldc, beta, M, N, R, splits, s);
-    if (sm == 1) return launch_pp1s<AK, BKM, SLAB, DIAG, 1>(a, lda, b, ldb, slab, c, ldc, beta, M, N, R, splits, s);
-    launch_pp1s<AK, BKM, SLAB, DIAG, 0>(a, lda, b, ldb, slab, c, ldc, beta, M, N, R, splits, s);
-}
-
-// BPE_GPP_DIAG (a build define, ``python -m bpe_transformer.ops.build --variant diag -D BPE_GPP_DIAG=<n>``): the
-// timing diagnostics of ktile / ktile_spread (numerically wrong) in an A/B copy of the library
-#ifndef BPE_GPP_DIAG
-#define BPE_GPP_DIAG 0
-#endif
-template <bool AK, bool BKM, bool SLAB>
+// The plain bf16 GEMM of one layout pair: split-K partials into the slab (the caller reduces them), or one pass
+template <bool AK, bool BKM>
 static void launch_pp(const __bf16* a, long lda, const __bf16* b, long ldb, float* slab, __bf16* c, long ldc,
                       float beta, int M, int N, int R, int splits, hipStream_t s) {
-    launch_pp1<AK, BKM, SLAB, BPE_GPP_DIAG>(a, lda, b, ldb, slab, c, ldc, beta, M, N, R, splits, s);
+    if (slab != nullptr)
+        launch<&gemm_pp_kernel<AK, BKM, true>>(false, (M / BT) * (N / BT) * splits, 0, s, a, lda, b, ldb, slab, c, ldc,
+                                               beta, M, N, R, splits, make_epi(g_gm >= 0 ? g_gm : 0));
+    else
+        launch_onepass<AK, BKM, EPI_NONE>(a, lda, b, ldb, c, ldc, beta, M, N, R, make_epi(order_for(N / BT)), s);
 }
 
 // Grouped weight gradients (gemm_pp_dwg_kernel, then dwg_reduce_kernel): np <= 4 problems C_p[M_p][N_p] =
@@ -1764,17 +1474,10 @@ void launch_gemm_pp_dw_group(int np, const void* const* A, const long* lda, cons
     gp.R = R;
     gp.prio = prio_mode();
     o.beta = beta;
-    if (b_kmajor) {
-        static bool attr = false;
-        auto* k = &gemm_pp_dwg_kernel<true>;
-        if (!attr) lds_attr(k), attr = true;
-        k<<<tiles * splits, NT, LDS_LAUNCH, s>>>(gp, slab);
-    } else {
-        static bool attr = false;
-        auto* k = &gemm_pp_dwg_kernel<false>;
-        if (!attr) lds_attr(k), attr = true;
-        k<<<tiles * splits, NT, LDS_LAUNCH, s>>>(gp, slab);
-    }
+    if (b_kmajor)
+        launch<&gemm_pp_dwg_kernel<true>>(false, tiles * splits, 0, s, gp, slab);
+    else
+        launch<&gemm_pp_dwg_kernel<false>>(false, tiles * splits, 0, s, gp, slab);
     const int g = (int)std::min<long>((e4 + 255) / 256, 2048);
     if (c_f32)
         dwg_reduce_kernel<float><<<g, 256, 0, s>>>(slab, o);
@@ -1787,16 +1490,12 @@ void launch_gemm_pp(int a_kmajor, int b_kmajor, const void* A, long lda, const v
     const __bf16* a = (const __bf16*)A;
     const __bf16* b = (const __bf16*)B;
     __bf16* c = (__bf16*)C;
-#define L(AK, BKM, SL) launch_pp<AK, BKM, SL>(a, lda, b, ldb, slab, c, ldc, beta, M, N, R, splits, s)
-    if (slab != nullptr) {  // splits > 1, or an fp32 C: fp32 partials, then the ordered reduce
-        if (a_kmajor) { if (b_kmajor) L(true, true, true); else L(true, false, true); }
-        else { if (b_kmajor) L(false, true, true); else L(false, false, true); }
-        splitk_reduce(slab, C, ldc, beta, M, N, splits, c_f32, s);
-    } else {
-        if (a_kmajor) { if (b_kmajor) L(true, true, false); else L(true, false, false); }
-        else { if (b_kmajor) L(false, true, false); else L(false, false, false); }
-    }
+#define L(AK, BKM) launch_pp<AK, BKM>(a, lda, b, ldb, slab, c, ldc, beta, M, N, R, splits, s)
+    if (a_kmajor) { if (b_kmajor) L(true, true); else L(true, false); }
+    else { if (b_kmajor) L(false, true); else L(false, false); }
 #undef L
+    // splits > 1, or an fp32 C: the kernel wrote fp32 partials; the ordered reduce
+    if (slab != nullptr) splitk_reduce(slab, C, ldc, beta, M, N, splits, c_f32, s);
 }
 
 // copy the last gemm_pp launch's stamps out (BPE_GPP_STAMPS builds; false otherwise)

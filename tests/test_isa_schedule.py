@@ -46,9 +46,9 @@ def _kernels(src: str):
 def test_one_quadrant_per_section(gemm_pp_asm):
     seen_f8 = seen_bf16 = 0
     for name, sec in _kernels(gemm_pp_asm):
-        # template <AK, BKM, SLAB, DIAG, EPI, SPREAD, F8>: the seventh argument is F8
+        # template <AK, BKM, SLAB, EPI, F8>: the fifth argument is F8
         targs = re.findall(r"L[bi](\d+)E", name[name.index("gemm_pp_kernelI"):name.index("EEv")])
-        f8 = int(targs[6])
+        f8 = int(targs[4])
         limit = 8 if f8 else 16
         assert max(sec) <= limit, (name[:80], sec)
         assert sum(sec) % limit == 0, (name[:80], sec)

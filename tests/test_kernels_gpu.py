@@ -531,7 +531,7 @@ def test_gemm_swiglu_bwd(gpu_device, gpp_mode):
 
 def test_gemm_swiglu_bwd_bitwise_on_exact_products(gpu_device, gpp_mode):
     """Small-integer dY and W2 make da = dY W2 exact (and exact in bf16), so the fused epilogue (packed two-element
-    fp32 arithmetic, BPE_GPP_PK=1) must give bitwise the unfused ``swiglu_bwd`` of that da on the same gu."""
+    fp32 arithmetic) must give bitwise the unfused ``swiglu_bwd`` of that da on the same gu."""
     torch.manual_seed(6)
     M, d, F = 512, 192, 768
     dy = torch.randint(-2, 3, (M, d), device=gpu_device).to(torch.bfloat16)

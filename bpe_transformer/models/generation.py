@@ -167,11 +167,21 @@ class KVCache:
         return 2 * self.k.numel() * self.k.element_size()
 
 
-def _sample(logits: Tensor, temperature: float, top_p: float | None, generator) -> Tensor:
-    """Next token per row of ``logits [B, V]`` (greedy when ``temperature <= 0``); returns ``[B]`` int64."""
+def _top_k_logits(logits: Tensor, top_k: int | None) -> Tensor:
+    """``logits`` with everything outside each row's ``top_k`` largest set to ``-inf`` (``None`` / 0 / >= V: as is)."""
+    if not top_k or top_k >= logits.shape[-1]:
+        return logits
+    idx = logits.topk(int(top_k), dim=-1).indices
+    return torch.full_like(logits, -math.inf).scatter_(-1, idx, logits.gather(-1, idx))
+
+
+def _sample(logits: Tensor, temperature: float, top_p: float | None, generator, top_k: int | None = None) -> Tensor:
+    """Next token per row of ``logits [B, V]`` (greedy when ``temperature <= 0``); returns ``[B]`` int64.  ``top_k``
+    is applied before ``top_p``."""
     logits = logits.float()
     if temperature <= 0:
         return logits.argmax(-1)
+    logits = _top_k_logits(logits, top_k)
     probs = torch.softmax(logits / temperature, dim=-1)
     if top_p is not None and top_p < 1.0:
         sp, si = probs.sort(dim=-1, descending=True)
@@ -225,6 +235,7 @@ class DecodeSession:
         self._step = torch.ones(batch, device=self.device, dtype=torch.int32) if ragged and self.fast else None
         self._step_host = [1] * batch  # what _step holds
         self._graph = None
+        self._samp = None  # the device sampler's buffers and graph (_sampler_state)
         if self.fast:
             self._prepare_weights()
 
@@ -373,20 +384,36 @@ class DecodeSession:
 
     @torch.no_grad()
     def generate(self, prompt, max_new_tokens: int, temperature: float = 1.0, top_p: float | None = None,
-                 eos_token_id: int | None = None, generator: torch.Generator | None = None):
+                 eos_token_id: int | None = None, generator: torch.Generator | None = None,
+                 top_k: int | None = None, sampler: str = "host", seed: int | None = None, sync_every: int = 16):
         """``prompt [B, S]`` -> ``[B, S + n]`` (stops early once every row emitted ``eos_token_id``).
 
         Ragged sessions also take a list of ``B`` 1-D prompts of different lengths and return a list of 1-D tensors:
         each prompt plus its continuation, ending with the first ``eos_token_id`` if one was emitted.  A sequence
-        that has emitted EOS becomes inactive; the loop ends when all are done or at ``max_new_tokens``."""
+        that has emitted EOS becomes inactive; the loop ends when all are done or at ``max_new_tokens``.
+
+        ``top_k`` keeps the ``top_k`` most likely tokens (applied before ``top_p``; ``None``: off).
+
+        ``sampler="host"`` (default) samples in PyTorch from ``generator`` and looks at every token on the host.
+        ``sampler="device"`` samples with ``ops.sample_step`` (``ops/sampling.py`` states the function), on the fast
+        path inside a second captured graph -- decode step -> ``sample_step`` -> ``rng[1] += 1`` -- that writes the
+        next token straight into its own input; EOS and the ragged active mask are handled on the device, and the
+        host only reads the ``done`` flags every ``sync_every`` tokens (never, without ``eos_token_id``).  Its random
+        stream is Philox keyed by ``seed`` at counter (token index, row); ``seed=None`` draws one from ``generator``
+        (else from torch's default generator), which is all ``generator`` is used for in this mode.  The results have
+        the shapes of the host sampler's; ``prompt + max_new_tokens <= max_len`` is checked once, up front."""
+        assert sampler in ("host", "device"), "sampler: 'host' or 'device'"
+        if sampler == "device":
+            return self._generate_device(prompt, max_new_tokens, temperature, top_k, top_p, eos_token_id, generator,
+                                         seed, sync_every)
         if isinstance(prompt, (list, tuple)):
-            return self._generate_ragged(prompt, max_new_tokens, temperature, top_p, eos_token_id, generator)
+            return self._generate_ragged(prompt, max_new_tokens, temperature, top_p, eos_token_id, generator, top_k)
         self.reset()
         logits = self.prefill(prompt)
         outs = [prompt.to(self.device)]
         done = None
         for i in range(max_new_tokens):
-            nxt = _sample(logits, temperature, top_p, generator)
+            nxt = _sample(logits, temperature, top_p, generator, top_k)
             outs.append(nxt[:, None])
             if eos_token_id is not None:
                 hit = nxt == eos_token_id
@@ -397,7 +424,8 @@ class DecodeSession:
                 logits = self.decode(nxt)
         return torch.cat(outs, 1)
 
-    def _generate_ragged(self, prompts, max_new_tokens, temperature, top_p, eos_token_id, generator) -> list[Tensor]:
+    def _pad_prompts(self, prompts):
+        """A list of 1-D prompts -> (the prompts on the device, their lengths, right-padded ``ids [B, max]``)."""
         assert self.ragged, "a list of prompts needs DecodeSession(..., ragged=True)"
         B = self.batch
         assert len(prompts) == B, f"session batch is {B}, got {len(prompts)} prompts"
@@ -407,12 +435,18 @@ class DecodeSession:
         ids = torch.zeros(B, max(n), dtype=torch.long, device=self.device)  # right-padded (the pad id is never seen)
         for b, p in enumerate(prompts):
             ids[b, : n[b]] = p
+        return prompts, n, ids
+
+    def _generate_ragged(self, prompts, max_new_tokens, temperature, top_p, eos_token_id, generator,
+                         top_k=None) -> list[Tensor]:
+        B = self.batch
+        prompts, n, ids = self._pad_prompts(prompts)
         self.reset()
         logits = self.prefill(ids, n)
         new: list[list[int]] = [[] for _ in range(B)]
         done = [False] * B
         for i in range(max_new_tokens):
-            nxt = _sample(logits, temperature, top_p, generator)
+            nxt = _sample(logits, temperature, top_p, generator, top_k)
             for b, tok in enumerate(nxt.tolist()):
                 if not done[b]:
                     new[b].append(tok)
@@ -424,6 +458,133 @@ class DecodeSession:
                 if any(done):  # an inactive row's logits are unspecified: keep the sampler's input finite
                     logits[[b for b in range(B) if done[b]]] = 0.0
         return [torch.cat([p, torch.tensor(t, dtype=p.dtype, device=self.device)]) for p, t in zip(prompts, new)]
+
+    # ------------------------------------------------------------------ device sampler
+    def _sampler_state(self, temperature: float, top_k: int, top_p: float, eos: int):
+        """The device sampler's static buffers -- ``ids [B, 1]`` (the next token: the step's input), ``out
+        [B, max_len]`` (token ``i`` of the continuation in column ``i``), ``done [B]``, ``rng = (seed, count)`` --
+        and, with ``use_graph``, the graph of one decode step + ``sample_step`` + ``rng[1] += 1`` for these sampling
+        parameters (they are baked into the graph: other parameters capture it again).  Captured like ``_capture``:
+        one stream, so no parallel branches; the warm-up run's writes are all re-initialised by the caller."""
+        from ..ops import sampling
+
+        st = self._samp
+        if st is None:
+            B, dev = self.batch, self.device
+            st = self._samp = {
+                "ids": torch.zeros(B, 1, dtype=torch.long, device=dev),
+                "out": torch.full((B, self.max_len), -1, dtype=torch.long, device=dev),
+                "done": torch.zeros(B, dtype=torch.int32, device=dev),
+                "rng": torch.zeros(2, dtype=torch.long, device=dev),
+                # a ragged session off the fast path has no static step: the sampler's own
+                "step": self._step if self._step is not None else (
+                    torch.ones(B, dtype=torch.int32, device=dev) if self.ragged else None),
+                "graph": None, "key": None,
+            }
+        key = (float(temperature), top_k, top_p, eos)
+        st["params"] = key
+        if self.use_graph and st["key"] != key:
+            def run():
+                logits = self._forward_fast(st["ids"], prefill=False, step=self._step)
+                sampling.sample_step(logits, *key[:3], st["rng"], st["ids"], st["out"], st["step"], st["done"], eos)
+                st["rng"][1:].add_(1)
+
+            pos0 = self.cache.pos.clone()
+            s = torch.cuda.Stream(device=self.device)
+            s.wait_stream(torch.cuda.current_stream(self.device))
+            with torch.cuda.stream(s):
+                run()
+            torch.cuda.current_stream(self.device).wait_stream(s)
+            self.cache.pos.copy_(pos0)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                run()
+            self.cache.pos.copy_(pos0)
+            st["graph"], st["key"] = g, key
+        return st
+
+    def _device_step(self, st) -> None:
+        """Decode the token in ``st["ids"]`` and sample the next one into it: one replay on the fast path."""
+        from ..ops import sampling
+
+        if self.use_graph:
+            st["graph"].replay()
+            return
+        step = st["step"]
+        if self.fast:
+            logits = self._forward_fast(st["ids"], prefill=False, step=self._step)
+        else:  # the oracle math reads host lengths: the step comes back per token (no graph to keep fed here)
+            rows = list(range(self.batch))
+            n = [1] * self.batch if step is None else [int(x) for x in step.tolist()]
+            logits = self._forward_reference(st["ids"], n, rows)
+            self.cache.advance(rows, n)
+        temperature, top_k, top_p, eos = st["params"]
+        sampling.sample_step(logits, temperature, top_k, top_p, st["rng"], st["ids"], st["out"], step, st["done"], eos)
+        st["rng"][1:].add_(1)
+
+    def _generate_device(self, prompt, max_new_tokens, temperature, top_k, top_p, eos_token_id, generator, seed,
+                         sync_every):
+        from ..ops import sampling
+
+        B = self.batch
+        as_list = isinstance(prompt, (list, tuple))
+        if as_list:
+            prompts, n, ids = self._pad_prompts(prompt)
+        else:
+            ids = prompt.to(self.device)
+            n = [ids.shape[1]] * B
+        assert sync_every >= 1, "sync_every: a positive number of tokens"
+        assert max(n) + max_new_tokens <= self.max_len, "KV cache full: prompt + max_new_tokens exceeds max_len"
+        if max_new_tokens <= 0:
+            return prompts if as_list else ids
+        if seed is None:
+            gdev = generator.device if generator is not None else "cpu"
+            seed = int(torch.randint(0, 2**62, (1,), generator=generator, device=gdev))
+        eos = -1 if eos_token_id is None else int(eos_token_id)
+        top_k = int(top_k or 0)
+        top_p = 1.0 if top_p is None else float(top_p)
+        # A tensor prompt's finished rows keep generating until every row has finished, as with the host sampler, so
+        # their tokens are needed: no EOS for the kernel there, and `done` is read off `out` at each sync instead.
+        self.reset()
+        st = self._sampler_state(temperature, top_k, top_p, eos if as_list else -1)
+        st["rng"].copy_(torch.tensor([seed, 0], dtype=torch.long))
+        st["out"].fill_(-1)
+        st["done"].zero_()
+        step = st["step"]
+        if step is not None:
+            step.fill_(1)
+            self._step_host = [1] * B
+        logits = self.prefill(ids, n if as_list else None)
+        sampling.sample_step(logits, temperature, top_k, top_p, st["rng"], st["ids"], st["out"], step, st["done"],
+                             st["params"][3])
+        st["rng"][1:].add_(1)
+        made = 1  # tokens sampled per row
+        while made < max_new_tokens:
+            if eos >= 0 and made % sync_every == 0:  # the only host sync of the loop
+                done = st["done"] != 0 if as_list else (st["out"][:, :made] == eos).any(1)
+                if bool(done.all()):
+                    break
+            self._device_step(st)
+            made += 1
+        out = st["out"][:, :made].cpu()
+        hit = out == eos if eos >= 0 else torch.zeros_like(out, dtype=torch.bool)
+        first = torch.where(hit.any(1), hit.int().argmax(1), torch.full((B,), made)).tolist()  # first EOS, or `made`
+        c = self.cache
+        if as_list:
+            # row b was fed first[b] of its tokens (its EOS is not fed; a row that never finished, all but the last);
+            # pos[b] already says so on the device: rebuild the host mirrors
+            for b in range(B):
+                c._len[b] = n[b] + min(first[b], made - 1)
+            if self._step is not None:
+                self._step_host = [int(f >= made) for f in first]
+            return [torch.cat([p, out[b, : min(first[b] + 1, made)].to(self.device, p.dtype)])
+                    for b, p in enumerate(prompts)]
+        # tensor prompt: keep the steps up to the one at which every row had emitted EOS; the replays past it (up to
+        # sync_every - 1) are dropped, from the cache too
+        keep = min(max(first) + 1, made)
+        c.pos.fill_(n[0] + keep - 1)
+        c._len[:] = [n[0] + keep - 1] * B
+        return torch.cat([ids, out[:, :keep].to(self.device, ids.dtype)], 1)
 
     # ------------------------------------------------------------------ HIP path
     def _capture(self) -> None:

@@ -184,8 +184,11 @@ class TransformerLM(nn.Module):
         eos_token_id: int | None = None,
         generator: torch.Generator | None = None,
         use_cache: bool = True,
+        top_k: int | None = None,
+        sampler: str = "host",
+        seed: int | None = None,
     ) -> Tensor:
-        """Autoregressive sampling (temperature + nucleus).  ``prompt``: ``[S]`` or ``[B, S]``.
+        """Autoregressive sampling (temperature, top-k, nucleus).  ``prompt``: ``[S]`` or ``[B, S]``.
 
         With ``use_cache`` (and prompt + new tokens within ``context_length``) decoding runs through a KV-cache
         :class:`~bpe_transformer.models.generation.DecodeSession` (HIP-graph-captured decode step on the GPU);
@@ -194,7 +197,14 @@ class TransformerLM(nn.Module):
         A list of 1-D prompts of different lengths is served as one ragged batch (every sequence at its own cache
         position) and returns a list of 1-D tensors, each its prompt plus its continuation up to and including its
         first ``eos_token_id``.
+
+        ``top_k`` keeps the ``top_k`` most likely tokens and is applied before ``top_p``.  ``sampler="device"`` samples
+        inside the captured decode graph, from a Philox stream keyed by ``seed`` (``None``: drawn from ``generator``,
+        which is otherwise unused in this mode), and syncs with the host every few tokens instead of every token
+        (:meth:`DecodeSession.generate`); it needs the KV-cache path.
         """
+        assert sampler in ("host", "device"), "sampler: 'host' or 'device'"
+        kw = dict(top_k=top_k, sampler=sampler, seed=seed)
         if isinstance(prompt, (list, tuple)):
             self._fence(self)
             longest = max(int(p.numel()) for p in prompt)
@@ -202,10 +212,10 @@ class TransformerLM(nn.Module):
                 from .generation import DecodeSession
 
                 sess = DecodeSession(self, len(prompt), max_len=longest + max_new_tokens, ragged=True)
-                return sess.generate(list(prompt), max_new_tokens, temperature, top_p, eos_token_id, generator)
+                return sess.generate(list(prompt), max_new_tokens, temperature, top_p, eos_token_id, generator, **kw)
             # without the cache: one sequence at a time through the loop below (which stops at its EOS)
-            return [self.generate(p.reshape(-1), max_new_tokens, temperature, top_p, eos_token_id, generator, use_cache)
-                    for p in prompt]
+            return [self.generate(p.reshape(-1), max_new_tokens, temperature, top_p, eos_token_id, generator, use_cache,
+                                  **kw) for p in prompt]
         squeeze = prompt.dim() == 1
         ids = prompt.unsqueeze(0) if squeeze else prompt
         self._fence(self)  # the decode session packs / reads every weight up front
@@ -213,8 +223,10 @@ class TransformerLM(nn.Module):
             from .generation import DecodeSession
 
             sess = DecodeSession(self, ids.shape[0], max_len=ids.shape[1] + max_new_tokens)
-            out = sess.generate(ids, max_new_tokens, temperature, top_p, eos_token_id, generator)
+            out = sess.generate(ids, max_new_tokens, temperature, top_p, eos_token_id, generator, **kw)
             return out[0] if squeeze else out
+        assert sampler == "host" or max_new_tokens <= 0, "sampler='device' needs the KV-cache path (use_cache, and " \
+            "prompt + max_new_tokens within context_length)"
         for _ in range(max_new_tokens):
             ctx = ids[:, -self.context_length :]
             # (sampling is not document-masked: hidden_states takes explicit bounds only, never doc_mask_token)
@@ -222,6 +234,10 @@ class TransformerLM(nn.Module):
             if temperature <= 0:
                 nxt = logits.argmax(-1, keepdim=True)
             else:
+                if top_k:
+                    from .generation import _top_k_logits
+
+                    logits = _top_k_logits(logits, top_k)
                 probs = torch.softmax(logits / temperature, dim=-1)
                 if top_p is not None and top_p < 1.0:
                     sp, si = probs.sort(dim=-1, descending=True)

@@ -18,6 +18,7 @@ from .loss import IGNORE_INDEX, cross_entropy, lm_head_cross_entropy
 from .norm import rmsnorm
 from .optim import clip_grad_norm_, fused_adamw_step, grad_norm
 from .rope import apply_rope
+from .sampling import philox_uniform, sample_logits, sample_step
 from .softmax import softmax
 
 __all__ = [
@@ -39,8 +40,11 @@ __all__ = [
     "library_path",
     "lm_head_cross_entropy",
     "load",
+    "philox_uniform",
     "prefill_attention",
     "rmsnorm",
+    "sample_logits",
+    "sample_step",
     "scaled_dot_product_attention",
     "silu",
     "softmax",

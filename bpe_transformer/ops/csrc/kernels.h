@@ -190,6 +190,31 @@ size_t gemv_lds_bytes(int M, int K);
 bool gemv_ok(int M, int K);
 void launch_gemv(const GemvArgs& a, int epi, hipStream_t s);
 
+// sample.hip (token sampling, one workgroup per logits row [B][V], row stride V).  Either `u` (given uniforms [B])
+// or `rng` (device (seed, count): Philox in the kernel) is set; neither = u 0.5.  `res` [B] takes the tokens
+// (sample_logits); with `ids` set the in-graph epilogue runs instead (sample_step): ids[b] = token,
+// out[b][count] = token, or -1 for a row that is done or whose step is 0, and on `eos` done[b] = 1, step[b] = 0.
+constexpr int SAMPLE_MAX_TILES = 2048;  // 64 x 16-byte vectors each: V <= SAMPLE_MAX_V for both types
+constexpr int SAMPLE_MAX_V = SAMPLE_MAX_TILES * 256 - 8;
+struct SampleArgs {
+    const void* logits;
+    int V;
+    float temperature;  // <= 0: greedy
+    int top_k;          // 0: off
+    double top_p;       // >= 1: off
+    const float* u;
+    const long long* rng;
+    long long* res;
+    long long* ids;
+    long long* out;
+    long out_ld;
+    int out_n;
+    int* step;  // optional (ragged sessions)
+    int* done;
+    int eos;    // < 0: none
+};
+void launch_sample(const SampleArgs& a, int dtype, int B, hipStream_t s);
+
 size_t fa_fwd_lds_bytes(int D);
 size_t fa_bwd_lds_bytes(int D);
 void launch_fa_fwd(const FaArgs& a, hipStream_t s);

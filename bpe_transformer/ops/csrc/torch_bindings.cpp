@@ -1257,9 +1257,72 @@ std::tuple<at::Tensor, at::Tensor> decode_qkv(const at::Tensor& x, const c10::op
     return {q, xsum};
 }
 
+// ---------------------------------------------------------------- token sampling (sample.hip)
+SampleArgs sample_setup(const at::Tensor& logits, double temperature, int64_t top_k, double top_p) {
+    check_cuda(logits, "logits");
+    TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(), "sample: logits must be contiguous [B, V]");
+    TORCH_CHECK(logits.size(1) >= 1 && logits.size(1) <= SAMPLE_MAX_V, "sample: 1 <= V <= ", SAMPLE_MAX_V);
+    TORCH_CHECK(top_k >= 0, "sample: top_k must be >= 0 (0 = off)");
+    SampleArgs a{};
+    a.logits = logits.data_ptr();
+    a.V = (int)logits.size(1);
+    a.temperature = (float)temperature;
+    a.top_k = (int)std::min<int64_t>(top_k, logits.size(1));
+    a.top_p = top_p;
+    a.eos = -1;
+    return a;
+}
+
+// the stateless core: one token per row for the given uniforms
+at::Tensor sample_logits(const at::Tensor& logits, double temperature, int64_t top_k, double top_p,
+                         const at::Tensor& u) {
+    SampleArgs a = sample_setup(logits, temperature, top_k, top_p);
+    const int64_t B = logits.size(0);
+    TORCH_CHECK(u.is_cuda() && u.scalar_type() == at::kFloat && u.is_contiguous() && u.numel() == B,
+                "sample_logits: u must be a contiguous fp32 GPU tensor [B]");
+    DevGuard g(logits.device());
+    auto res = at::empty({B}, logits.options().dtype(at::kLong));
+    a.u = u.data_ptr<float>();
+    a.res = (long long*)res.data_ptr<int64_t>();
+    launch_sample(a, dt_code(logits), (int)B, cur_stream());
+    return res;
+}
+
+// the in-graph form: the uniform from rng = (seed, count), the token into ids / out[:, count], EOS into done / step
+void sample_step(const at::Tensor& logits, double temperature, int64_t top_k, double top_p, const at::Tensor& rng,
+                 at::Tensor ids, at::Tensor out, const c10::optional<at::Tensor>& step, at::Tensor done, int64_t eos) {
+    SampleArgs a = sample_setup(logits, temperature, top_k, top_p);
+    const int64_t B = logits.size(0);
+    TORCH_CHECK(rng.is_cuda() && rng.scalar_type() == at::kLong && rng.is_contiguous() && rng.numel() == 2,
+                "sample_step: rng must be a contiguous int64 GPU tensor (seed, count)");
+    TORCH_CHECK(ids.is_cuda() && ids.scalar_type() == at::kLong && ids.is_contiguous() && ids.numel() == B,
+                "sample_step: ids must be a contiguous int64 GPU tensor [B, 1]");
+    TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kLong && out.dim() == 2 && out.size(0) == B &&
+                    (out.size(1) <= 1 || out.stride(1) == 1), "sample_step: out must be int64 [B, N], rows dense");
+    TORCH_CHECK(done.is_cuda() && done.scalar_type() == at::kInt && done.is_contiguous() && done.numel() == B,
+                "sample_step: done must be a contiguous int32 GPU tensor [B]");
+    if (step.has_value())
+        TORCH_CHECK(step->is_cuda() && step->scalar_type() == at::kInt && step->is_contiguous() && step->numel() == B,
+                    "sample_step: step must be a contiguous int32 GPU tensor [B]");
+    TORCH_CHECK(eos < logits.size(1), "sample_step: eos outside the vocabulary");
+    DevGuard g(logits.device());
+    a.rng = (const long long*)rng.data_ptr<int64_t>();
+    a.ids = (long long*)ids.data_ptr<int64_t>();
+    a.out = (long long*)out.data_ptr<int64_t>();
+    a.out_ld = out.stride(0);
+    a.out_n = (int)out.size(1);
+    a.step = step.has_value() ? step->data_ptr<int>() : nullptr;
+    a.done = done.data_ptr<int>();
+    a.eos = eos < 0 ? -1 : (int)eos;
+    launch_sample(a, dt_code(logits), (int)B, cur_stream());
+}
+
 }  // namespace
 
 TORCH_LIBRARY(bpe_hip, m) {
+    m.def("sample_logits(Tensor logits, float temperature, int top_k, float top_p, Tensor u) -> Tensor");
+    m.def("sample_step(Tensor logits, float temperature, int top_k, float top_p, Tensor rng, Tensor(a!) ids, "
+          "Tensor(b!) out, Tensor(c!)? step, Tensor(d!) done, int eos) -> ()");
     m.def("decode_gemv(Tensor x, Tensor? xd, Tensor? ln, float eps, Tensor w, int epi) -> (Tensor, Tensor)");
     m.def("decode_qkv(Tensor x, Tensor? xd, Tensor? ln, float eps, Tensor w, Tensor(a!) k_cache, "
           "Tensor(b!) v_cache, Tensor cos, Tensor sin, Tensor pos, int H, bool rope) -> (Tensor, Tensor)");
@@ -1383,4 +1446,6 @@ TORCH_LIBRARY_IMPL(bpe_hip, CUDA, m) {
     m.impl("decode_gemv", &decode_gemv);
     m.impl("decode_qkv", &decode_qkv);
     m.impl("decode_attn_proj", &decode_attn_proj);
+    m.impl("sample_logits", &sample_logits);
+    m.impl("sample_step", &sample_step);
 }

@@ -58,23 +58,12 @@ __device__ __forceinline__ float wave_max(float v) {
 // ---- streaming (non-temporal) vector access ---------------------------------
 // Activations that a memory-bound kernel reads or writes exactly once (hundreds of MB per tensor, never cached
 // usefully) go through these: the nt hint keeps them from displacing reusable lines.  Measured on the
-// softmax-CE kernel: 5.1 -> 5.5 TB/s (docs/performance.md).  -DBPE_STREAM_NT=0 builds the plain form (A/B).
-#ifndef BPE_STREAM_NT
-#define BPE_STREAM_NT 1
-#endif
+// softmax-CE kernel: 5.1 -> 5.5 TB/s (docs/performance.md).
 template <typename V> __device__ __forceinline__ V ld_stream(const V* p) {
-#if BPE_STREAM_NT
     return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
 }
 template <typename V> __device__ __forceinline__ void st_stream(V* p, V v) {
-#if BPE_STREAM_NT
     __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
 }
 
 // ---- typed 16-byte vector load/store, converting to/from fp32 -------------

@@ -175,16 +175,9 @@ __device__ __forceinline__ void dma_tile64_buf(const __bf16* base, int nbytes, c
 // of index math (integer divisions by the grid's shape) and address set-up before the first load can issue --
 // got the leftover slots.  Stamps (profiles/attention_stamps_r5.md): the 16-row dQ kernel's last wave issued its
 // prologue loads ~6.4 k cycles after entry, its rows arrived 1.6 k later.  The prologue runs at s_setprio 3 and the
-// loop at 0 (BPE_FA_PRIO=0 builds the old form for A/B).
-#ifndef BPE_FA_PRIO
-#define BPE_FA_PRIO 1
-#endif
-__device__ __forceinline__ void prologue_prio_begin() {
-    if (BPE_FA_PRIO) __builtin_amdgcn_s_setprio(3);
-}
-__device__ __forceinline__ void prologue_prio_end() {
-    if (BPE_FA_PRIO) __builtin_amdgcn_s_setprio(0);
-}
+// loop at 0.
+__device__ __forceinline__ void prologue_prio_begin() { __builtin_amdgcn_s_setprio(3); }
+__device__ __forceinline__ void prologue_prio_end() { __builtin_amdgcn_s_setprio(0); }
 
 // (Measured and dropped, round 5: pinning the prologue's Q rows / LSE before the barrier with an empty asm use --
 // hipcc otherwise sinks those loads into the loop preheader, after the barrier -- together with float-reciprocal

@@ -524,10 +524,7 @@ __global__ void __launch_bounds__(256) update_scales_kernel(unsigned* __restrict
 
 using namespace bpe;
 
-// 1: the 128 x 128 tile kernels where the shape allows (a variant build with 0 keeps the 64 x 64 ones for A/B)
-#ifndef BPE_CAST_T128
-#define BPE_CAST_T128 1
-#endif
+// The two-layout casts take the 128 x 128 tile kernels where the shape allows, the 64 x 64 ones otherwise.
 
 void launch_cast_fp8(int dtype, int fmt, const void* x, size_t n, const float* scale, void* out,
                      unsigned* amax_bits, hipStream_t s) {
@@ -542,7 +539,7 @@ void launch_cast_fp8(int dtype, int fmt, const void* x, size_t n, const float* s
 
 void launch_cast_fp8_t(const void* w, int N, int K, const float* scale, void* w8, void* w8t, unsigned* amax_bits,
                        int fmt, hipStream_t s) {
-    if (BPE_CAST_T128 && N % 128 == 0 && K % 128 == 0) {
+    if (N % 128 == 0 && K % 128 == 0) {
         const int nt = (N / 128) * (K / 128);
         const int g = nt < 2048 ? nt : 2048;
         if (fmt == 0)
@@ -565,7 +562,7 @@ void launch_cast_fp8_t(const void* w, int N, int K, const float* scale, void* w8
 
 void launch_swiglu_cast_fp8_t(int mode, const void* gu, const void* dout, int M, int F, const float* scale, void* o8,
                               void* o8t, unsigned* amax_bits, hipStream_t s) {
-    if (BPE_CAST_T128 && M % 128 == 0 && F % 128 == 0) {
+    if (M % 128 == 0 && F % 128 == 0) {
         const int nt = (M / 128) * (F / 128);
         const int g = nt < 2048 ? nt : 2048;
         if (mode == 0)

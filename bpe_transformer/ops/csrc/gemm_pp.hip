@@ -449,14 +449,7 @@ __device__ long long g_gpp_stamps[65536 * 8];
 // operands) and folds max |a| into the slot's amax -- the swiglu_cast_fp8 pass over gu (0.43 ms per Llama layer at
 // 65 536 tokens) disappears.  Same values, rounding and amax as launch_gemm_fp8 + swiglu_cast_fp8_t (bitwise).
 // Persistent kernel only (the a8 tile is transposed through 18 KiB of LDS past the two stages).
-// EPI_SWIGLU_BWD8: the fp8 input-gradient GEMM da = dY8 . W2_8 (e5m2 x e4m3, both K-major) with the SwiGLU backward
-// AND the two-layout e5m2 cast of its result in the epilogue: reads g / u from gu, writes dgu8 = e5m2([dg | du] *
-// scale) [M][2F] and dgu8t [2F][M] and folds max(|dg|, |du|) into the slot's amax -- neither da nor a bf16 dgu
-// reaches HBM, and the swiglu_cast_fp8 backward pass (0.71 ms per Llama layer) disappears.  Same values as the hand
-// fp8 GEMM + swiglu_cast_fp8_t (bitwise).  Persistent kernel only (the transposes go through the A8T tile).  Opt-in
-// (ops/fp8.py BPE_FP8_SWIGLU_BWD_GEMM): 1.89 vs 1.34 ms per Llama layer against hipBLASLt + the cast pass -- the
-// epilogue's 512 KiB of traffic per tile serialises behind the main loop, and the kernel spills 476 B per lane.
-enum { EPI_NONE = 0, EPI_SWIGLU_BWD = 1, EPI_SWIGLU_FWD = 2, EPI_ROPE = 3, EPI_SWIGLU_FWD8 = 4, EPI_SWIGLU_BWD8 = 5 };
+enum { EPI_NONE = 0, EPI_SWIGLU_BWD = 1, EPI_SWIGLU_FWD = 2, EPI_ROPE = 3, EPI_SWIGLU_FWD8 = 4 };
 constexpr bool is_swf(int e) { return e == EPI_SWIGLU_FWD || e == EPI_SWIGLU_FWD8; }
 constexpr int A8T_STRIDE = 144;               // bytes per token row of the a8 transpose tile (conflict-free reads)
 constexpr int A8T_BYTES = 128 * A8T_STRIDE;   // one pass: 128 token rows x 128 a columns
@@ -619,86 +612,6 @@ __device__ __forceinline__ void epilogue_bf16(const f32x4 (&acc)[8][4], char* st
                 st16<POL_SWF_A>(ep.act + (long)(i0 + r0) * ep.ld_act + jb, (unsigned)(((long)i * ep.ld_act + c * 8) * 2),
                                 av);
             }
-        } else if constexpr (EPI == EPI_SWIGLU_BWD8) {
-            // in two 64-row halves (registers: one half's g / u and e5m2 results at a time); per half, dg then du go
-            // through the 64 x 256 byte transpose tile (xtra, rows of 272 bytes) into dgu8t
-            static_assert(NPASS == 2, "the transpose tile covers half of one 128-row pass");
-            constexpr int QB = 4;  // 16-row groups per half
-            constexpr int TS = 272;  // transpose-tile row stride (bytes)
-            const int c = tid & 31;
-            u16x8 gv[QB], uv[QB];
-            auto load_gu = [&](int b) {
-#pragma unroll
-                for (int qq = 0; qq < QB; ++qq) {
-                    const long ro = (long)(i0 + r0 + (b * QB + qq) * 16 + (tid >> 5)) * ep.ld + j0 + c * 8;
-                    gv[qq] = ld_stream(reinterpret_cast<const u16x8*>(ep.gu + ro));
-                    uv[qq] = ld_stream(reinterpret_cast<const u16x8*>(ep.gu + ro + ep.F));
-                }
-            };
-            load_gu(0);  // the first half's operands before the barrier (as EPI_SWIGLU_BWD)
-            __builtin_amdgcn_s_waitcnt(0xc07f);
-            bar();
-            if (h == 0) GPP_STAMP_T(sid, 3);
-            const float sc = ep.a_scale[0];
-            float am = *amx;
-            const long W = 2L * ep.F;  // dgu8 row length
-            const int f4 = tid & 63, tg = tid >> 6;
-#pragma unroll
-            for (int b = 0; b < 2; ++b) {
-                if (b == 1) load_gu(1);
-                uint2 qg[QB], qu[QB];  // e5m2 dg / du of this thread's 8 columns in rows (b QB + qq) 16 + (tid >> 5)
-#pragma unroll
-                for (int qq = 0; qq < QB; ++qq) {
-                    const int i = (b * QB + qq) * 16 + (tid >> 5);
-                    const u16x8 v = *reinterpret_cast<const u16x8*>(stg + i * 512 + ((c ^ (i & 15)) << 4));
-                    float dgv[8], duv[8];
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {  // swiglu_cast_fp8_c128_kernel<1, 1>'s arithmetic, in its order
-                        const float gg = bf2f(gv[qq][e]), uu = bf2f(uv[qq][e]), dd = bf2f(v[e]);
-                        const float sg = fast_sigmoid(gg);
-                        const float silu = gg * sg;
-                        duv[e] = bf2f(f2bf(dd * silu));
-                        dgv[e] = bf2f(f2bf(dd * uu * sg * (1.f + gg * (1.f - sg))));
-                        am = fmaxf(am, fabsf(dgv[e]));
-                        am = fmaxf(am, fabsf(duv[e]));
-                    }
-                    qg[qq] = uint2{pack4_fp8<1>(dgv[0] * sc, dgv[1] * sc, dgv[2] * sc, dgv[3] * sc),
-                                   pack4_fp8<1>(dgv[4] * sc, dgv[5] * sc, dgv[6] * sc, dgv[7] * sc)};
-                    qu[qq] = uint2{pack4_fp8<1>(duv[0] * sc, duv[1] * sc, duv[2] * sc, duv[3] * sc),
-                                   pack4_fp8<1>(duv[4] * sc, duv[5] * sc, duv[6] * sc, duv[7] * sc)};
-                    uint8_t* row = ep.a8 + (long)(i0 + r0 + i) * W + j0 + c * 8;
-                    *reinterpret_cast<uint2*>(row) = qg[qq];
-                    *reinterpret_cast<uint2*>(row + ep.F) = qu[qq];
-                }
-#pragma unroll
-                for (int o = 0; o < 2; ++o) {  // dg, then du: [64 tokens][256 columns] -> [256 columns][64 tokens]
-                    if (b + o > 0) {  // the previous round's transposed reads are done before the tile is rewritten
-                        __builtin_amdgcn_s_waitcnt(0xc07f);
-                        bar();
-                    }
-#pragma unroll
-                    for (int qq = 0; qq < QB; ++qq)
-                        *reinterpret_cast<uint2*>(xtra + (qq * 16 + (tid >> 5)) * TS + c * 8) = o == 0 ? qg[qq] : qu[qq];
-                    __builtin_amdgcn_s_waitcnt(0xc07f);
-                    bar();
-                    unsigned wv[8];
-#pragma unroll
-                    for (int k = 0; k < 8; ++k)
-                        wv[k] = *reinterpret_cast<const unsigned*>(xtra + (8 * tg + k) * TS + 4 * f4);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        unsigned lo = 0, hi = 0;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) {
-                            lo |= ((wv[k] >> (8 * j)) & 0xffu) << (8 * k);
-                            hi |= ((wv[k + 4] >> (8 * j)) & 0xffu) << (8 * k);
-                        }
-                        *reinterpret_cast<uint2*>(ep.a8t + ((long)o * ep.F + j0 + 4 * f4 + j) * ep.ld_a8t + i0 + r0 +
-                                                  64 * b + 8 * tg) = uint2{lo, hi};
-                    }
-                }
-            }
-            *amx = am;
         } else if constexpr (EPI == EPI_SWIGLU_FWD8) {
             // as EPI_SWIGLU_FWD for gu; a = bf16(silu(g) u) (swiglu_cast_fp8_c128_kernel's values) is cast to e4m3
             // with the slot's scale, stored row-major from registers and, through the a8 tile in LDS (xtra), as
@@ -1032,7 +945,7 @@ gemm_pp_persist_kernel(const __bf16* __restrict__ A, long lda, const __bf16* __r
         j0 = j0n;
         jb = jbn;
     }
-    if constexpr (EPI == EPI_SWIGLU_FWD8 || EPI == EPI_SWIGLU_BWD8) {  // the workgroup's max: one atomic per workgroup
+    if constexpr (EPI == EPI_SWIGLU_FWD8) {  // the workgroup's max: one atomic per workgroup
         float m = amx;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
@@ -1044,173 +957,6 @@ gemm_pp_persist_kernel(const __bf16* __restrict__ A, long lda, const __bf16* __r
 #pragma unroll
             for (int i = 1; i < NT / 64; ++i) m = fmaxf(m, red[i]);
             atomicMax(ep.a_amax, __float_as_uint(m));  // amax >= 0: the bit pattern orders as the float
-        }
-    }
-}
-
-// Grouped weight gradients: the dW GEMMs of one layer that become ready together (W2 + [W1; W3] after the
-// SwiGLU-backward GEMM, Wo + [Wq; Wk; Wv] after the attention backward) in ONE split-K launch.  Each problem p is
-// dW_p[M_p][N_p] += dY_p^T X_p with dY_p [R][M_p] and X_p [R][N_p] token-major (or X_p^T [N_p][R] when BKM: the
-// transposed-copy route) over the same R tokens; their tiles are concatenated into one tile list and every tile
-// is split over K the same `splits` ways.  Why: a layer's dW shapes have 9-48 output tiles each, and a tile count
-// times a split count rarely fills whole waves of 256 CUs -- alone, GPT-2's W2 / W13 / Wo / Wqkv dW ran 240 / 240 /
-// 243 / 243 workgroups for 256 CUs, 5-6 % of the chip idle, plus a separate reduce launch each
-// (profiles/bench/dw_stamps_r6.log).  Grouped, the tiles x splits product is chosen for the whole set
-// (ops/gemm.py choose_splits_group).  The workgroup order is split-major with consecutive work ids on one XCD,
-// so the workgroups that read the same tokens (one split) share their dY / X rows in that XCD's L2.  Partials
-// go to each problem's fp32 slab region [splits][M_p][N_p] and dwg_reduce_kernel sums them in split order:
-// deterministic, bitwise equal to the single-problem split-K kernel at the same split count.
-constexpr int DWG_MAX = 4;
-struct DwGroup {
-    const __bf16* A[DWG_MAX];
-    const __bf16* B[DWG_MAX];
-    long lda[DWG_MAX], ldb[DWG_MAX];
-    long slab_off[DWG_MAX];  // float offset of problem p's slab region [splits][M_p][N_p]
-    int M[DWG_MAX], N[DWG_MAX];
-    int tile_end[DWG_MAX];  // inclusive prefix sums of the problems' tile counts
-    int np, ntiles, splits, R;
-    int prio;
-};
-
-template <bool BKM>
-__global__ void __launch_bounds__(NT, 1) gemm_pp_dwg_kernel(DwGroup gp, float* __restrict__ slab) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, l = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int g = w >> 2, wl = w & 3;
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int xcd = orig & 7, qq = nwg >> 3, rr = nwg & 7;
-    const int wid = (xcd < rr ? xcd * (qq + 1) : rr * (qq + 1) + (xcd - rr) * qq) + (orig >> 3);
-    const int split = wid / gp.ntiles, gt = wid % gp.ntiles;
-    // the problem of global tile gt, selected with constant indices only (no dynamic indexing of the kernarg
-    // arrays, which hipcc would copy to scratch)
-    const __bf16* A = gp.A[0];
-    const __bf16* B = gp.B[0];
-    long lda = gp.lda[0], ldb = gp.ldb[0], soff = gp.slab_off[0];
-    int M = gp.M[0], N = gp.N[0], t0 = 0;
-#pragma unroll
-    for (int q = 1; q < DWG_MAX; ++q) {
-        if (q < gp.np && gt >= gp.tile_end[q - 1]) {
-            A = gp.A[q];
-            B = gp.B[q];
-            lda = gp.lda[q];
-            ldb = gp.ldb[q];
-            soff = gp.slab_off[q];
-            M = gp.M[q];
-            N = gp.N[q];
-            t0 = gp.tile_end[q - 1];
-        }
-    }
-    const int tile = gt - t0, tiles_n = N / BT;
-    const int i0 = (tile / tiles_n) * BT, j0 = (tile % tiles_n) * BT;
-    const int nkt = gp.R / BK;
-    const int kb = (int)((long)split * nkt / gp.splits);
-    const int nk = (int)((long)(split + 1) * nkt / gp.splits) - kb;
-    GPP_STAMP(0);
-    GPP_STAMP_VAL(6, wid);
-#ifdef BPE_GPP_STAMPS
-    {
-        unsigned xcc, hw;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-        GPP_STAMP_VAL(7, (long long)(xcc & 15));
-        GPP_STAMP_VAL(5, (long long)hw);
-    }
-#endif
-    if (gp.prio && g == 1) __builtin_amdgcn_s_setprio(1);
-    f32x4 acc[8][4];
-#pragma unroll
-    for (int a = 0; a < 8; ++a)
-#pragma unroll
-        for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // BKM (X^T copy, B K-major): two DMA pieces per load section; both token-major: one of them inside each MFMA
-    // section (ktile_spread SPLIT) -- the same choices as the single-problem routes
-    const SpreadOff so = spread_offsets<false, BKM>(g, wl, l, (int)lda, (int)ldb);
-    {
-        const long k0 = (long)kb * BK;
-        const __bf16* a0 = tile_ptr<false>(A, lda, i0, k0);
-        const __bf16* b0 = tile_ptr<BKM>(B, ldb, j0, k0);
-        dma_pair(a0, so.a0, smem, so.la0);
-        dma_pair(b0, so.b0, smem + OPB, so.lb0);
-        dma_pair(b0, so.b1, smem + OPB, so.lb1);
-        dma_pair(a0, so.a1, smem, so.la1);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        bar();
-    }
-    GPP_STAMP(1);
-    if (g == 1) bar();  // the stagger
-    for (int kt = 0; kt < nk; ++kt) {
-        char* cur = smem + (kt & 1) * STAGE;
-        char* nxt = smem + ((kt + 1) & 1) * STAGE;
-        const long k1 = (long)(kb + kt + 1) * BK;
-        ktile_spread<false, BKM, 0>(cur, nxt, kt + 1 < nk, tile_ptr<false>(A, lda, i0, k1),
-                                    tile_ptr<BKM>(B, ldb, j0, k1), so, g, wl, l, acc, false, kt);
-    }
-    GPP_STAMP(2);
-    if (g == 0) bar();
-    __builtin_amdgcn_s_waitcnt(0x70);
-    bar();
-    float* sp = slab + soff + (long)split * M * N;
-#pragma unroll
-    for (int ib = 0; ib < 8; ++ib)
-#pragma unroll
-        for (int jq = 0; jq < 4; ++jq) {
-            const long i = i0 + 128 * g + 16 * ib + (l & 15);
-            const long j = j0 + 64 * wl + 16 * jq + 4 * (l >> 4);
-            *reinterpret_cast<f32x4*>(sp + i * N + j) = acc[ib][jq];
-        }
-    GPP_STAMP(4);
-}
-
-// C_p = beta * C_p + sum over splits of problem p's slab region, in split order (the grouped form of
-// splitk_reduce_kernel: one launch for every problem of a group).  end4[p]: inclusive prefix sums of M_p N_p / 4.
-struct DwOut {
-    void* C[DWG_MAX];
-    long ldc[DWG_MAX];
-    long slab_off[DWG_MAX];
-    long end4[DWG_MAX];
-    int N[DWG_MAX];
-    int np, splits;
-    float beta;
-};
-
-template <typename CT>
-__global__ void __launch_bounds__(256) dwg_reduce_kernel(const float* __restrict__ slab, DwOut o) {
-    const long total4 = o.end4[o.np - 1];
-    for (long t = blockIdx.x * 256L + threadIdx.x; t < total4; t += (long)gridDim.x * 256) {
-        CT* C = (CT*)o.C[0];
-        long ldc = o.ldc[0], soff = o.slab_off[0], b4 = 0, mn = o.end4[0] * 4;
-        int N = o.N[0];
-#pragma unroll
-        for (int q = 1; q < DWG_MAX; ++q) {
-            if (q < o.np && t >= o.end4[q - 1]) {
-                C = (CT*)o.C[q];
-                ldc = o.ldc[q];
-                soff = o.slab_off[q];
-                b4 = o.end4[q - 1];
-                mn = (o.end4[q] - o.end4[q - 1]) * 4;
-                N = o.N[q];
-            }
-        }
-        const long e = (t - b4) * 4;
-        const long i = e / N, j = e % N;
-        const float* sp = slab + soff + e;
-        f32x4 s = *reinterpret_cast<const f32x4*>(sp);
-        for (int k = 1; k < o.splits; ++k) s += *reinterpret_cast<const f32x4*>(sp + (long)k * mn);
-        if constexpr (sizeof(CT) == 4) {
-            f32x4* cp = reinterpret_cast<f32x4*>(C + i * ldc + j);
-            if (o.beta != 0.f) s += o.beta * *cp;
-            *cp = s;
-        } else {
-            u16x4* cp = reinterpret_cast<u16x4*>(C + i * ldc + j);
-            if (o.beta != 0.f) {
-                const u16x4 c = *cp;
-                s[0] += o.beta * bf2f(c[0]);
-                s[1] += o.beta * bf2f(c[1]);
-                s[2] += o.beta * bf2f(c[2]);
-                s[3] += o.beta * bf2f(c[3]);
-            }
-            *cp = u16x4{f2bf(s[0]), f2bf(s[1]), f2bf(s[2]), f2bf(s[3])};
         }
     }
 }
@@ -1386,28 +1132,6 @@ void launch_gemm_fp8_swiglu(const void* A8, long lda, const void* B8, long ldb, 
         (__bf16*)nullptr, 0L, 0.f, M, 2 * F, K / 2, ep);
 }
 
-// da = (G8 . W2t_8^T) * sa * sb (G8 e5m2 [M][K], W2t_8 e4m3 [F][K], both K-major) with the SwiGLU backward over gu
-// ([M][2F] bf16) and the two-layout e5m2 cast of [dg | du] (scale d_scale) into dgu8 [M][2F] / dgu8t [2F][M], the
-// max folded into *d_amax (EPI_SWIGLU_BWD8).  M a multiple of 256, F of 256, K of 128.  Persistent kernel only.
-void launch_gemm_fp8_swiglu_bwd(const void* G8, long ldg8, const void* W8, long ldw8, const void* gu, void* dgu8,
-                                void* dgu8t, int M, int F, int K, const float* sa, const float* sb,
-                                const float* d_scale, unsigned* d_amax, hipStream_t s) {
-    Epi ep = make_epi(g_gm >= 0 ? g_gm : 8);
-    ep.gu = (const __bf16*)gu;
-    ep.ld = 2L * F;
-    ep.F = F;
-    ep.sa = sa;
-    ep.sb = sb;
-    ep.a8 = (uint8_t*)dgu8;
-    ep.a8t = (uint8_t*)dgu8t;
-    ep.ld_a8t = M;
-    ep.a_scale = d_scale;
-    ep.a_amax = d_amax;
-    launch<&gemm_pp_persist_kernel<true, true, EPI_SWIGLU_BWD8, 2>>(
-        true, (M / BT) * (F / BT), A8T_BYTES, s, (const __bf16*)G8, ldg8 / 2, (const __bf16*)W8, ldw8 / 2,
-        (__bf16*)nullptr, 0L, 0.f, M, F, K / 2, ep);
-}
-
 // C = beta * C + (A8 . B8^T) * sa * sb, split over K into `splits` fp32 partials (slab [splits][M][N]) summed in a
 // fixed order by splitk_reduce: the fp8 weight-gradient GEMM (few output tiles, K = all tokens).  C bf16 or fp32.
 void launch_gemm_fp8_splitk(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K,
@@ -1441,48 +1165,6 @@ static void launch_pp(const __bf16* a, long lda, const __bf16* b, long ldb, floa
                                                beta, M, N, R, splits, make_epi(g_gm >= 0 ? g_gm : 0));
     else
         launch_onepass<AK, BKM, EPI_NONE>(a, lda, b, ldb, c, ldc, beta, M, N, R, make_epi(order_for(N / BT)), s);
-}
-
-// Grouped weight gradients (gemm_pp_dwg_kernel, then dwg_reduce_kernel): np <= 4 problems C_p[M_p][N_p] =
-// beta C_p + dY_p^T X_p over R tokens, every tile split `splits` ways; slab: splits * sum M_p N_p floats.
-void launch_gemm_pp_dw_group(int np, const void* const* A, const long* lda, const void* const* B, const long* ldb,
-                             int b_kmajor, void* const* C, const long* ldc, const int* M, const int* N, int R,
-                             int splits, float beta, float* slab, int c_f32, hipStream_t s) {
-    DwGroup gp{};
-    DwOut o{};
-    long off = 0, e4 = 0;
-    int tiles = 0;
-    for (int p = 0; p < np; ++p) {
-        gp.A[p] = (const __bf16*)A[p];
-        gp.B[p] = (const __bf16*)B[p];
-        gp.lda[p] = lda[p];
-        gp.ldb[p] = ldb[p];
-        gp.slab_off[p] = o.slab_off[p] = off;
-        gp.M[p] = M[p];
-        gp.N[p] = o.N[p] = N[p];
-        tiles += (M[p] / BT) * (N[p] / BT);
-        gp.tile_end[p] = tiles;
-        off += (long)splits * M[p] * N[p];
-        o.C[p] = C[p];
-        o.ldc[p] = ldc[p];
-        e4 += (long)M[p] * N[p] / 4;
-        o.end4[p] = e4;
-    }
-    gp.np = o.np = np;
-    gp.ntiles = tiles;
-    gp.splits = o.splits = splits;
-    gp.R = R;
-    gp.prio = prio_mode();
-    o.beta = beta;
-    if (b_kmajor)
-        launch<&gemm_pp_dwg_kernel<true>>(false, tiles * splits, 0, s, gp, slab);
-    else
-        launch<&gemm_pp_dwg_kernel<false>>(false, tiles * splits, 0, s, gp, slab);
-    const int g = (int)std::min<long>((e4 + 255) / 256, 2048);
-    if (c_f32)
-        dwg_reduce_kernel<float><<<g, 256, 0, s>>>(slab, o);
-    else
-        dwg_reduce_kernel<__bf16><<<g, 256, 0, s>>>(slab, o);
 }
 
 void launch_gemm_pp(int a_kmajor, int b_kmajor, const void* A, long lda, const void* B, long ldb, void* C, long ldc,

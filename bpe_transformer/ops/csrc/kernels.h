@@ -88,22 +88,12 @@ bool gemm_pp_shape_ok(int M, int N, int R, int splits);
 void launch_gemm_pp(int a_kmajor, int b_kmajor, const void* A, long lda, const void* B, long ldb, void* C, long ldc,
                     float beta, int M, int N, int R, int splits, float* slab, int c_f32, hipStream_t s);
 
-// grouped weight gradients: np <= 4 problems C_p (+)= dY_p^T X_p over the same R tokens in one split-K launch and
-// one ordered reduce (X_p token-major, or X_p^T [N_p][R] with b_kmajor); slab: splits * sum M_p N_p floats
-void launch_gemm_pp_dw_group(int np, const void* const* A, const long* lda, const void* const* B, const long* ldb,
-                             int b_kmajor, void* const* C, const long* ldc, const int* M, const int* N, int R,
-                             int splits, float beta, float* slab, int c_f32, hipStream_t s);
-
 // fp8 x fp8 -> bf16 on the ping-pong kernel with v_mfma_scale_f32_16x16x128_f8f6f4: C = A8 B8^T * sa * sb,
 // A8 [M][K] (fmt_a 0 e4m3 / 1 e5m2), B8 [N][K] e4m3, both K-major; strides in bytes (A, B) / elements (C)
 // gu = (X8 . W13_8^T) * sa * sb with a = silu(g) u cast to e4m3 in both layouts + amax (fused fp8 SwiGLU forward)
 void launch_gemm_fp8_swiglu(const void* A8, long lda, const void* B8, long ldb, void* gu, long ldg, void* a8,
                             void* a8t, int M, int F, int K, const float* sa, const float* sb, const float* a_scale,
                             unsigned* a_amax, hipStream_t s);
-// da = G8 . W2t_8^T with the SwiGLU backward and the two-layout e5m2 cast of [dg | du] + amax (fused fp8 backward)
-void launch_gemm_fp8_swiglu_bwd(const void* G8, long ldg8, const void* W8, long ldw8, const void* gu, void* dgu8,
-                                void* dgu8t, int M, int F, int K, const float* sa, const float* sb,
-                                const float* d_scale, unsigned* d_amax, hipStream_t s);
 void launch_gemm_fp8(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K,
                      int fmt_a, const float* sa, const float* sb, hipStream_t s);
 

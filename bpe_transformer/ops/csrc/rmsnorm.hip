@@ -465,12 +465,8 @@ void launch_rmsnorm_fwd(int dtype, const void* x, const void* w, void* y, float*
                                                          eps);
 }
 
-// 1: the half-wave-row backward where the row width allows (a variant build with 0 keeps the one-wave-per-row kernel)
-#ifndef BPE_RMS_BWD_HW
-#define BPE_RMS_BWD_HW 1
-#endif
-
-// returns the grid it launched (the partial rows colsum_kernel then sums; at most the grid it was given)
+// The half-wave-row backward where the row width allows, the one-wave-per-row kernel for the other widths.
+// Returns the grid it launched (the partial rows colsum_kernel then sums; at most the grid it was given).
 template <typename T>
 static int rms_bwd_dispatch(const T* dy, const T* x, const T* w, const float* rstd, T* dx, float* partial,
                             const T* dres, int grid, int M, int N, hipStream_t s) {
@@ -485,7 +481,7 @@ static int rms_bwd_dispatch(const T* dy, const T* x, const T* w, const float* rs
         return grid;
     }
     const size_t lds = (size_t)4 * N * sizeof(float);
-    if (BPE_RMS_BWD_HW && M % 2 == 0 && (N / V) % 32 == 0 && N / V >= 64 && N / V <= 128) {
+    if (M % 2 == 0 && (N / V) % 32 == 0 && N / V >= 64 && N / V <= 128) {
         grid = grid < 512 ? grid : 512;  // one resident round: 2 workgroups per CU at 184 VGPRs (C = 3)
         switch (N / V / 32) {
             case 2: rmsnorm_bwd_hw_kernel<T, 2><<<grid, 256, lds, s>>>(dy, x, w, rstd, dx, partial, dres, M, N); break;
@@ -524,12 +520,10 @@ void launch_add_rmsnorm_fwd(int dtype, const void* x, const void* d, const void*
 }
 
 // one resident round: the narrow kernel holds 3 workgroups per CU (156 VGPRs at C = 2), 256 CUs
-#ifndef BPE_RMS_BWD_GRID
-#define BPE_RMS_BWD_GRID 768
-#endif
+constexpr int RMS_BWD_GRID = 768;
 int rmsnorm_bwd_grid(int M) {
     int g = (M + 3) / 4;
-    return g < BPE_RMS_BWD_GRID ? g : BPE_RMS_BWD_GRID;
+    return g < RMS_BWD_GRID ? g : RMS_BWD_GRID;
 }
 
 // dw_mode: 0 = write dw (the activation dtype), 1 / 2 = accumulate into a bf16 / fp32 gradient slot at dw

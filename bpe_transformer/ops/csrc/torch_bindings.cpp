@@ -411,60 +411,6 @@ void gemm_pp(const at::Tensor& A, bool a_kmajor, const at::Tensor& B, bool b_kma
                    c32 ? 1 : 0, cur_stream());
 }
 
-// Grouped weight gradients (gemm_pp.hip gemm_pp_dw_group): gs[p] = beta * gs[p] + dys[p]^T xs[p] for up to 4
-// problems over the same R tokens in ONE split-K launch plus one ordered reduce.  dys[p] [R, M_p] token-major;
-// xs[p] [R, N_p] token-major, or X^T [N_p, R] with x_kmajor; gs[p] [M_p, N_p], all bf16 or all fp32.
-void gemm_pp_dw_group(at::TensorList gs, at::TensorList dys, at::TensorList xs, bool x_kmajor, int64_t splits,
-                      double beta) {
-    const int np = (int)gs.size();
-    TORCH_CHECK(np >= 1 && np <= 4 && (int)dys.size() == np && (int)xs.size() == np,
-                "gemm_pp_dw_group: 1-4 problems, one dY and one X per gradient");
-    const bool c32 = gs[0].scalar_type() == at::kFloat;
-    const void* A[4];
-    const void* B[4];
-    void* C[4];
-    long lda[4], ldb[4], ldc[4];
-    int M[4], N[4];
-    const int R = (int)dys[0].size(0);
-    long slab_elems = 0;
-    for (int p = 0; p < np; ++p) {
-        const at::Tensor& g = gs[p];
-        const at::Tensor& dy = dys[p];
-        const at::Tensor& x = xs[p];
-        check_cuda(g, "g");
-        TORCH_CHECK(g.scalar_type() == gs[0].scalar_type() &&
-                        (g.scalar_type() == at::kBFloat16 || g.scalar_type() == at::kFloat) &&
-                        dy.scalar_type() == at::kBFloat16 && x.scalar_type() == at::kBFloat16,
-                    "gemm_pp_dw_group: bf16 operands, gradients all bf16 or all fp32");
-        TORCH_CHECK(g.dim() == 2 && dy.dim() == 2 && x.dim() == 2 && g.stride(1) == 1 && dy.stride(1) == 1 &&
-                        x.stride(1) == 1, "gemm_pp_dw_group: 2-D row-major operands required");
-        TORCH_CHECK(dy.device() == g.device() && x.device() == g.device() && g.device() == gs[0].device(),
-                    "gemm_pp_dw_group: operands on different devices");
-        M[p] = (int)g.size(0);
-        N[p] = (int)g.size(1);
-        TORCH_CHECK(dy.size(0) == R && dy.size(1) == M[p], "gemm_pp_dw_group: dY [R, M] with one R for all problems");
-        TORCH_CHECK(x_kmajor ? (x.size(0) == N[p] && x.size(1) == R) : (x.size(0) == R && x.size(1) == N[p]),
-                    "gemm_pp_dw_group: X shape mismatch");
-        TORCH_CHECK(gemm_pp_shape_ok(M[p], N[p], R, (int)splits),
-                    "gemm_pp_dw_group: M, N must be multiples of 256, R of 64 (>= splits)");
-        TORCH_CHECK(dy.stride(0) % 8 == 0 && x.stride(0) % 8 == 0 && g.stride(0) % 8 == 0,
-                    "gemm_pp_dw_group: 16-byte row alignment");
-        TORCH_CHECK(dy.stride(0) * 256 < (1L << 31) && x.stride(0) * 256 < (1L << 31),
-                    "gemm_pp_dw_group: leading dimension too large for 32-bit tile offsets");
-        A[p] = dy.data_ptr();
-        B[p] = x.data_ptr();
-        C[p] = g.data_ptr();
-        lda[p] = dy.stride(0);
-        ldb[p] = x.stride(0);
-        ldc[p] = g.stride(0);
-        slab_elems += splits * (long)M[p] * N[p];
-    }
-    DevGuard dg(gs[0].device());
-    auto slab = at::empty({slab_elems}, gs[0].options().dtype(at::kFloat));
-    launch_gemm_pp_dw_group(np, A, lda, B, ldb, x_kmajor ? 1 : 0, C, ldc, M, N, R, (int)splits, (float)beta,
-                            slab.data_ptr<float>(), c32 ? 1 : 0, cur_stream());
-}
-
 // y = (a8 @ b8^T) * sa * sb in bf16: a8 [M, K] e4m3 / e5m2, b8 [N, K] e4m3 (both K-major), sa / sb device fp32
 // scalars (the per-tensor inverse scales); the hand-written fp8 MFMA ping-pong kernel (gemm_pp.hip)
 at::Tensor gemm_fp8(const at::Tensor& a8, const at::Tensor& b8, const at::Tensor& sa, const at::Tensor& sb) {
@@ -522,42 +468,6 @@ at::Tensor gemm_fp8_swiglu(const at::Tensor& x8, const at::Tensor& w8, const at:
                            sb.data_ptr<float>(), a_scale.data_ptr<float>(),
                            reinterpret_cast<unsigned*>(a_amax.data_ptr<int>()), cur_stream());
     return gu;
-}
-
-// the fp8 W2 input gradient with the SwiGLU backward fused: da = (g8 @ w8t^T) * sa * sb (g8 e5m2 [M, K], w8t e4m3
-// [F, K]) never leaves the kernel; [dg | du] from da and gu ([M, 2F] bf16) is written as e5m2 with d_scale in both
-// layouts (dgu8 [M, 2F], dgu8t [2F, M]) and its max folded into d_amax (gemm_pp.hip EPI_SWIGLU_BWD8)
-void gemm_fp8_swiglu_bwd(const at::Tensor& g8, const at::Tensor& w8t, const at::Tensor& sa, const at::Tensor& sb,
-                         const at::Tensor& gu, const at::Tensor& d_scale, at::Tensor dgu8, at::Tensor dgu8t,
-                         at::Tensor d_amax) {
-    check_cuda(g8, "g8");
-    check_cuda(w8t, "w8t");
-    check_cuda(gu, "gu");
-    TORCH_CHECK(g8.scalar_type() == at::kFloat8_e5m2 && w8t.scalar_type() == at::kFloat8_e4m3fn,
-                "gemm_fp8_swiglu_bwd: g8 e5m2, w8t e4m3");
-    TORCH_CHECK(g8.dim() == 2 && w8t.dim() == 2 && g8.is_contiguous() && w8t.is_contiguous() && g8.size(1) == w8t.size(1),
-                "gemm_fp8_swiglu_bwd: g8 [M, K] and w8t [F, K] contiguous with a common K");
-    const int64_t M = g8.size(0), F = w8t.size(0), K = g8.size(1);
-    TORCH_CHECK(M % 256 == 0 && F % 256 == 0 && K % 128 == 0 && K > 0,
-                "gemm_fp8_swiglu_bwd: M and F multiples of 256, K of 128");
-    TORCH_CHECK(K * 256 < (1L << 32) && F * K < (1L << 32), "gemm_fp8_swiglu_bwd: operand offsets exceed 32 bits");
-    TORCH_CHECK(gu.scalar_type() == at::kBFloat16 && gu.is_contiguous() && gu.dim() == 2 && gu.size(0) == M &&
-                    gu.size(1) == 2 * F && gu.device() == g8.device(), "gemm_fp8_swiglu_bwd: gu bf16 [M, 2F]");
-    TORCH_CHECK(dgu8.is_contiguous() && dgu8t.is_contiguous() && dgu8.scalar_type() == at::kFloat8_e5m2 &&
-                    dgu8t.scalar_type() == at::kFloat8_e5m2 && dgu8.dim() == 2 && dgu8.size(0) == M &&
-                    dgu8.size(1) == 2 * F && dgu8t.dim() == 2 && dgu8t.size(0) == 2 * F && dgu8t.size(1) == M &&
-                    dgu8.device() == g8.device() && dgu8t.device() == g8.device(),
-                "gemm_fp8_swiglu_bwd: dgu8 [M, 2F] and dgu8t [2F, M] e5m2 on the operands' device");
-    TORCH_CHECK(sa.scalar_type() == at::kFloat && sb.scalar_type() == at::kFloat && d_scale.scalar_type() == at::kFloat &&
-                    sa.numel() >= 1 && sb.numel() >= 1 && d_scale.numel() == 1 && d_amax.scalar_type() == at::kInt &&
-                    d_amax.numel() == 1 && sa.device() == g8.device() && sb.device() == g8.device() &&
-                    d_scale.device() == g8.device() && d_amax.device() == g8.device(),
-                "gemm_fp8_swiglu_bwd: fp32 device scalars sa, sb, d_scale and one int32 amax slot");
-    DevGuard g(g8.device());
-    launch_gemm_fp8_swiglu_bwd(g8.data_ptr(), g8.stride(0), w8t.data_ptr(), w8t.stride(0), gu.data_ptr(),
-                               dgu8.data_ptr(), dgu8t.data_ptr(), (int)M, (int)F, (int)K, sa.data_ptr<float>(),
-                               sb.data_ptr<float>(), d_scale.data_ptr<float>(),
-                               reinterpret_cast<unsigned*>(d_amax.data_ptr<int>()), cur_stream());
 }
 
 // qkv = (a8 @ b8^T) * sa * sb (e4m3 x e4m3) with RoPE on output columns [0, rot_cols) in the epilogue
@@ -1357,12 +1267,9 @@ TORCH_LIBRARY(bpe_hip, m) {
     m.def("gemm_fp8(Tensor a8, Tensor b8, Tensor sa, Tensor sb) -> Tensor");
     m.def("gemm_fp8_swiglu(Tensor x8, Tensor w8, Tensor sa, Tensor sb, Tensor a_scale, Tensor(a!) a8, Tensor(b!) a8t, "
           "Tensor(c!) a_amax) -> Tensor");
-    m.def("gemm_fp8_swiglu_bwd(Tensor g8, Tensor w8t, Tensor sa, Tensor sb, Tensor gu, Tensor d_scale, "
-          "Tensor(a!) dgu8, Tensor(b!) dgu8t, Tensor(c!) d_amax) -> ()");
     m.def("gemm_fp8_rope(Tensor a8, Tensor b8, Tensor sa, Tensor sb, Tensor cos, Tensor sin, int S, int D, "
           "int rot_cols) -> Tensor");
     m.def("gemm_pp(Tensor A, bool a_kmajor, Tensor B, bool b_kmajor, Tensor(a!) C, float beta, int splits=1) -> ()");
-    m.def("gemm_pp_dw_group(Tensor(a!)[] gs, Tensor[] dys, Tensor[] xs, bool x_kmajor, int splits, float beta=1.0) -> ()");
     m.def("gemm(Tensor A, bool a_kmajor, Tensor B, bool b_kmajor, Tensor(a!) C, float beta, int splits, int tile=128) -> ()");
     m.def("cast_fp8(Tensor x, Tensor scale, Tensor(a!) out, Tensor(b!) amax_bits) -> ()");
     m.def("transpose_bf16(Tensor w, Tensor? scale=None) -> Tensor");
@@ -1416,14 +1323,12 @@ TORCH_LIBRARY_IMPL(bpe_hip, CUDA, m) {
     m.impl("scale_", &scale_);
     m.impl("gemm", &gemm);
     m.impl("gemm_pp", &gemm_pp);
-    m.impl("gemm_pp_dw_group", &gemm_pp_dw_group);
     m.impl("gemm_swiglu_bwd", &gemm_swiglu_bwd);
     m.impl("gemm_swiglu_fwd", &gemm_swiglu_fwd);
     m.impl("gemm_qkv_rope", &gemm_qkv_rope);
     m.impl("gemm_fp8_acc", &gemm_fp8_acc);
     m.impl("gemm_fp8", &gemm_fp8);
     m.impl("gemm_fp8_swiglu", &gemm_fp8_swiglu);
-    m.impl("gemm_fp8_swiglu_bwd", &gemm_fp8_swiglu_bwd);
     m.impl("gemm_fp8_rope", &gemm_fp8_rope);
     m.impl("cast_fp8", &cast_fp8);
     m.impl("transpose_bf16", &transpose_bf16);

@@ -655,57 +655,6 @@ def test_gemm_pp_tile_order_bitwise(gpu_device, persist):
     assert rel(outs[0][0].cpu(), (x.float() @ w.float().t()).cpu()) < 1e-2
 
 
-@pytest.mark.parametrize("x_k", [False, True])
-@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
-@pytest.mark.parametrize("splits", [1, 3])
-def test_gemm_pp_dw_group_exact(gpu_device, x_k, dtype, splits):
-    """Grouped weight gradients on small-integer operands: three problems of different shapes and strides (one a
-    column slice of a wider buffer, like a stacked-weight gradient view) in one launch, every output exact."""
-    torch.manual_seed(3)
-    R = 1216
-    shapes = [(512, 768), (256, 256), (768, 512)]
-    gs, dys, xs, refs = [], [], [], []
-    for i, (m, n) in enumerate(shapes):
-        dy = torch.randint(-1, 2, (R, m), device=gpu_device).to(torch.bfloat16)
-        x = torch.randint(-1, 2, (R, n), device=gpu_device).to(torch.bfloat16)
-        wide = torch.randint(-3, 4, (m, n + 256 * i), device=gpu_device).to(dtype)
-        g = wide[:, 256 * i :]  # a strided view: row stride != N for i > 0
-        refs.append(g.float() + dy.float().t() @ x.float())
-        gs.append(g)
-        dys.append(dy)
-        xs.append(x.t().contiguous() if x_k else x)
-    torch.ops.bpe_hip.gemm_pp_dw_group(gs, dys, xs, x_k, splits, 1.0)
-    for g, ref in zip(gs, refs):
-        assert torch.equal(g.float().cpu(), ref.cpu())
-
-
-def test_gemm_pp_dw_group_bitwise_vs_single(gpu_device, monkeypatch):
-    """Random operands at GPT-2-like dW shapes (more workgroups than CUs): the grouped launch runs each tile's
-    split exactly as the single-problem split-K kernel does and reduces in the same split order, so every
-    gradient matches the per-shape ``gemm_pp`` route bitwise; repeated launches are bitwise stable."""
-    from bpe_transformer.ops import gemm
-    from bpe_transformer.ops.gemm import accumulate_weight_grads, choose_splits_group
-
-    monkeypatch.setattr(gemm, "_GROUP", True)  # the grouped launch is opt-in (BPE_DW_GROUP=1)
-    torch.manual_seed(4)
-    T = 16384
-    shapes = [(768, 2048), (4096, 768)]  # W2 and [W1; W3] of GPT-2-small: 24 + 48 tiles
-    dys = [torch.randn(T, m, device=gpu_device, dtype=torch.bfloat16) * 0.1 for m, _ in shapes]
-    xs = [torch.randn(T, n, device=gpu_device, dtype=torch.bfloat16) for _, n in shapes]
-    g0 = [torch.randn(m, n, device=gpu_device, dtype=torch.bfloat16) for m, n in shapes]
-    s = choose_splits_group(72, T, sum(m * n for m, n in shapes))
-    single = [g.clone() for g in g0]
-    for g, dy, x in zip(single, dys, xs):
-        torch.ops.bpe_hip.gemm_pp(dy, False, x, False, g, 1.0, s)
-    for _ in range(2):
-        grouped = [g.clone() for g in g0]
-        accumulate_weight_grads(list(zip(grouped, dys, xs)))
-        for a, b in zip(grouped, single):
-            assert torch.equal(a, b)
-    ref = g0[1].float() + dys[1].float().t() @ xs[1].float()
-    assert rel(grouped[1].cpu(), ref.cpu()) < 1e-2
-
-
 @pytest.mark.parametrize("a_k,b_k", [(True, True), (True, False), (False, True), (False, False)])
 @pytest.mark.parametrize("splits", [1, 3])
 def test_gemm_pp_exact(gpu_device, gpp_mode, a_k, b_k, splits):
@@ -1332,38 +1281,6 @@ def test_gemm_fp8_swiglu_matches_gemm_then_cast(gpu_device, M, F, K, persist):
     g, u = ref[:, :F], ref[:, F:]
     a = g * torch.sigmoid(g) * u
     assert rel(a8.float().cpu() / 4.0, a.cpu()) < 0.08
-
-
-@pytest.mark.parametrize("M,F,K,persist", [(512, 512, 256, 1), (4096, 768, 512, 40), (1024, 5632, 2048, 1)])
-def test_gemm_fp8_swiglu_bwd_matches_gemm_then_cast(gpu_device, M, F, K, persist):
-    """The fused fp8 W2 input gradient + SwiGLU backward + two-layout e5m2 cast (gemm_fp8_swiglu_bwd,
-    EPI_SWIGLU_BWD8) against the pair it replaces -- the hand fp8 GEMM da = g8 @ w8t^T (e5m2 x e4m3) then
-    swiglu_cast_fp8_t(gu, da): dgu8, dgu8t and the amax must match BITWISE."""
-    h = torch.ops.bpe_hip
-    torch.manual_seed(12)
-    g8 = torch.randn(M, K, device=gpu_device).to(torch.float8_e5m2)
-    w8t = (4 * torch.randn(F, K, device=gpu_device)).to(torch.float8_e4m3fn)
-    gu = torch.randn(M, 2 * F, device=gpu_device).to(torch.bfloat16)
-    sg = torch.tensor([0.25], device=gpu_device)
-    sw = torch.tensor([1.0 / K**0.5], device=gpu_device)
-    sc = torch.tensor([64.0], device=gpu_device)
-    prev = h.gpp_persist_config(persist)
-    try:
-        amax_f = torch.zeros(1, dtype=torch.int32, device=gpu_device)
-        d8 = torch.empty(M, 2 * F, dtype=torch.float8_e5m2, device=gpu_device)
-        d8t = torch.empty(2 * F, M, dtype=torch.float8_e5m2, device=gpu_device)
-        h.gemm_fp8_swiglu_bwd(g8, w8t, sg, sw, gu, sc, d8, d8t, amax_f)
-        da = h.gemm_fp8(g8, w8t, sg, sw)
-    finally:
-        h.gpp_persist_config(prev)
-    amax_r = torch.zeros(1, dtype=torch.int32, device=gpu_device)
-    d8_r = torch.empty_like(d8)
-    d8t_r = torch.empty_like(d8t)
-    h.swiglu_cast_fp8_t(gu, da, sc, d8_r, d8t_r, amax_r)
-    assert torch.equal(d8.view(torch.uint8), d8_r.view(torch.uint8))
-    assert torch.equal(d8t.view(torch.uint8), d8t_r.view(torch.uint8))
-    assert torch.equal(d8t.view(torch.uint8), d8.view(torch.uint8).t())
-    assert int(amax_f) == int(amax_r) and int(amax_f) != 0
 
 
 def test_gemm_fp8_persistent_bitwise_many_tiles(gpu_device):

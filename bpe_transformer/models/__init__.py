@@ -12,7 +12,7 @@ from .layers import (
     SwiGLU,
     TransformerBlock,
 )
-from .generation import DecodeSession, KVCache
+from .generation import DecodeSession, KVCache, SpeculativeSession
 from .transformer import TransformerLM
 
 __all__ = [
@@ -26,6 +26,7 @@ __all__ = [
     "MultiHeadSelfAttention",
     "RMSNorm",
     "RotaryPositionalEmbedding",
+    "SpeculativeSession",
     "SwiGLU",
     "TransformerBlock",
     "TransformerLM",

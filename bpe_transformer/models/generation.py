@@ -323,6 +323,42 @@ class DecodeSession:
         return out
 
     @torch.no_grad()
+    def score(self, ids: Tensor) -> Tensor:
+        """Append the window ``ids [B, T]`` like :meth:`prefill`, every sequence the whole of it, and return the
+        logits of every position, ``[B, T, V]``: row ``t`` is the distribution of the token after ``ids[:, t]``.
+        Routing is ``_append_plan``'s: a window of at most ``8 // G`` tokens on a filled cache is one ``decode_attn``
+        step, a larger one ``cache_attn`` -- what verifying draft tokens needs."""
+        ids = ids.to(self.device)
+        B, T = ids.shape
+        assert B == self.batch, f"session batch is {self.batch}, got {B}"
+        c = self.cache
+        rows = list(range(B))
+        assert all(p + T <= self.max_len for p in c._len), "KV cache full"
+        if not self.fast:  # the oracle math reads the host lengths, which therefore move chunk by chunk
+            out = []
+            for t0, w in _chunks(T, self.prefill_chunk):
+                out.append(self._forward_reference(ids[:, t0 : t0 + w], [w] * B, rows, all_logits=True))
+                c.advance(rows, [w] * B)
+            return torch.cat(out, 1)
+        out = [self._forward_fast(ids[:, t0 : t0 + w], prefill=kind == "flash", cache=kind == "cache",
+                                  all_logits=True).view(B, w, -1)
+               for t0, w, kind in _append_plan(T, self.H // self.Hkv, max(c._len) > 0, self.prefill_chunk)]
+        c.advance(rows, [T] * B)
+        return out[0] if len(out) == 1 else torch.cat(out, 1)
+
+    @torch.no_grad()
+    def truncate(self, lengths) -> None:
+        """Ragged sessions: cut sequence ``b`` back to its first ``lengths[b]`` tokens (at most what it holds).  The
+        cache rows past the new position become invisible, like everything at and past ``pos[b]``."""
+        assert self.ragged, "truncate needs DecodeSession(..., ragged=True)"
+        n = [int(x) for x in (lengths.tolist() if isinstance(lengths, Tensor) else lengths)]
+        c = self.cache
+        assert len(n) == self.batch and all(0 <= x <= p for x, p in zip(n, c._len)), \
+            "lengths: one int per sequence, at most its cached length"
+        c.pos.copy_(torch.tensor(n, dtype=torch.int32))
+        c._len[:] = n
+
+    @torch.no_grad()
     def reset_slot(self, b: int) -> None:
         """Ragged sessions: empty slot ``b`` for a new request; the other sequences are untouched."""
         assert self.ragged, "slots need DecodeSession(..., ragged=True)"
@@ -612,12 +648,14 @@ class DecodeSession:
         return (hip(), *(kv or (c.k, c.v, c.pos)), self._cos, self._sin, self._cos.numel() > 0)
 
     def _forward_fast(self, ids: Tensor, prefill: bool, step: Tensor | None = None, last: Tensor | None = None,
-                      kv=None, cache: bool = False) -> Tensor:
+                      kv=None, cache: bool = False, all_logits: bool = False, advance: bool = True) -> Tensor:
         """``prefill``: flash attention inside the window (empty cache); ``cache``: ``cache_attn`` over the cache
         instead of ``decode_attn`` (a window of more than ``8 / G`` tokens); ``step``: device int32 advance per sequence instead of ``T``; ``last``: index of the token whose logits
         each sequence returns instead of ``T - 1`` (both only where the sequences differ); ``kv``: the (k, v, pos)
-        to run on -- one slot's views of the cache instead of the whole."""
-        if not prefill and ids.shape[1] == 1 and ids.shape[0] <= _GEMV_MAX_BATCH and self._gemv_fits(ids.shape[0]):
+        to run on -- one slot's views of the cache instead of the whole; ``all_logits``: the logits of every position,
+        ``[B * T, V]``, instead of the last one's; ``advance=False`` leaves the position where it was (a speculative
+        round sets it after the verification)."""
+        if not prefill and ids.shape[1] == 1 and not all_logits and ids.shape[0] <= _GEMV_MAX_BATCH and self._gemv_fits(ids.shape[0]):
             return self._decode_gemv(ids, step, kv)
         h, kc, vc, pos, cos, sin, use_rope = self._operands(kv)
         m = self.model
@@ -646,7 +684,9 @@ class DecodeSession:
             xr, h2, _ = h.add_rmsnorm_fwd(xr, g1, ln2, eps)
             a = h.swiglu_fwd(torch.matmul(h2, w13.t()))
             xd = torch.matmul(a, w2.t())
-        if T > 1 and last is not None:  # ragged: each sequence's own last valid token
+        if all_logits:
+            pass
+        elif T > 1 and last is not None:  # ragged: each sequence's own last valid token
             rows = torch.arange(B, device=last.device)
             xr = xr.view(B, T, -1)[rows, last].contiguous()
             xd = xd.view(B, T, -1)[rows, last].contiguous()
@@ -656,7 +696,8 @@ class DecodeSession:
         fin = m.ln_final
         _, hf, _ = h.add_rmsnorm_fwd(xr, xd, fin.weight, fin.eps)
         logits = torch.matmul(hf, m.lm_head.weight.t())
-        pos.add_(T if step is None else step)
+        if advance:
+            pos.add_(T if step is None else step)
         return logits
 
     def _gemv_fits(self, m: int) -> bool:
@@ -688,7 +729,7 @@ class DecodeSession:
         return logits
 
     # ------------------------------------------------------------------ oracle path
-    def _forward_reference(self, ids: Tensor, n: list[int], rows: list[int]) -> Tensor:
+    def _forward_reference(self, ids: Tensor, n: list[int], rows: list[int], all_logits: bool = False) -> Tensor:
         """Plain-PyTorch math over the same cache (any dtype / device / ablation): ``ids [len(rows), T]``
         (right-padded), of which the first ``n[i]`` tokens are appended to sequence ``rows[i]`` at its own position
         (RoPE positions and visibility per sequence; with one shared position they all agree).  Returns the logits
@@ -734,10 +775,246 @@ class DecodeSession:
             else:
                 x = x + attend(layer.ln1(x))
                 x = x + layer.ffn(layer.ln2(x))
-        last = torch.tensor([max(c - 1, 0) for c in n], device=dev)
-        logits = m.lm_head(m.ln_final(x[torch.arange(R, device=dev), last]))
+        if all_logits:  # every position's, [R, T, V]
+            logits = m.lm_head(m.ln_final(x))
+        else:
+            last = torch.tensor([max(c - 1, 0) for c in n], device=dev)
+            logits = m.lm_head(m.ln_final(x[torch.arange(R, device=dev), last]))
         if self.ragged:
             self.cache.pos[rows] += torch.tensor(n, dtype=torch.int32, device=dev)
         else:  # one shared position: every sequence took the whole window
             self.cache.pos.add_(T)
         return logits
+
+
+class SpeculativeSession:
+    """Speculative decoding with a draft model (Leviathan et al., ICML 2023; Chen et al., 2023): every round the
+    draft proposes ``num_draft_tokens`` tokens one decode step at a time, the target scores the whole window in one
+    pass, and ``ops.spec_verify_step`` (``ops/sampling.py`` states the function) keeps the drafts that stand and adds
+    one token of the target's own.  Greedy decoding emits exactly the target's tokens; temperature sampling emits
+    tokens distributed as the target's.  ``top_k`` / ``top_p`` are not supported with a draft model.
+
+    It owns two ragged :class:`DecodeSession` s.  At the start of a round both caches hold every emitted token but
+    the last, which sits in ``win[:, 0]`` (the target's window) and in the draft's ``ids``.  One round:
+
+    1. ``base = pos``;
+    2. K draft steps, each a decode step + ``sample_step(col=j)``, which writes draft ``j`` into ``win[:, j]``;
+    3. one more draft step that only feeds draft ``K`` into the draft cache (its logits are unused), so the draft
+       cache is whole when all K drafts stand;
+    4. the target's pass over ``win [B, K + 1]``, every position's logits (``decode_attn`` up to ``8 // G`` tokens,
+       ``cache_attn`` beyond), which leaves the target's position at ``base``;
+    5. ``spec_verify_step``: emits into ``out``, sets both positions to ``base + emitted``, puts the last emitted
+       token into ``win[:, 0]`` and ``ids``, finishes a row at EOS or at ``max_new_tokens``;
+    6. ``rng[1] += K + 1``.
+
+    On the fast path the round is captured once into one graph on one stream (no parallel branches) and replayed
+    with no host sync inside; the host reads ``done`` every ``sync_every`` rounds.  Off the fast path (CPU, fp32,
+    ablations) the same round runs eagerly on the oracle ops.  The random stream is Philox keyed by ``seed``: the
+    first token is the target's own draw at counter ``(0, row, stream 2)``, round ``r`` starts at ``c = 1 + r (K +
+    1)`` and draws draft ``j`` at ``(c + j - 1, row, stream 0)``, its accept test at ``(c + j - 1, row, stream 1)``
+    and the final token at ``(c, row, stream 2)``.
+    """
+
+    def __init__(self, target, draft, batch: int, num_draft_tokens: int = 4, max_len: int | None = None,
+                 use_graph: bool = True):
+        K = int(num_draft_tokens)
+        if K < 1:
+            raise ValueError("num_draft_tokens must be at least 1")
+        if target.config.vocab_size != draft.config.vocab_size:
+            raise ValueError(f"the draft's vocabulary ({draft.config.vocab_size}) is not the target's "
+                             f"({target.config.vocab_size})")
+        self.K = K
+        self.batch = batch
+        self.max_len = max_len or min(target.context_length, draft.context_length)
+        if self.max_len > min(target.context_length, draft.context_length):
+            raise ValueError("max_len exceeds the context length of the target or the draft")
+        self.target = DecodeSession(target, batch, self.max_len, use_graph, ragged=True)
+        self.draft = DecodeSession(draft, batch, self.max_len, use_graph, ragged=True)
+        self.device = dev = self.target.device
+        self.fast = self.target.fast and self.draft.fast
+        self.use_graph = use_graph and self.fast
+        t, d = self.target, self.draft
+        if self.fast:  # the target's window must be one pass over the layers (no position moves inside the round)
+            plan = _append_plan(K + 1, t.H // t.Hkv, True)
+            assert len(plan) == 1, plan
+            self._win_cache = plan[0][2] == "cache"
+        i32 = dict(dtype=torch.int32, device=dev)
+        self._st = {
+            "win": torch.zeros(batch, K + 1, dtype=torch.long, device=dev),
+            "ids": torch.zeros(batch, 1, dtype=torch.long, device=dev),
+            "out": torch.full((batch, self.max_len), -1, dtype=torch.long, device=dev),
+            "n_out": torch.zeros(batch, **i32), "base": torch.zeros(batch, **i32), "done": torch.zeros(batch, **i32),
+            # row j = (seed, c + j): the counters of draft j + 1, and row 0 the verifier's
+            "rngs": torch.zeros(K + 1, 2, dtype=torch.long, device=dev),
+            # a session off the fast path has no static step: the round's own
+            "step_t": t._step if t._step is not None else torch.ones(batch, **i32),
+            "step_d": d._step if d._step is not None else torch.ones(batch, **i32),
+        }
+        self._graph, self._key = None, None
+
+    # ------------------------------------------------------------------ one round
+    def _decode_draft(self) -> Tensor:
+        d, st = self.draft, self._st
+        if d.fast:
+            return d._forward_fast(st["ids"], prefill=False, step=st["step_d"])
+        rows = list(range(self.batch))
+        n = [int(x) for x in st["step_d"].tolist()]
+        logits = d._forward_reference(st["ids"], n, rows)
+        d.cache.advance(rows, n)
+        return logits
+
+    def _score_window(self) -> Tensor:
+        t, st = self.target, self._st
+        B, K = self.batch, self.K
+        if t.fast:
+            return t._forward_fast(st["win"], prefill=False, cache=self._win_cache, all_logits=True,
+                                   advance=False).view(B, K + 1, -1)
+        return t._forward_reference(st["win"], [0] * B, list(range(B)), all_logits=True)  # (0: no advance)
+
+    def _round(self, temperature: float, eos: int, out: Tensor) -> None:
+        from ..ops import sampling
+
+        st, K = self._st, self.K
+        st["base"].copy_(self.target.cache.pos)
+        kept = []
+        for j in range(1, K + 1):
+            logits = self._decode_draft()
+            sampling.sample_step(logits, temperature, 0, 1.0, st["rngs"][j - 1], st["ids"], st["win"], st["step_d"],
+                                 st["done"], -1, col=j)
+            if temperature > 0:
+                kept.append(logits)
+        self._decode_draft()
+        tl = self._score_window()
+        sl = torch.stack(kept, 1).to(tl.dtype) if kept else None  # the one gathering launch of a sampling round
+        sampling.spec_verify_step(tl, sl, temperature, st["rngs"][0], st["win"], st["ids"], out, st["n_out"],
+                                  st["base"], self.target.cache.pos, self.draft.cache.pos, st["step_t"], st["step_d"],
+                                  st["done"], eos)
+        st["rngs"][:, 1].add_(K + 1)
+
+    def _sync_mirrors(self) -> None:
+        for s in (self.target, self.draft):
+            s.cache._len[:] = [int(x) for x in s.cache.pos.tolist()]
+
+    def _capture(self, key) -> None:
+        """Capture one round for ``key = (temperature, eos, max_new_tokens)`` (baked into the graph), like
+        ``DecodeSession._capture``: a warm-up run on a side stream, then the capture, on benign state at position 0
+        (the caller initialises every buffer afterwards)."""
+        temperature, eos, n = key
+        out = self._st["out"][:, :n]
+        s = torch.cuda.Stream(device=self.device)
+        s.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(s):
+            self._round(temperature, eos, out)
+        torch.cuda.current_stream(self.device).wait_stream(s)
+        self._init_state(0)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._round(temperature, eos, out)
+        self._graph, self._key = g, key
+
+    def _init_state(self, seed: int) -> None:
+        st, K = self._st, self.K
+        self.target.reset()
+        self.draft.reset()
+        st["win"].zero_()
+        st["ids"].zero_()
+        st["out"].fill_(-1)
+        for k in ("n_out", "base", "done"):
+            st[k].zero_()
+        for k, s in (("step_t", self.target), ("step_d", self.draft)):
+            st[k].fill_(1)
+            s._step_host = [1] * self.batch
+        st["rngs"].copy_(torch.tensor([[seed, 1 + j] for j in range(K + 1)], dtype=torch.long))
+
+    # ------------------------------------------------------------------ public API
+    @torch.no_grad()
+    def generate(self, prompt, max_new_tokens: int, temperature: float = 1.0, eos_token_id: int | None = None,
+                 seed: int | None = None, generator: torch.Generator | None = None, sync_every: int = 4):
+        """``prompt [B, S]`` -> ``[B, S + n]``, or a list of ``B`` 1-D prompts -> a list of 1-D tensors, with the
+        shapes and EOS rules of :meth:`DecodeSession.generate`.  ``seed=None`` draws the Philox seed from
+        ``generator`` (else torch's default generator).  The host reads the ``done`` flags every ``sync_every``
+        rounds.  ``prompt + max_new_tokens + num_draft_tokens + 1 <= max_len`` is checked once, up front."""
+        from ..ops import sampling
+
+        t, d, st, K, B = self.target, self.draft, self._st, self.K, self.batch
+        as_list = isinstance(prompt, (list, tuple))
+        if as_list:
+            prompts, n, ids = t._pad_prompts(prompt)
+        else:
+            ids = prompt.to(self.device)
+            assert ids.dim() == 2 and ids.shape[0] == B, f"session batch is {B}"
+            n = [ids.shape[1]] * B
+        assert sync_every >= 1, "sync_every: a positive number of rounds"
+        if max(n) + max_new_tokens + K + 1 > self.max_len:
+            raise ValueError(f"KV cache full: prompt ({max(n)}) + max_new_tokens ({max_new_tokens}) + "
+                             f"num_draft_tokens + 1 ({K + 1}) exceeds max_len ({self.max_len})")
+        if max_new_tokens <= 0:
+            return prompts if as_list else ids
+        if seed is None:
+            gdev = generator.device if generator is not None else "cpu"
+            seed = int(torch.randint(0, 2**62, (1,), generator=generator, device=gdev))
+        eos = -1 if eos_token_id is None else int(eos_token_id)
+        # a tensor prompt's finished rows keep generating until every row has finished (DecodeSession.generate), so
+        # the kernel sees no EOS there and the host looks for it in `out` at each sync
+        key = (float(temperature), eos if as_list else -1, int(max_new_tokens))
+        self._init_state(seed)
+        if self.use_graph and self._key != key:
+            self._capture(key)
+            self._init_state(seed)
+        out = st["out"][:, :max_new_tokens]
+        # the first token is the target's own: prefill both, draw at Philox counter (0, row, stream 2)
+        logits = t.prefill(ids, n)
+        d.prefill(ids, n)
+        first = sampling.sample_logits(logits, temperature, 0, 1.0, sampling.philox_uniform(seed, 0, B, stream=2))
+        first = first.to(self.device)
+        out[:, 0] = first
+        st["win"][:, 0] = first
+        st["ids"][:, 0] = first
+        st["n_out"].fill_(1)
+        fin = torch.full_like(first, max_new_tokens <= 1, dtype=torch.bool)
+        if key[1] >= 0:
+            fin |= first == key[1]
+        st["done"].copy_(fin)
+        for k, s in (("step_t", t), ("step_d", d)):
+            st[k].copy_(~fin)
+            s._step_host = None  # the device owns the steps until the end
+        rounds = 0
+        while rounds < max_new_tokens - 1:
+            if rounds % sync_every == 0 and self._finished(as_list, eos, out):  # the only host sync of the loop
+                break
+            if self.use_graph:
+                self._graph.replay()
+            else:
+                self._round(*key[:2], out)
+                self._sync_mirrors()
+            rounds += 1
+        made = [int(x) for x in st["n_out"].tolist()]
+        res = out.cpu()
+        for s, k in ((t, "step_t"), (d, "step_d")):
+            s._step_host = [int(x) for x in st[k].tolist()]
+        if as_list:
+            # both caches hold every emitted token but the last; pos[b] already says so on the device
+            for s in (t, d):
+                s.cache._len[:] = [n[b] + made[b] - 1 for b in range(B)]
+            return [torch.cat([p, res[b, : made[b]].to(self.device, p.dtype)]) for b, p in enumerate(prompts)]
+        # tensor prompt: keep the tokens up to the one at which every row had emitted EOS, as DecodeSession does
+        keep = min(made)
+        if eos >= 0:
+            hit = res[:, :keep] == eos
+            if bool(hit.any(1).all()):
+                keep = min(keep, int(hit.int().argmax(1).max()) + 1)
+        for s in (t, d):
+            s.cache.pos.fill_(n[0] + keep - 1)
+            s.cache._len[:] = [n[0] + keep - 1] * B
+        return torch.cat([ids, res[:, :keep].to(self.device, ids.dtype)], 1)
+
+    def _finished(self, as_list: bool, eos: int, out: Tensor) -> bool:
+        st = self._st
+        if bool((st["done"] != 0).all()):
+            return True
+        if as_list or eos < 0:
+            return False
+        made = st["n_out"].tolist()
+        hit = out.cpu() == eos
+        first = [int(h[:m].int().argmax()) if bool(h[:m].any()) else -1 for h, m in zip(hit, made)]
+        return min(first) >= 0 and min(made) >= max(first) + 1

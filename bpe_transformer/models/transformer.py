@@ -10,6 +10,7 @@ their gradient.
 
 from __future__ import annotations
 
+import dataclasses
 
 import torch
 from torch import Tensor, nn
@@ -174,6 +175,41 @@ class TransformerLM(nn.Module):
         sd = {k.replace("_orig_mod.", ""): v for k, v in state_dict.items()}
         return self.load_state_dict(sd, strict=strict)
 
+    def truncated(self, n_layers: int) -> "TransformerLM":
+        """A draft model for speculative decoding made of this model's own weights: its embeddings, first
+        ``n_layers`` blocks, final norm and LM head, shared with this model (no weight is copied)."""
+        assert 1 <= n_layers <= len(self.layers), "n_layers: between 1 and the number of blocks"
+        m = TransformerLM.__new__(TransformerLM)
+        nn.Module.__init__(m)
+        m.config = dataclasses.replace(self.config, num_layers=n_layers)
+        m.context_length = self.context_length
+        m.token_embeddings = self.token_embeddings
+        m.layers = nn.ModuleList(list(self.layers[:n_layers]))
+        m.ln_final = self.ln_final
+        m.lm_head = self.lm_head
+        m.train(self.training)
+        return m
+
+    def _generate_speculative(self, prompt, max_new_tokens, temperature, top_p, eos_token_id, generator, top_k, seed,
+                              draft_model, num_draft_tokens):
+        from .generation import SpeculativeSession
+
+        if top_k or (top_p is not None and top_p < 1.0):
+            raise ValueError("top_k / top_p cannot be combined with draft_model: speculative verification needs "
+                             "the unwarped distributions of both models")
+        K = int(num_draft_tokens)
+        self._fence(self)
+        as_list = isinstance(prompt, (list, tuple))
+        squeeze = not as_list and prompt.dim() == 1
+        ids = list(prompt) if as_list else (prompt.unsqueeze(0) if squeeze else prompt)
+        longest = max(int(p.numel()) for p in ids) if as_list else ids.shape[1]
+        need = longest + max(max_new_tokens, 0) + K + 1
+        if need > min(self.context_length, draft_model.context_length):
+            raise ValueError(f"prompt + max_new_tokens + num_draft_tokens + 1 = {need} exceeds the context length")
+        sess = SpeculativeSession(self, draft_model, len(ids), K, max_len=need)
+        out = sess.generate(ids, max_new_tokens, temperature, eos_token_id, seed, generator)
+        return out[0] if squeeze else out
+
     @torch.no_grad()
     def generate(
         self,
@@ -187,6 +223,8 @@ class TransformerLM(nn.Module):
         top_k: int | None = None,
         sampler: str = "host",
         seed: int | None = None,
+        draft_model: "TransformerLM | None" = None,
+        num_draft_tokens: int = 4,
     ) -> Tensor:
         """Autoregressive sampling (temperature, top-k, nucleus).  ``prompt``: ``[S]`` or ``[B, S]``.
 
@@ -202,8 +240,17 @@ class TransformerLM(nn.Module):
         inside the captured decode graph, from a Philox stream keyed by ``seed`` (``None``: drawn from ``generator``,
         which is otherwise unused in this mode), and syncs with the host every few tokens instead of every token
         (:meth:`DecodeSession.generate`); it needs the KV-cache path.
+
+        ``draft_model`` turns on speculative decoding (:class:`~bpe_transformer.models.generation.SpeculativeSession`):
+        the draft proposes ``num_draft_tokens`` tokens per round and this model verifies them in one pass; greedy
+        output is this model's own, sampled output is distributed as this model's.  It implies the device sampler
+        and cannot be combined with ``top_k`` or ``top_p`` (``ValueError``).  :meth:`truncated` gives a draft
+        without a second checkpoint.
         """
         assert sampler in ("host", "device"), "sampler: 'host' or 'device'"
+        if draft_model is not None:
+            return self._generate_speculative(prompt, max_new_tokens, temperature, top_p, eos_token_id, generator,
+                                              top_k, seed, draft_model, num_draft_tokens)
         kw = dict(top_k=top_k, sampler=sampler, seed=seed)
         if isinstance(prompt, (list, tuple)):
             self._fence(self)

@@ -18,7 +18,7 @@ from .loss import IGNORE_INDEX, cross_entropy, lm_head_cross_entropy
 from .norm import rmsnorm
 from .optim import clip_grad_norm_, fused_adamw_step, grad_norm
 from .rope import apply_rope
-from .sampling import philox_uniform, sample_logits, sample_step
+from .sampling import philox_uniform, sample_logits, sample_step, spec_verify, spec_verify_step
 from .softmax import softmax
 
 __all__ = [
@@ -45,6 +45,8 @@ __all__ = [
     "rmsnorm",
     "sample_logits",
     "sample_step",
+    "spec_verify",
+    "spec_verify_step",
     "scaled_dot_product_attention",
     "silu",
     "softmax",

@@ -202,8 +202,47 @@ struct SampleArgs {
     int* step;  // optional (ragged sessions)
     int* done;
     int eos;    // < 0: none
+    int col;    // >= 0: the column of `out` that takes the token instead of `count`; an idle row then writes none
 };
 void launch_sample(const SampleArgs& a, int dtype, int B, hipStream_t s);
+
+// spec_verify.hip (speculative decoding: which draft tokens stand, and the token after them; ops/sampling.py states
+// the function).  One workgroup per sequence.  t [B][K + 1][V] target logits, s [B][K][V] draft logits (sampling
+// only), both dense rows of one dtype; draft[b * draft_ld + i] = draft token i + 1.  Uniforms: `ua` [B][K] and `us`
+// [B] given, or drawn from `rng` = (seed, c): accept i at Philox counter (c + i - 1, row, 1), the final draw at
+// (c, row, 2).  `res_n` / `res_y` [B] take (n, y) (spec_verify); with `n_out` set the in-graph epilogue runs instead
+// (spec_verify_step): a row that is done or whose step_t is 0 does nothing at all; otherwise the emitted tokens
+// d[1..n], y go to out[b][n_out[b]..] up to the first `eos` (inclusive) or the last column of `out`, n_out[b]
+// advances by their number m, the last of them goes to win[b][0] and ids[b], pos_t[b] = pos_d[b] = base[b] + m, and
+// a row that emitted `eos` or filled `out` sets done[b] and clears step_t[b], step_d[b].
+struct SpecArgs {
+    const void* t;
+    const void* s;  // nullptr: greedy
+    int V, K;
+    float temperature;  // <= 0: greedy
+    const long long* draft;
+    long draft_ld;
+    const float* ua;
+    const float* us;
+    const long long* rng;
+    int* res_n;
+    long long* res_y;
+    long long* out;
+    long out_ld;
+    int out_n;
+    int* n_out;
+    long long* win;
+    long win_ld;
+    long long* ids;
+    const int* base;
+    int* pos_t;
+    int* pos_d;
+    int* step_t;
+    int* step_d;
+    int* done;
+    int eos;  // < 0: none
+};
+void launch_spec_verify(const SpecArgs& a, int dtype, int B, hipStream_t s);
 
 size_t fa_fwd_lds_bytes(int D);
 size_t fa_bwd_lds_bytes(int D);

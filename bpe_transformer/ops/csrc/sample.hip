@@ -25,126 +25,19 @@
 // V * 2^-41 of the mass of the top token -- below the fp32 exp's own.  Histogram bins are replicated 32x, replica
 // = lane % 32, at address bin * 32 + replica: every lane of a half-wave lands in its own LDS bank whatever the bins
 // are, so equal logits (most of a row shares a few exponent bins) never serialise the atomics.
-#include "common.h"
-#include "kernels.h"
+//
+// The row addressing, Philox, the argmax, the order-independent sums and the index-order draw live in
+// sample_common.h, which spec_verify.hip shares.
+#include "sample_common.h"
 
 namespace bpe {
 namespace {
-
-typedef unsigned long long u64;
-
-constexpr int S_NT = 1024, S_NW = S_NT / 64, S_REP = 32, S_BINS = 256;
-constexpr float S_FIX = 1099511627776.f;  // 2^40
-
-// dynamic LDS layout (bytes)
-constexpr int L_CNT = 0;                                 // unsigned [256][32]
-constexpr int L_MASS = L_CNT + S_BINS * S_REP * 4;       // u64 [256][32]; the tile sums of a prefix search alias it
-constexpr int L_SEL = L_MASS + S_BINS * S_REP * 8;       // u64 [256] bins summed over replicas (count or mass)
-constexpr int L_CNTR = L_SEL + S_BINS * 8;               // unsigned [256]
-constexpr int L_SCAL = L_CNTR + S_BINS * 4;              // u64 [8] broadcast scalars
-constexpr int L_WRED = L_SCAL + 64;                      // unsigned [2][16] argmax partials
-constexpr int L_TOTAL = L_WRED + 2 * S_NW * 4;
-static_assert(SAMPLE_MAX_TILES * 8 <= S_BINS * S_REP * 8, "tile sums alias the mass histogram");
-
-template <typename T> struct RowT;
-template <> struct RowT<__bf16> {
-    static constexpr int VEC = 8, KB = 16;
-    typedef u16 raw_t;
-    static __device__ __forceinline__ unsigned key(unsigned h) {
-        if (h == 0x8000u) h = 0;  // -0 ranks with +0
-        return (h & 0x8000u) ? (~h & 0xFFFFu) : (h | 0x8000u);
-    }
-    static __device__ __forceinline__ float val(unsigned h) { return bf2f((u16)h); }
-    static __device__ __forceinline__ float key_val(unsigned k) {
-        return bf2f((u16)((k & 0x8000u) ? (k ^ 0x8000u) : (~k & 0xFFFFu)));
-    }
-};
-template <> struct RowT<float> {
-    static constexpr int VEC = 4, KB = 32;
-    typedef unsigned raw_t;
-    static __device__ __forceinline__ unsigned key(unsigned b) {
-        if (b == 0x80000000u) b = 0;
-        return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    }
-    static __device__ __forceinline__ float val(unsigned b) { return __uint_as_float(b); }
-    static __device__ __forceinline__ float key_val(unsigned k) {
-        return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-    }
-};
-
-__device__ __forceinline__ u64 wave_sum64(u64 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ u64 wave_scan64(u64 v, int lane) {  // inclusive
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u64 t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-
-// Philox4x32-10, first output word
-__device__ __forceinline__ unsigned philox_x0(unsigned k0, unsigned k1, unsigned c0, unsigned c1, unsigned c2,
-                                              unsigned c3) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const u64 p0 = (u64)0xD2511F53u * c0, p1 = (u64)0xCD9E8D57u * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1;
-        const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return c0;
-}
 
 // keep iff key > K, or key == K at an index <= I  (K = 0, I = V - 1: everything)
 struct Filt {
     unsigned K;
     int I;
     __device__ __forceinline__ bool has(unsigned key, int i) const { return key > K || (key == K && i <= I); }
-};
-
-template <typename T> struct Ctx {
-    typedef RowT<T> R;
-    const typename R::raw_t* p0;  // 16-byte aligned: row start minus off elements
-    int off, V, nvec, ntiles;
-    float xmax, invT;
-    char* smem;
-    int lane, wave;
-
-    // virtual vector v: raw bits of its elements and which of them are inside the row
-    __device__ __forceinline__ unsigned load(int v, unsigned (&raw)[R::VEC]) const {
-        const int j0 = v * R::VEC;
-        if (j0 >= off && j0 + R::VEC <= off + V) {
-            if constexpr (R::VEC == 8) {
-                const u16x8 t = *reinterpret_cast<const u16x8*>(p0 + j0);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) raw[e] = t[e];
-            } else {
-                typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-                const u32x4 t = *reinterpret_cast<const u32x4*>(p0 + j0);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) raw[e] = t[e];
-            }
-            return (1u << R::VEC) - 1;
-        }
-        unsigned m = 0;  // the unaligned head / the tail of the row: element by element, inside [0, V) only
-#pragma unroll
-        for (int e = 0; e < R::VEC; ++e) {
-            const int i = j0 + e - off;
-            raw[e] = 0;
-            if (i >= 0 && i < V) { raw[e] = p0[j0 + e]; m |= 1u << e; }
-        }
-        return m;
-    }
-    __device__ __forceinline__ u64 zq(unsigned raw) const {  // fixed-point weight of one logit
-        const float z = fminf(__expf((R::val(raw) - xmax) * invT), 1.f);
-        return (u64)(z * S_FIX);
-    }
-    __device__ __forceinline__ u64* scal() const { return reinterpret_cast<u64*>(smem + L_SCAL); }
 };
 
 // One radix select inside the filter `in`.  MASS = false: the k-th key in rank order (target = k, on counts).
@@ -250,84 +143,6 @@ __device__ void radix_select(const Ctx<T>& c, Filt in, u64 target, double top_p,
     if (r > n) r = n;
 }
 
-// Lowest index i at which the inclusive cumulative weight, in index order, exceeds the target; -1 when the total
-// weight is 0.  W(raw, key, i) -> u64 weight; TF(total) -> target (< total).
-template <typename T, typename WF, typename TF>
-__device__ int prefix_find(const Ctx<T>& c, WF weight, TF target_of) {
-    typedef RowT<T> R;
-    u64* tsum = reinterpret_cast<u64*>(c.smem + L_MASS);
-    u64* sc = c.scal();
-    for (int tile = c.wave; tile < c.ntiles; tile += S_NW) {
-        const int v = tile * 64 + c.lane;
-        u64 w = 0;
-        if (v < c.nvec) {
-            unsigned raw[R::VEC];
-            const unsigned m = c.load(v, raw);
-#pragma unroll
-            for (int e = 0; e < R::VEC; ++e)
-                if (m >> e & 1) w += weight(raw[e], R::key(raw[e]), v * R::VEC + e - c.off);
-        }
-        w = wave_sum64(w);
-        if (c.lane == 0) tsum[tile] = w;
-    }
-    __syncthreads();
-    if (c.wave == 0) {
-        // which tile: every lane sums a contiguous chunk of tiles
-        const int chunk = (c.ntiles + 63) / 64;
-        const int t0 = c.lane * chunk, t1 = min(t0 + chunk, c.ntiles);
-        u64 t = 0;
-        for (int i = t0; i < t1; ++i) t += tsum[i];
-        const u64 incl = wave_scan64(t, c.lane);
-        const u64 total = __shfl(incl, 63, 64);
-        int result = -1;
-        if (total > 0) {
-            const u64 target = target_of(total);
-            const u64 hit = __ballot(incl > target);
-            const int first = hit ? __ffsll((long long)hit) - 1 : 63;
-            u64 acc = incl - t;
-            int tile = t0;
-            if (c.lane == first) {
-                for (; tile < t1 - 1; ++tile) {
-                    if (acc + tsum[tile] > target) break;
-                    acc += tsum[tile];
-                }
-            }
-            tile = min(max(__shfl(tile, first, 64), 0), c.ntiles - 1);
-            const u64 resid = target - __shfl(acc, first, 64);
-            // which lane of that tile, then which element
-            const int v = tile * 64 + c.lane;
-            unsigned raw[R::VEC];
-            u64 w[R::VEC], ws = 0;
-            unsigned m = 0;
-            if (v < c.nvec) m = c.load(v, raw);
-#pragma unroll
-            for (int e = 0; e < R::VEC; ++e) {
-                w[e] = (m >> e & 1) ? weight(raw[e], R::key(raw[e]), v * R::VEC + e - c.off) : 0;
-                ws += w[e];
-            }
-            const u64 li = wave_scan64(ws, c.lane);
-            const u64 lhit = __ballot(li > resid);
-            // (a lane always passes: the tile's sum is the same integers added again)
-            const int lf = lhit ? __ffsll((long long)lhit) - 1 : 63;
-            int idx = -1;
-            if (c.lane == lf) {
-                u64 a = li - ws;
-#pragma unroll
-                for (int e = 0; e < R::VEC; ++e) {
-                    if (idx < 0 && w[e] > 0 && a + w[e] > resid) idx = v * R::VEC + e - c.off;
-                    a += w[e];
-                }
-            }
-            result = __shfl(idx, lf, 64);
-        }
-        if (c.lane == 0) sc[4] = (u64)(long long)result;
-    }
-    __syncthreads();
-    const int res = (int)(long long)sc[4];
-    __syncthreads();  // sc[4] and the tile sums are free again
-    return res;
-}
-
 // the index cutoff that keeps exactly the first r of the n tokens inside `in` with key == K
 template <typename T>
 __device__ Filt cut_ties(const Ctx<T>& c, Filt in, unsigned K, unsigned r, unsigned n) {
@@ -346,47 +161,13 @@ __global__ void __launch_bounds__(S_NT) sample_kernel(SampleArgs a) {
     typedef RowT<T> R;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int row = blockIdx.x;
-    const typename R::raw_t* xr = reinterpret_cast<const typename R::raw_t*>(a.logits) + (long)row * a.V;
     Ctx<T> c;
-    c.off = (int)((reinterpret_cast<uintptr_t>(xr) / sizeof(typename R::raw_t)) % R::VEC);
-    c.p0 = xr - c.off;
-    c.V = a.V;
-    c.nvec = (c.off + a.V + R::VEC - 1) / R::VEC;
-    c.ntiles = (c.nvec + 63) / 64;
-    c.smem = smem;
-    c.lane = threadIdx.x & 63;
-    c.wave = threadIdx.x >> 6;
+    c.init(a.logits, (long)row, a.V, smem);
 
     // ---- argmax: highest key, lowest index among equals
-    unsigned bk = 0;
-    int bi = 0;
-    for (int tile = c.wave; tile < c.ntiles; tile += S_NW) {
-        const int v = tile * 64 + c.lane;
-        if (v >= c.nvec) continue;
-        unsigned raw[R::VEC];
-        const unsigned m = c.load(v, raw);
-#pragma unroll
-        for (int e = 0; e < R::VEC; ++e) {
-            const unsigned key = R::key(raw[e]);
-            if ((m >> e & 1) && key > bk) { bk = key; bi = v * R::VEC + e - c.off; }  // (ascending i per thread)
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned ok = __shfl_xor(bk, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ok > bk || (ok == bk && oi < bi)) { bk = ok; bi = oi; }
-    }
-    unsigned* wred = reinterpret_cast<unsigned*>(smem + L_WRED);
-    if (c.lane == 0) { wred[c.wave] = bk; wred[S_NW + c.wave] = (unsigned)bi; }
-    __syncthreads();
-    bk = wred[0];
-    bi = (int)wred[S_NW];
-    for (int w = 1; w < S_NW; ++w) {
-        const unsigned ok = wred[w];
-        const int oi = (int)wred[S_NW + w];
-        if (ok > bk || (ok == bk && oi < bi)) { bk = ok; bi = oi; }
-    }
+    unsigned bk;
+    int bi;
+    row_argmax(c, bk, bi);
     int tok = bi;  // greedy, and what every degenerate row (all NaN, no mass) falls back to: always inside [0, V)
 
     // ---- the uniform: given, or Philox4x32-10 keyed by the seed at counter (count, row, 0)
@@ -395,9 +176,7 @@ __global__ void __launch_bounds__(S_NT) sample_kernel(SampleArgs a) {
     if (a.rng != nullptr) {
         const u64 seed = (u64)a.rng[0];
         count = a.rng[1];
-        const unsigned x0 = philox_x0((unsigned)seed, (unsigned)(seed >> 32), (unsigned)(u64)count,
-                                      (unsigned)((u64)count >> 32), (unsigned)row, 0u);
-        u = ((float)(x0 >> 8) + 0.5f) * 5.9604644775390625e-8f;  // 2^-24 (one rounding, of the sum)
+        u = philox_u(seed, (u64)count, (unsigned)row, 0u);
     } else if (a.u != nullptr) {
         u = a.u[row];
     }
@@ -417,10 +196,7 @@ __global__ void __launch_bounds__(S_NT) sample_kernel(SampleArgs a) {
         }
         const int i = prefix_find(
             c, [&](unsigned raw, unsigned key, int i) -> u64 { return f.has(key, i) ? c.zq(raw) : 0; },
-            [&](u64 M) -> u64 {
-                const u64 t = (u64)((double)u * (double)M);
-                return t < M ? t : M - 1;  // u >= 1 (or its product rounding up to M): the last token with mass
-            });
+            [&](u64 M) -> u64 { return draw_target(u, M); });
         if (i >= 0 && i < a.V) tok = i;
     }
 
@@ -429,7 +205,11 @@ __global__ void __launch_bounds__(S_NT) sample_kernel(SampleArgs a) {
         if (a.ids != nullptr) {
             const bool idle = a.done[row] != 0 || (a.step != nullptr && a.step[row] == 0);
             a.ids[row] = tok;
-            if (count >= 0 && count < a.out_n) a.out[(long)row * a.out_ld + count] = idle ? -1 : (long long)tok;
+            if (a.col >= 0) {  // a named column (a speculative window): an idle row leaves it as it is
+                if (a.col < a.out_n && !idle) a.out[(long)row * a.out_ld + a.col] = (long long)tok;
+            } else if (count >= 0 && count < a.out_n) {
+                a.out[(long)row * a.out_ld + count] = idle ? -1 : (long long)tok;
+            }
             if (!idle && a.eos >= 0 && tok == a.eos) {
                 a.done[row] = 1;
                 if (a.step != nullptr) a.step[row] = 0;

@@ -1180,6 +1180,7 @@ SampleArgs sample_setup(const at::Tensor& logits, double temperature, int64_t to
     a.top_k = (int)std::min<int64_t>(top_k, logits.size(1));
     a.top_p = top_p;
     a.eos = -1;
+    a.col = -1;
     return a;
 }
 
@@ -1200,7 +1201,8 @@ at::Tensor sample_logits(const at::Tensor& logits, double temperature, int64_t t
 
 // the in-graph form: the uniform from rng = (seed, count), the token into ids / out[:, count], EOS into done / step
 void sample_step(const at::Tensor& logits, double temperature, int64_t top_k, double top_p, const at::Tensor& rng,
-                 at::Tensor ids, at::Tensor out, const c10::optional<at::Tensor>& step, at::Tensor done, int64_t eos) {
+                 at::Tensor ids, at::Tensor out, const c10::optional<at::Tensor>& step, at::Tensor done, int64_t eos,
+                 int64_t col) {
     SampleArgs a = sample_setup(logits, temperature, top_k, top_p);
     const int64_t B = logits.size(0);
     TORCH_CHECK(rng.is_cuda() && rng.scalar_type() == at::kLong && rng.is_contiguous() && rng.numel() == 2,
@@ -1224,7 +1226,110 @@ void sample_step(const at::Tensor& logits, double temperature, int64_t top_k, do
     a.step = step.has_value() ? step->data_ptr<int>() : nullptr;
     a.done = done.data_ptr<int>();
     a.eos = eos < 0 ? -1 : (int)eos;
+    a.col = col < 0 ? -1 : (int)std::min<int64_t>(col, INT32_MAX);
     launch_sample(a, dt_code(logits), (int)B, cur_stream());
+}
+
+// ---------------------------------------------------------------- speculative verification (spec_verify.hip)
+// dense rows: [B, R, V] whose rows follow each other V elements apart, from any element offset
+bool spec_dense(const at::Tensor& x) {
+    return x.dim() == 3 && (x.size(2) == 1 || x.stride(2) == 1) && (x.size(1) == 1 || x.stride(1) == x.size(2)) &&
+           (x.size(0) == 1 || x.stride(0) == x.size(1) * x.size(2));
+}
+bool spec_i32(const at::Tensor& x, int64_t B) {
+    return x.is_cuda() && x.scalar_type() == at::kInt && x.is_contiguous() && x.numel() == B;
+}
+
+SpecArgs spec_setup(const at::Tensor& t, const c10::optional<at::Tensor>& s, double temperature, int64_t K) {
+    check_cuda(t, "target_logits");
+    TORCH_CHECK(K >= 1 && spec_dense(t) && t.size(1) == K + 1, "spec_verify: target_logits must be dense [B, K + 1, V]");
+    TORCH_CHECK(t.size(2) >= 1 && t.size(2) <= SAMPLE_MAX_V, "spec_verify: 1 <= V <= ", SAMPLE_MAX_V);
+    TORCH_CHECK(t.scalar_type() == at::kBFloat16 || t.scalar_type() == at::kFloat, "spec_verify: bf16 or fp32 logits");
+    TORCH_CHECK(t.numel() < ((int64_t)1 << 40), "spec_verify: logits too large");
+    SpecArgs a{};
+    a.t = t.data_ptr();
+    a.V = (int)t.size(2);
+    a.K = (int)K;
+    a.temperature = (float)temperature;
+    a.eos = -1;
+    if (temperature > 0) {
+        TORCH_CHECK(s.has_value(), "spec_verify: sampling (temperature > 0) needs the draft logits");
+        TORCH_CHECK(s->is_cuda() && s->get_device() == t.get_device() && s->scalar_type() == t.scalar_type() &&
+                        spec_dense(*s) && s->size(0) == t.size(0) && s->size(1) == K && s->size(2) == t.size(2),
+                    "spec_verify: draft_logits must be dense [B, K, V] of the target's dtype and device");
+        a.s = s->data_ptr();
+    }
+    return a;
+}
+
+// the stateless core: (n, y) per sequence for the given uniforms
+std::tuple<at::Tensor, at::Tensor> spec_verify(const at::Tensor& t, const at::Tensor& draft,
+                                               const c10::optional<at::Tensor>& s, double temperature,
+                                               const c10::optional<at::Tensor>& ua,
+                                               const c10::optional<at::Tensor>& us) {
+    TORCH_CHECK(draft.dim() == 2, "spec_verify: draft_tokens must be [B, K]");
+    const int64_t B = t.size(0), K = draft.size(1);
+    SpecArgs a = spec_setup(t, s, temperature, K);
+    TORCH_CHECK(draft.is_cuda() && draft.scalar_type() == at::kLong && draft.is_contiguous() && draft.size(0) == B,
+                "spec_verify: draft_tokens must be a contiguous int64 GPU tensor [B, K]");
+    if (temperature > 0) {
+        TORCH_CHECK(ua.has_value() && ua->is_cuda() && ua->scalar_type() == at::kFloat && ua->is_contiguous() &&
+                        ua->numel() == B * K, "spec_verify: ua must be a contiguous fp32 GPU tensor [B, K]");
+        TORCH_CHECK(us.has_value() && us->is_cuda() && us->scalar_type() == at::kFloat && us->is_contiguous() &&
+                        us->numel() == B, "spec_verify: us must be a contiguous fp32 GPU tensor [B]");
+        a.ua = ua->data_ptr<float>();
+        a.us = us->data_ptr<float>();
+    }
+    DevGuard g(t.device());
+    auto n = at::empty({B}, t.options().dtype(at::kInt));
+    auto y = at::empty({B}, t.options().dtype(at::kLong));
+    a.draft = (const long long*)draft.data_ptr<int64_t>();
+    a.draft_ld = K;
+    a.res_n = n.data_ptr<int>();
+    a.res_y = (long long*)y.data_ptr<int64_t>();
+    launch_spec_verify(a, dt_code(t), (int)B, cur_stream());
+    return {n, y};
+}
+
+// the in-graph form: uniforms from rng = (seed, c), draft tokens in win[:, 1:], state as kernels.h describes
+void spec_verify_step(const at::Tensor& t, const c10::optional<at::Tensor>& s, double temperature,
+                      const at::Tensor& rng, at::Tensor win, at::Tensor ids, at::Tensor out, at::Tensor n_out,
+                      const at::Tensor& base, at::Tensor pos_t, at::Tensor pos_d, at::Tensor step_t, at::Tensor step_d,
+                      at::Tensor done, int64_t eos) {
+    TORCH_CHECK(win.dim() == 2 && win.size(1) >= 2, "spec_verify_step: win must be [B, K + 1]");
+    const int64_t B = t.size(0), K = win.size(1) - 1;
+    SpecArgs a = spec_setup(t, s, temperature, K);
+    TORCH_CHECK(rng.is_cuda() && rng.scalar_type() == at::kLong && rng.is_contiguous() && rng.numel() == 2,
+                "spec_verify_step: rng must be a contiguous int64 GPU tensor (seed, count)");
+    TORCH_CHECK(win.is_cuda() && win.scalar_type() == at::kLong && win.size(0) == B && win.stride(1) == 1,
+                "spec_verify_step: win must be an int64 GPU tensor [B, K + 1], rows dense");
+    TORCH_CHECK(ids.is_cuda() && ids.scalar_type() == at::kLong && ids.is_contiguous() && ids.numel() == B,
+                "spec_verify_step: ids must be a contiguous int64 GPU tensor [B, 1]");
+    TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kLong && out.dim() == 2 && out.size(0) == B &&
+                    (out.size(1) <= 1 || out.stride(1) == 1), "spec_verify_step: out must be int64 [B, N], rows dense");
+    TORCH_CHECK(spec_i32(n_out, B) && spec_i32(base, B) && spec_i32(pos_t, B) && spec_i32(pos_d, B) &&
+                    spec_i32(step_t, B) && spec_i32(step_d, B) && spec_i32(done, B),
+                "spec_verify_step: n_out, base, pos, step and done must be contiguous int32 GPU tensors [B]");
+    TORCH_CHECK(eos < t.size(2), "spec_verify_step: eos outside the vocabulary");
+    DevGuard g(t.device());
+    a.rng = (const long long*)rng.data_ptr<int64_t>();
+    a.win = (long long*)win.data_ptr<int64_t>();
+    a.win_ld = win.stride(0);
+    a.draft = a.win + 1;
+    a.draft_ld = win.stride(0);
+    a.ids = (long long*)ids.data_ptr<int64_t>();
+    a.out = (long long*)out.data_ptr<int64_t>();
+    a.out_ld = out.stride(0);
+    a.out_n = (int)out.size(1);
+    a.n_out = n_out.data_ptr<int>();
+    a.base = base.data_ptr<int>();
+    a.pos_t = pos_t.data_ptr<int>();
+    a.pos_d = pos_d.data_ptr<int>();
+    a.step_t = step_t.data_ptr<int>();
+    a.step_d = step_d.data_ptr<int>();
+    a.done = done.data_ptr<int>();
+    a.eos = eos < 0 ? -1 : (int)eos;
+    launch_spec_verify(a, dt_code(t), (int)B, cur_stream());
 }
 
 }  // namespace
@@ -1232,7 +1337,12 @@ void sample_step(const at::Tensor& logits, double temperature, int64_t top_k, do
 TORCH_LIBRARY(bpe_hip, m) {
     m.def("sample_logits(Tensor logits, float temperature, int top_k, float top_p, Tensor u) -> Tensor");
     m.def("sample_step(Tensor logits, float temperature, int top_k, float top_p, Tensor rng, Tensor(a!) ids, "
-          "Tensor(b!) out, Tensor(c!)? step, Tensor(d!) done, int eos) -> ()");
+          "Tensor(b!) out, Tensor(c!)? step, Tensor(d!) done, int eos, int col=-1) -> ()");
+    m.def("spec_verify(Tensor target_logits, Tensor draft_tokens, Tensor? draft_logits, float temperature, "
+          "Tensor? ua, Tensor? us) -> (Tensor, Tensor)");
+    m.def("spec_verify_step(Tensor target_logits, Tensor? draft_logits, float temperature, Tensor rng, "
+          "Tensor(a!) win, Tensor(b!) ids, Tensor(c!) out, Tensor(d!) n_out, Tensor base, Tensor(e!) pos_t, "
+          "Tensor(f!) pos_d, Tensor(g!) step_t, Tensor(h!) step_d, Tensor(i!) done, int eos) -> ()");
     m.def("decode_gemv(Tensor x, Tensor? xd, Tensor? ln, float eps, Tensor w, int epi) -> (Tensor, Tensor)");
     m.def("decode_qkv(Tensor x, Tensor? xd, Tensor? ln, float eps, Tensor w, Tensor(a!) k_cache, "
           "Tensor(b!) v_cache, Tensor cos, Tensor sin, Tensor pos, int H, bool rope) -> (Tensor, Tensor)");
@@ -1353,4 +1463,6 @@ TORCH_LIBRARY_IMPL(bpe_hip, CUDA, m) {
     m.impl("decode_attn_proj", &decode_attn_proj);
     m.impl("sample_logits", &sample_logits);
     m.impl("sample_step", &sample_step);
+    m.impl("spec_verify", &spec_verify);
+    m.impl("spec_verify_step", &spec_verify_step);
 }

@@ -21,6 +21,42 @@ captured decode graph: it draws ``u`` itself -- Philox4x32-10, key ``seed``, cou
 On the GPU both run the HIP kernel (fp32 ``exp``, masses summed in 2^-40 fixed point); on the CPU the
 ``*_reference`` functions below compute the same function in torch with fp64 masses and Philox in integer
 arithmetic, so ``sampler="device"`` means the same thing on either device.
+
+**Speculative verification** (``csrc/spec_verify.hip``; the rejection scheme of Leviathan et al., "Fast Inference
+from Transformers via Speculative Decoding", ICML 2023, and Chen et al., "Accelerating Large Language Model Decoding
+with Speculative Sampling", 2023).  Per sequence, with target logits ``t[0..K]`` (each ``[V]``; ``t[i-1]`` is the
+target's row for the position of draft ``i``), draft tokens ``d[1..K]`` and, for sampling, draft logits ``s[1..K]``,
+a temperature ``T`` and uniforms ``ua[1..K]`` and ``us``:
+
+Greedy (``T <= 0``):
+
+1. ``n`` is the number of leading ``i`` with ``d[i] == argmax t[i-1]``, lowest index on ties.
+2. ``y = argmax t[n]``.
+
+Sampling (``T > 0``):
+
+1. ``p_i = softmax(t[i-1] / T)`` and ``q_i = softmax(s[i] / T)``; a ``-inf`` logit has mass 0.
+2. Draft ``i`` is accepted iff ``ua[i] * q_i(d[i]) < p_i(d[i])``.
+3. ``n`` is the number accepted before the first rejection.
+4. If ``n < K``, ``y`` is drawn from ``r = max(p_{n+1} - q_{n+1}, 0)``: the lowest index whose inclusive cumulative
+   ``r``, in index order, exceeds ``us * R`` with ``R = sum r``; if rounding finds none, the last index with
+   ``r > 0``; if ``R == 0``, from ``p_{n+1}`` in the same way.
+5. If ``n == K``, ``y`` is drawn the same way from ``p_{K+1}``.
+
+The result is ``(n, y)``; the emitted tokens are ``d[1..n], y``.  For greedy decoding they are exactly the target's
+own; for sampling ``d[i] ~ q_i`` makes them distributed as the target's.  ``top_k`` / ``top_p`` are not part of
+this function: the warped ``p`` and ``q`` would both need the radix-select cut, so a draft model cannot be combined
+with either.
+
+:func:`spec_verify` is that function for given uniforms.  :func:`spec_verify_step` is the form inside the captured
+graph of a speculative round.  With ``rng = (seed, c)`` it draws ``ua[i]`` with Philox at counter
+``(c + i - 1, row, 1)`` and ``us`` at ``(c, row, 2)`` -- the fourth counter word is the *stream*; stream 0 stays
+``sample_step``'s -- and per active row writes the emitted tokens into ``out[b, n_out[b] ..]``, advances
+``n_out[b]`` by their number ``m``, puts the last of them into ``win[b, 0]`` (the next round's first target token)
+and the draft's ``ids[b, 0]``, and sets ``pos_target[b] = pos_draft[b] = base[b] + m``: both caches then hold every
+emitted token but the last.  Emission stops, inclusive, at the first ``eos`` or at the last column of ``out``;
+either sets ``done[b]`` and clears the row's ``step`` in both sessions (without them ``m = n + 1``).  A row with
+``done`` set or ``step == 0`` writes nothing.  ``rng`` is read only.
 """
 
 from __future__ import annotations
@@ -44,11 +80,12 @@ def philox4x32(key: tuple[int, int], counter: tuple[int, int, int, int], rounds:
     return c0, c1, c2, c3
 
 
-def philox_uniform(seed: int, count: int, B: int, device=None) -> Tensor:
-    """The uniforms :func:`sample_step` draws for rows ``0 .. B-1`` at ``rng = (seed, count)``: fp32 ``[B]``."""
+def philox_uniform(seed: int, count: int, B: int, device=None, stream: int = 0) -> Tensor:
+    """The uniforms :func:`sample_step` draws for rows ``0 .. B-1`` at ``rng = (seed, count)``: fp32 ``[B]``.
+    ``stream`` is the fourth counter word (1, 2: the accept tests and the final draw of :func:`spec_verify_step`)."""
     seed, count = int(seed) & (2**64 - 1), int(count) & (2**64 - 1)
     key = (seed & _M32, seed >> 32)
-    x0 = [philox4x32(key, (count & _M32, count >> 32, b, 0))[0] for b in range(B)]
+    x0 = [philox4x32(key, (count & _M32, count >> 32, b, int(stream)))[0] for b in range(B)]
     u = (torch.tensor([x >> 8 for x in x0], dtype=torch.float64) + 0.5) * 2.0**-24
     return u.to(torch.float32).to(device)
 
@@ -95,22 +132,26 @@ def sample_logits_reference(logits: Tensor, temperature: float, top_k: int, top_
 
 
 def sample_step(logits: Tensor, temperature: float, top_k: int, top_p: float, rng: Tensor, ids: Tensor, out: Tensor,
-                step: Tensor | None, done: Tensor, eos: int) -> None:
+                step: Tensor | None, done: Tensor, eos: int, col: int = -1) -> None:
     """Sample one token per row in place, for a decode loop that never leaves the device.
 
     ``rng`` int64 ``[2]`` = (seed, count), read only; ``ids`` int64 ``[B, 1]`` takes the token; ``out`` int64
     ``[B, N]`` takes it in column ``count``, or ``-1`` if the row is already done (``done[b] != 0``) or inactive
     (``step[b] == 0``); ``done`` int32 ``[B]`` is set where an active row draws ``eos`` (``eos < 0``: none), and a
-    ragged session's ``step`` int32 ``[B]`` is cleared there, so that sequence stops advancing."""
+    ragged session's ``step`` int32 ``[B]`` is cleared there, so that sequence stops advancing.
+
+    ``col >= 0`` names the column of ``out`` that takes the token instead of ``count`` (a draft model writes draft
+    ``j`` straight into the target's window, ``win[:, j]``); a done or inactive row then leaves that column as it is,
+    so a window only ever holds tokens."""
     _check(logits, temperature, top_k, top_p)
     if logits.is_cuda:
         ops().sample_step(logits.contiguous(), float(temperature), int(top_k), float(top_p), rng, ids, out, step, done,
-                          int(eos))
+                          int(eos), int(col))
         return
-    sample_step_reference(logits, temperature, top_k, top_p, rng, ids, out, step, done, eos)
+    sample_step_reference(logits, temperature, top_k, top_p, rng, ids, out, step, done, eos, col)
 
 
-def sample_step_reference(logits, temperature, top_k, top_p, rng, ids, out, step, done, eos) -> None:
+def sample_step_reference(logits, temperature, top_k, top_p, rng, ids, out, step, done, eos, col: int = -1) -> None:
     B = logits.shape[0]
     seed, count = (int(v) for v in rng.tolist())
     tok = sample_logits_reference(logits, temperature, top_k, top_p, philox_uniform(seed, count, B, logits.device))
@@ -118,10 +159,141 @@ def sample_step_reference(logits, temperature, top_k, top_p, rng, ids, out, step
     if step is not None:
         idle = idle | (step == 0)
     ids.view(-1).copy_(tok)
-    if 0 <= count < out.shape[1]:
+    if col >= 0:
+        if col < out.shape[1]:
+            out[:, col] = torch.where(idle, out[:, col], tok)
+    elif 0 <= count < out.shape[1]:
         out[:, count] = torch.where(idle, torch.full_like(tok, -1), tok)
     if eos >= 0:
         hit = ~idle & (tok == eos)
         done[hit] = 1
         if step is not None:
             step[hit] = 0
+
+
+# ---------------------------------------------------------------- speculative verification
+def _check_spec(target_logits: Tensor, draft_tokens: Tensor, draft_logits: Tensor | None, temperature: float) -> None:
+    assert target_logits.dim() == 3 and draft_tokens.dim() == 2, "target_logits [B, K + 1, V], draft_tokens [B, K]"
+    B, K1, V = target_logits.shape
+    assert K1 >= 2 and V >= 1 and tuple(draft_tokens.shape) == (B, K1 - 1), "target_logits [B, K + 1, V], K >= 1"
+    assert target_logits.dtype in (torch.bfloat16, torch.float32), "logits: bf16 or fp32"
+    if temperature > 0:
+        assert draft_logits is not None and tuple(draft_logits.shape) == (B, K1 - 1, V) \
+            and draft_logits.dtype == target_logits.dtype, "sampling needs draft_logits [B, K, V] of the target's dtype"
+
+
+def spec_verify(target_logits: Tensor, draft_tokens: Tensor, draft_logits: Tensor | None, temperature: float,
+                ua: Tensor | None = None, us: Tensor | None = None) -> tuple[Tensor, Tensor]:
+    """``(n [B] int32, y [B] int64)`` of the module docstring for ``target_logits [B, K + 1, V]``, ``draft_tokens
+    [B, K]``, ``draft_logits [B, K, V]`` (``None`` for greedy) and the uniforms ``ua [B, K]``, ``us [B]`` (unused
+    for greedy)."""
+    _check_spec(target_logits, draft_tokens, draft_logits, temperature)
+    if not target_logits.is_cuda:
+        return spec_verify_reference(target_logits, draft_tokens, draft_logits, temperature, ua, us)
+    dev = target_logits.device
+    if temperature > 0:
+        ua, us = ua.to(dev, torch.float32).contiguous(), us.to(dev, torch.float32).contiguous()
+        draft_logits = draft_logits.contiguous()
+    else:
+        ua = us = draft_logits = None
+    return ops().spec_verify(target_logits.contiguous(), draft_tokens.to(dev, torch.long).contiguous(), draft_logits,
+                             float(temperature), ua, us)
+
+
+def _inv_cdf(w: Tensor, u: float) -> int:
+    """Lowest index whose inclusive cumulative ``w`` (fp64, index order) exceeds ``u * sum w``; if rounding finds
+    none, the last index with ``w > 0``; ``-1`` when there is no mass."""
+    cum = w.cumsum(0)
+    if not float(cum[-1]) > 0:
+        return -1
+    hit = ((cum > u * cum[-1]) & (w > 0)).nonzero()
+    return int(hit[0]) if hit.numel() else int((w > 0).nonzero()[-1])
+
+
+def _argmax_low(x: Tensor) -> int:
+    return int((x == x.max()).nonzero()[0])
+
+
+def spec_verify_reference(target_logits, draft_tokens, draft_logits, temperature, ua=None, us=None):
+    """The verification function in torch, fp64 masses, one sequence at a time."""
+    t = target_logits.double()
+    B, K1, V = t.shape
+    K = K1 - 1
+    ns, ys = [], []
+    for b in range(B):
+        d = [int(v) for v in draft_tokens[b].tolist()]
+        if temperature <= 0:
+            n = 0
+            while n < K and d[n] == _argmax_low(t[b, n]):
+                n += 1
+            ns.append(n)
+            ys.append(_argmax_low(t[b, n]))
+            continue
+        soft = lambda x: torch.softmax(x / float(temperature), -1)  # noqa: E731  (exp(-inf) = 0)
+        s = draft_logits[b].double()
+        n, r = 0, None
+        while n < K:
+            p, q = soft(t[b, n]), soft(s[n])
+            ok = 0 <= d[n] < V and float(ua[b, n]) * float(q[d[n]]) < float(p[d[n]])
+            if not ok:
+                r = (p - q).clamp_(min=0)
+                break
+            n += 1
+        u = float(us[b])
+        y = _inv_cdf(r, u) if r is not None else -1
+        if y < 0:
+            y = _inv_cdf(soft(t[b, n]), u)
+        ns.append(n)
+        ys.append(y if y >= 0 else _argmax_low(t[b, n]))
+    dev = target_logits.device
+    return torch.tensor(ns, dtype=torch.int32, device=dev), torch.tensor(ys, dtype=torch.long, device=dev)
+
+
+def spec_verify_step(target_logits: Tensor, draft_logits: Tensor | None, temperature: float, rng: Tensor, win: Tensor,
+                     ids: Tensor, out: Tensor, n_out: Tensor, base: Tensor, pos_target: Tensor, pos_draft: Tensor,
+                     step_target: Tensor, step_draft: Tensor, done: Tensor, eos: int) -> None:
+    """Verify one speculative round in place (module docstring): ``win`` int64 ``[B, K + 1]`` holds the last
+    emitted token and the K drafts, ``rng`` int64 ``[2]`` = (seed, c) is read only; ``ids`` int64 ``[B, 1]``, ``out``
+    int64 ``[B, N]``, ``n_out`` / ``base`` / ``pos_*`` / ``step_*`` / ``done`` int32 ``[B]``; ``eos < 0``: none."""
+    _check_spec(target_logits, win[:, 1:], draft_logits, temperature)
+    if target_logits.is_cuda:
+        ops().spec_verify_step(target_logits.contiguous(),
+                               draft_logits.contiguous() if temperature > 0 else None, float(temperature), rng, win,
+                               ids, out, n_out, base, pos_target, pos_draft, step_target, step_draft, done, int(eos))
+        return
+    spec_verify_step_reference(target_logits, draft_logits, temperature, rng, win, ids, out, n_out, base, pos_target,
+                               pos_draft, step_target, step_draft, done, eos)
+
+
+def spec_verify_step_reference(target_logits, draft_logits, temperature, rng, win, ids, out, n_out, base, pos_target,
+                               pos_draft, step_target, step_draft, done, eos) -> None:
+    B, K = win.shape[0], win.shape[1] - 1
+    seed, c = (int(v) for v in rng.tolist())
+    dev = target_logits.device
+    ua = us = None
+    if temperature > 0:
+        ua = torch.stack([philox_uniform(seed, c + i, B, dev, stream=1) for i in range(K)], 1)
+        us = philox_uniform(seed, c, B, dev, stream=2)
+    ns, ys = spec_verify_reference(target_logits, win[:, 1:], draft_logits, temperature, ua, us)
+    N = out.shape[1]
+    for b in range(B):
+        if int(done[b]) != 0 or int(step_target[b]) == 0:
+            continue
+        n, o = int(ns[b]), int(n_out[b])
+        toks = [int(v) for v in win[b, 1 : 1 + n].tolist()] + [int(ys[b])]
+        m, fin = 0, False
+        for tok in toks:
+            if o + m >= N or fin:
+                break
+            out[b, o + m] = tok
+            m += 1
+            fin = eos >= 0 and tok == eos
+        fin = fin or o + m >= N
+        n_out[b] = o + m
+        if m:
+            win[b, 0] = ids[b, 0] = toks[m - 1]
+            pos_target[b] = pos_draft[b] = int(base[b]) + m
+        if fin:
+            done[b] = 1
+            step_target[b] = 0
+            step_draft[b] = 0

@@ -5,9 +5,15 @@ For each batch size: prefill a prompt, then time ``--tokens`` decode steps (HIP-
 bandwidth of the K/V read).  ``--recompute`` also times the cache-less baseline (full prefix re-run per token).
 ``--ragged`` adds the same loop on a ragged session (one cache position per sequence) whose prompt lengths are
 spread over ``[prompt / 4, prompt]`` with a fixed seed: ms/step and tok/s beside the uniform figures.
+``--kv-dtype fp8`` adds, to every line, the fp8-cache session (``DecodeSession(kv_dtype="fp8")``) against the bf16
+one in the same process, alternating over ``--rounds`` rounds (median and min of each), both caches' bytes and the
+fp8 attention kernel alone.  ``--long-context`` replaces the model by the regime the fp8 cache is for: a Llama-shaped
+model cut to ``--layers`` layers (d 2048, 32 query / 4 KV heads, D 64), ``max_len`` 4096 and a prompt that nearly
+fills it (``4096 - tokens - 2``), batch 64 by default.
 Random-init weights, synthetic prompts; one JSON line per configuration.
 
     python benchmarks/decode_bench.py --model gpt2-small --batch 1 8 64 --prompt 128 --tokens 256
+    python benchmarks/decode_bench.py --kv-dtype fp8 --long-context --batch 64 --tokens 64
 """
 import argparse
 import json
@@ -33,6 +39,44 @@ def time_decode(sess, ids, prompt_len, tokens):
         sess.decode(nxt)
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / tokens
+
+
+def time_attn(fn, n=50):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(n):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n / 1e3
+
+
+def fp8_arm(model, sess, ids, prompt, tokens, rounds, graph, chunk):
+    """bf16 and fp8 sessions alternating in this process -> the extra fields of the JSON line."""
+    B = ids.shape[0]
+    f8 = DecodeSession(model, B, max_len=sess.max_len, use_graph=graph, kv_dtype="fp8", prefill_chunk=chunk)
+    t = {"bf16": [], "fp8": []}
+    for _ in range(rounds):
+        t["bf16"].append(time_decode(sess, ids, prompt, tokens))
+        t["fp8"].append(time_decode(f8, ids, prompt, tokens))
+    L = f8.length
+    q = torch.randn(B, f8.H * f8.D, device="cuda", dtype=torch.bfloat16)
+    pos = torch.tensor([L - 1], dtype=torch.int32, device="cuda")
+    c = f8.cache
+    t_attn = time_attn(lambda: dec.decode_attention_fp8(q, c.k[0], c.v[0], c.k_scale[0], c.v_scale[0], pos, f8.H))
+    kv_bytes = 2 * B * f8.Hkv * L * (f8.D + 4)
+    med = lambda x: sorted(x)[len(x) // 2]  # noqa: E731
+    return {
+        "kv_rounds": rounds,
+        "bf16_decode_ms_per_step_median_min": [round(med(t["bf16"]) * 1e3, 4), round(min(t["bf16"]) * 1e3, 4)],
+        "fp8_decode_ms_per_step_median_min": [round(med(t["fp8"]) * 1e3, 4), round(min(t["fp8"]) * 1e3, 4)],
+        "fp8_over_bf16": round(med(t["fp8"]) / med(t["bf16"]), 4),
+        "bf16_cache_bytes": sess.cache.nbytes(), "fp8_cache_bytes": c.nbytes(),
+        "fp8_attn_us_per_layer": round(t_attn * 1e6, 2), "fp8_attn_kv_GBps": round(kv_bytes / t_attn / 1e9, 1),
+    }
 
 
 def ragged_lengths(batch, prompt):
@@ -66,14 +110,26 @@ def main():
     ap.add_argument("--recompute", action="store_true")
     ap.add_argument("--ragged", action="store_true",
                     help="also time a ragged session: prompt lengths spread over [prompt/4, prompt]")
+    ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16",
+                    help="fp8: also time the fp8-cache session against the bf16 one, alternating in this process")
+    ap.add_argument("--rounds", type=int, default=5, help="alternating rounds of the --kv-dtype fp8 comparison")
+    ap.add_argument("--long-context", action="store_true",
+                    help="Llama-shaped model cut to --layers layers, max_len 4096, a prompt that nearly fills it")
+    ap.add_argument("--layers", type=int, default=4)
     a = ap.parse_args()
-    cfg = get_preset(a.model)
+    chunk = None
+    if a.long_context:
+        a.model, max_len, chunk = f"llama-1.1b[{a.layers} layers]", 4096, 512
+        a.prompt = max_len - a.tokens - 2
+        cfg = get_preset("llama-1.1b", num_layers=a.layers, context_length=max_len)
+    else:
+        cfg = get_preset(a.model)
+        max_len = a.prompt + a.tokens + 2
     torch.manual_seed(0)
     model = TransformerLM.from_config(cfg, device="cuda", dtype=torch.bfloat16).eval()
-    max_len = a.prompt + a.tokens + 2
     for B in a.batch:
         ids = torch.randint(0, cfg.vocab_size, (B, a.prompt + 1), device="cuda")
-        sess = DecodeSession(model, B, max_len=max_len, use_graph=not a.no_graph)
+        sess = DecodeSession(model, B, max_len=max_len, use_graph=not a.no_graph, prefill_chunk=chunk)
         with torch.no_grad():
             # prefill throughput
             sess.reset()
@@ -113,6 +169,8 @@ def main():
                 "attn_kv_GBps": round(kv_bytes / t_attn / 1e9, 1),
                 "cache_len": L,
             }
+            if a.kv_dtype == "fp8":
+                out.update(fp8_arm(model, sess, ids, a.prompt, a.tokens, a.rounds, not a.no_graph, chunk))
             if a.ragged:
                 lengths = ragged_lengths(B, a.prompt)
                 rs = DecodeSession(model, B, max_len=max_len, use_graph=not a.no_graph, ragged=True)

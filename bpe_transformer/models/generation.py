@@ -35,6 +35,17 @@ applied to K), i.e. each (sequence, kv head) is one contiguous ``Lmax x D``
 slab the decode kernel streams.  GPT-2-small at Lmax 1024 needs 36 MiB per
 sequence, so a 288 GB MI355X holds thousands of sequences.
 
+**fp8 cache** (``kv_dtype="fp8"``, opt-in): the same layout in
+``float8_e4m3fn`` bytes plus one power-of-two fp32 scale per row (``k_scale,
+v_scale: [num_layers, B, Hkv, Lmax]``), ``(D + 4) / (2 D)`` of the bytes, which
+is what the memory-bound decode attention reads.  It behaves as a bf16 cache
+that holds the dequantised rows (``ops/decode.py`` states the format).  Every
+step is ``kv_append_fp8`` + attention over the cache as stored --
+``decode_attn_fp8``, or ``kv_dequant`` + ``cache_attn`` for windows of more
+than ``8 / G`` tokens -- and the flash prefill is not used, so a prompt token
+sees the quantised keys of its own window too, whatever the chunking.  Not
+available with a draft model yet.
+
 On the CPU, in fp32, or with the reference ablations (post-norm, no RMSNorm,
 non-SwiGLU FFN) the same session runs the oracle math over the same cache.
 
@@ -100,15 +111,17 @@ def _chunks(T: int, prefill_chunk: int | None) -> list[tuple[int, int]]:
     return [(t0, min(c, T - t0)) for t0 in range(0, T, c)]
 
 
-def _append_plan(T: int, G: int, filled: bool, prefill_chunk: int | None = None) -> list[tuple[int, int, str]]:
+def _append_plan(T: int, G: int, filled: bool, prefill_chunk: int | None = None,
+                 flash: bool = True) -> list[tuple[int, int, str]]:
     """Steps ``(t0, w, kind)`` in which a window of ``T`` tokens is appended: tokens ``t0 .. t0 + w - 1`` in one pass
     over the layers whose attention is ``kind``: ``"flash"`` (empty cache: the training kernel, causal inside the
     window), ``"cache"`` (``cache_attn`` over the cache) or ``"decode"`` (``decode_attn``, ``G * w <= 8``).
-    ``filled``: some sequence already holds tokens.  ``prefill_chunk`` bounds ``w``."""
+    ``filled``: some sequence already holds tokens.  ``prefill_chunk`` bounds ``w``.  ``flash=False`` (an fp8 cache)
+    never plans ``"flash"``: a token always attends to the cache as stored, its own window included."""
     assert T >= 1 and G >= 1
     plan = []
     for t0, w in _chunks(T, prefill_chunk):
-        if t0 == 0 and not filled and w > 1:
+        if flash and t0 == 0 and not filled and w > 1:
             plan.append((t0, w, "flash"))
         elif G * w >= _CACHE_ATTN_MIN_ROWS:
             plan.append((t0, w, "cache"))
@@ -131,13 +144,28 @@ def _gemv_ok(m: int, k: int) -> bool:
 
 class KVCache:
     """Per-layer K/V caches ``[L, B, Hkv, Lmax, D]`` plus the device-side fill position: one int32 shared by the
-    batch, or with ``ragged`` one per sequence (``pos [B]``, host mirror ``lengths``)."""
+    batch, or with ``ragged`` one per sequence (``pos [B]``, host mirror ``lengths``).
+
+    ``kv_dtype="fp8"``: ``k`` / ``v`` are ``float8_e4m3fn`` bytes and ``k_scale`` / ``v_scale [L, B, Hkv, Lmax]`` hold
+    one power-of-two fp32 scale per row (``ops/decode.py`` states the format); ``dtype`` is then only the dtype in
+    which :meth:`read` hands rows back."""
 
     def __init__(self, num_layers: int, batch: int, num_kv_heads: int, max_len: int, head_dim: int, device=None,
-                 dtype=torch.bfloat16, ragged: bool = False):
+                 dtype=torch.bfloat16, ragged: bool = False, kv_dtype: str = "bf16"):
+        if kv_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"kv_dtype: 'bf16' or 'fp8', got {kv_dtype!r}")
         shape = (num_layers, batch, num_kv_heads, max_len, head_dim)
-        self.k = torch.zeros(shape, device=device, dtype=dtype)
-        self.v = torch.zeros(shape, device=device, dtype=dtype)
+        self.kv_dtype = kv_dtype
+        self.fp8 = kv_dtype == "fp8"
+        self.dtype = dtype
+        if self.fp8:
+            self.k = torch.zeros(shape, device=device, dtype=torch.float8_e4m3fn)
+            self.v = torch.zeros(shape, device=device, dtype=torch.float8_e4m3fn)
+            self.k_scale = torch.ones(shape[:-1], device=device, dtype=torch.float32)
+            self.v_scale = torch.ones(shape[:-1], device=device, dtype=torch.float32)
+        else:
+            self.k = torch.zeros(shape, device=device, dtype=dtype)
+            self.v = torch.zeros(shape, device=device, dtype=dtype)
         self.ragged = ragged
         self.pos = torch.zeros(batch if ragged else 1, device=device, dtype=torch.int32)  # tokens already cached
         self._len = [0] * batch  # host mirror of pos (never read back), per sequence: all equal unless ragged
@@ -164,7 +192,30 @@ class KVCache:
             self._len[r] += int(n)
 
     def nbytes(self) -> int:
-        return 2 * self.k.numel() * self.k.element_size()
+        """Bytes of K and V, the fp8 cache's scales included: ``(D + 4) / (2 D)`` of the bf16 cache's."""
+        n = 2 * self.k.numel() * self.k.element_size()
+        return n + 2 * self.k_scale.numel() * 4 if self.fp8 else n
+
+    def write(self, layer: int, row: int, lo: int, hi: int, k: Tensor, v: Tensor) -> None:
+        """Oracle path: ``k`` / ``v [Hkv, hi - lo, D]`` become rows ``lo .. hi - 1`` of sequence ``row`` (fp8: rounded
+        to bf16, as the bf16 cache would hold them, then quantised)."""
+        if not self.fp8:
+            self.k[layer, row, :, lo:hi] = k.to(self.k.dtype)
+            self.v[layer, row, :, lo:hi] = v.to(self.v.dtype)
+            return
+        from ..ops.decode import kv_quantize_reference
+
+        self.k[layer, row, :, lo:hi], self.k_scale[layer, row, :, lo:hi] = kv_quantize_reference(k.to(torch.bfloat16))
+        self.v[layer, row, :, lo:hi], self.v_scale[layer, row, :, lo:hi] = kv_quantize_reference(v.to(torch.bfloat16))
+
+    def read(self, layer: int, rows: list[int], n: int, dtype) -> tuple[Tensor, Tensor]:
+        """Oracle path: the first ``n`` rows of the sequences ``rows`` as ``dtype`` (fp8: dequantised, exactly)."""
+        if not self.fp8:
+            return self.k[layer, rows, :, :n].to(dtype), self.v[layer, rows, :, :n].to(dtype)
+        from ..ops.decode import kv_dequantize_reference as deq
+
+        return (deq(self.k[layer, rows, :, :n], self.k_scale[layer, rows, :, :n], dtype),
+                deq(self.v[layer, rows, :, :n], self.v_scale[layer, rows, :, :n], dtype))
 
 
 def _top_k_logits(logits: Tensor, top_k: int | None) -> Tensor:
@@ -208,10 +259,18 @@ class DecodeSession:
     is one pass over the layers for the whole window (``cache_attn``), as on an empty cache.  ``prefill_chunk=c``
     cuts every prefill or append, ragged or not, into chunks of at most ``c`` tokens, which bounds activation memory
     by ``B * c`` rows.
+
+    ``kv_dtype="fp8"`` keeps the cache as e4m3 rows with one power-of-two scale each (``csrc/kv_fp8.hip``;
+    ``ops/decode.py`` states the format): ``(D + 4) / (2 D)`` of the bf16 cache's bytes.  Every step appends with
+    ``kv_append_fp8`` and attends to the cache as stored, its own window included -- ``decode_attn_fp8`` up to ``8 /
+    G`` tokens, ``kv_dequant`` into a one-layer bf16 scratch + ``cache_attn`` beyond; the flash prefill is never used,
+    so prefill, chunked prefill and decode have one semantics, that of a bf16 cache holding the dequantised rows.  At
+    batch <= 8 the QKV projection is ``decode_gemv`` followed by ``kv_append_fp8`` (a row's amax spans several
+    workgroups of the fused ``decode_qkv`` epilogue): 6 launches per layer instead of 5.
     """
 
     def __init__(self, model, batch: int, max_len: int | None = None, use_graph: bool = True, ragged: bool = False,
-                 prefill_chunk: int | None = None):
+                 prefill_chunk: int | None = None, kv_dtype: str = "bf16"):
         assert prefill_chunk is None or prefill_chunk >= 1, "prefill_chunk: a positive number of tokens, or None"
         self.model = model
         self.ragged = ragged
@@ -228,7 +287,10 @@ class DecodeSession:
             assert self.max_len <= attn.rope.max_seq_len, "KV cache longer than the RoPE table (context_length)"
         p = model.lm_head.weight
         self.device = p.device
-        self.cache = KVCache(len(model.layers), batch, self.Hkv, self.max_len, self.D, self.device, p.dtype, ragged)
+        self.cache = KVCache(len(model.layers), batch, self.Hkv, self.max_len, self.D, self.device, p.dtype, ragged,
+                             kv_dtype)
+        self.fp8 = self.cache.fp8
+        self._deq = None  # fp8: one layer's bf16 K / V scratch for cache_attn (allocated by the first long window)
         self.fast = self._fast_ok()
         self.use_graph = use_graph and self.fast
         # ragged: per-sequence advance of the decode step (1 = active), static so that the captured graph reads it
@@ -342,7 +404,7 @@ class DecodeSession:
             return torch.cat(out, 1)
         out = [self._forward_fast(ids[:, t0 : t0 + w], prefill=kind == "flash", cache=kind == "cache",
                                   all_logits=True).view(B, w, -1)
-               for t0, w, kind in _append_plan(T, self.H // self.Hkv, max(c._len) > 0, self.prefill_chunk)]
+               for t0, w, kind in _append_plan(T, self.H // self.Hkv, max(c._len) > 0, self.prefill_chunk, not self.fp8)]
         c.advance(rows, [T] * B)
         return out[0] if len(out) == 1 else torch.cat(out, 1)
 
@@ -391,9 +453,11 @@ class DecodeSession:
             # Filled cache (multi-turn serving, a chunk of a long prompt): kv_append + cache_attn over the whole
             # window, every token attending the cache plus its own causal prefix; a window of up to 8 / G tokens
             # (speculative verification) is one decode_attn step (_append_plan)
-            plan = _append_plan(T, G, max(cur) > 0, self.prefill_chunk)
+            plan = _append_plan(T, G, max(cur) > 0, self.prefill_chunk, not self.fp8)
             b = rows[0]
             kv = None if B == self.batch else (c.k[:, b : b + 1], c.v[:, b : b + 1], c.pos[b : b + 1])
+            if kv is not None and self.fp8:
+                kv += (c.k_scale[:, b : b + 1], c.v_scale[:, b : b + 1])
         out = None
         for t0, w, kind in plan:
             # sequence i advances by the part of its length that falls in the chunk, and its logits come from
@@ -645,7 +709,19 @@ class DecodeSession:
         from ..ops._ext import ops as hip
 
         c = self.cache
-        return (hip(), *(kv or (c.k, c.v, c.pos)), self._cos, self._sin, self._cos.numel() > 0)
+        return (hip(), *(kv[:3] if kv else (c.k, c.v, c.pos)), self._cos, self._sin, self._cos.numel() > 0)
+
+    def _scales(self, kv):
+        """fp8: the (k_scale, v_scale) that go with ``_operands(kv)``'s (k, v)."""
+        return kv[3:] if kv else (self.cache.k_scale, self.cache.v_scale)
+
+    def _dequant_scratch(self, n: int):
+        """fp8: bf16 K / V ``[n, Hkv, Lmax, D]`` that ``kv_dequant`` fills for ``cache_attn``, one layer's worth,
+        reused by every layer.  Zero-filled once, so rows that were never written are finite, as in a bf16 cache."""
+        if self._deq is None:
+            shape = (self.batch, self.Hkv, self.max_len, self.D)
+            self._deq = tuple(torch.zeros(shape, device=self.device, dtype=torch.bfloat16) for _ in range(2))
+        return self._deq[0][:n], self._deq[1][:n]
 
     def _forward_fast(self, ids: Tensor, prefill: bool, step: Tensor | None = None, last: Tensor | None = None,
                       kv=None, cache: bool = False, all_logits: bool = False, advance: bool = True) -> Tensor:
@@ -662,6 +738,11 @@ class DecodeSession:
         B, T = ids.shape
         H, Hkv, D = self.H, self.Hkv, self.D
         scale = 1.0 / math.sqrt(D)
+        if self.fp8:
+            assert not prefill, "an fp8 session attends to the cache as stored (no flash prefill)"
+            ksc, vsc = self._scales(kv)
+            if cache:
+                kd, vd = self._dequant_scratch(B)
         xr = m.token_embeddings(ids).reshape(B * T, -1)
         xd = None
         for li, (ln1, wqkv, wo, ln2, w13, w2, eps) in enumerate(self._w):
@@ -674,6 +755,13 @@ class DecodeSession:
                 q, k, v = qkv[:, : H * D], qkv[:, H * D : (H + Hkv) * D], qkv[:, (H + Hkv) * D :]
                 o, _ = h.fa_fwd(q, k, v, cos, sin, B, T, H, Hkv, D, True, use_rope, scale)
                 h.kv_append(qkv, kc[li], vc[li], cos, sin, pos, B, T, H, use_rope)
+            elif self.fp8:
+                q = h.kv_append_fp8(qkv, kc[li], vc[li], ksc[li], vsc[li], cos, sin, pos, B, T, H, use_rope)
+                if cache:
+                    h.kv_dequant(kc[li], vc[li], ksc[li], vsc[li], pos, T, kd, vd)
+                    o = h.cache_attn(q, kd, vd, pos, H, scale, T)
+                else:
+                    o = h.decode_attn_fp8(q, kc[li], vc[li], ksc[li], vsc[li], pos, H, scale, True, T)
             else:
                 q = h.kv_append(qkv, kc[li], vc[li], cos, sin, pos, B, T, H, use_rope)
                 if cache:
@@ -708,18 +796,29 @@ class DecodeSession:
         """Decode step for batch <= 16 on the fused skinny-GEMM kernels (``csrc/decode_gemv.hip``): per layer
         qkv (+RMSNorm, +RoPE, +cache write) -> split-K decode attention -> Wo (+ the split combine) -> [W1; W3]
         (+residual add, +RMSNorm, +SwiGLU) -> W2; the residual add of W2's output is folded into the next layer's
-        QKV prologue: 5 launches per layer."""
+        QKV prologue: 5 launches per layer.  An fp8 cache takes 6: the QKV projection with the plain epilogue, then
+        ``kv_append_fp8`` (RoPE, quantisation, cache write), and ``decode_attn_fp8``."""
         h, kc, vc, pos, cos, sin, use_rope = self._operands(kv)
         m = self.model
         H = self.H
+        B = ids.shape[0]
         scale = 1.0 / math.sqrt(self.D)
-        xr = m.token_embeddings(ids).reshape(ids.shape[0], -1)
+        if self.fp8:
+            ksc, vsc = self._scales(kv)
+        xr = m.token_embeddings(ids).reshape(B, -1)
         xd = None
         for li, (ln1, wqkv, wo, ln2, w13, w2, eps) in enumerate(self._w):
-            q, s = h.decode_qkv(xr, xd, ln1, eps, wqkv, kc[li], vc[li], cos, sin, pos, H, use_rope)
+            if self.fp8:
+                qkv, s = h.decode_gemv(xr, xd, ln1, eps, wqkv, 0)
+                q = h.kv_append_fp8(qkv, kc[li], vc[li], ksc[li], vsc[li], cos, sin, pos, B, 1, H, use_rope)
+            else:
+                q, s = h.decode_qkv(xr, xd, ln1, eps, wqkv, kc[li], vc[li], cos, sin, pos, H, use_rope)
             if xd is not None:
                 xr = s
-            part = h.decode_attn(q, kc[li], vc[li], pos, H, scale, False)
+            if self.fp8:
+                part = h.decode_attn_fp8(q, kc[li], vc[li], ksc[li], vsc[li], pos, H, scale, False)
+            else:
+                part = h.decode_attn(q, kc[li], vc[li], pos, H, scale, False)
             g1 = h.decode_attn_proj(part, wo)  # the flash-decoding combine runs in Wo's prologue
             a, xr = h.decode_gemv(xr, g1, ln2, eps, w13, 1)
             xd, _ = h.decode_gemv(a, None, None, 0.0, w2, 0)
@@ -759,10 +858,8 @@ class DecodeSession:
                     k = attn.rope(k, tpr)
                 for i, r in enumerate(rows):
                     w = max(0, min(T, Lmax - cur[i]))
-                    self.cache.k[li, r, :, cur[i] : cur[i] + w] = k[i, :, :w].to(self.cache.k.dtype)
-                    self.cache.v[li, r, :, cur[i] : cur[i] + w] = v[i, :, :w].to(self.cache.v.dtype)
-                kk = self.cache.k[li, rows, :, :Lk].to(q.dtype)
-                vv = self.cache.v[li, rows, :, :Lk].to(q.dtype)
+                    self.cache.write(li, r, cur[i], cur[i] + w, k[i, :, :w], v[i, :, :w])
+                kk, vv = self.cache.read(li, rows, Lk, q.dtype)
                 if Hkv != H:
                     kk = kk.repeat_interleave(H // Hkv, dim=1)
                     vv = vv.repeat_interleave(H // Hkv, dim=1)
@@ -816,7 +913,7 @@ class SpeculativeSession:
     """
 
     def __init__(self, target, draft, batch: int, num_draft_tokens: int = 4, max_len: int | None = None,
-                 use_graph: bool = True):
+                 use_graph: bool = True, kv_dtype: str = "bf16"):
         K = int(num_draft_tokens)
         if K < 1:
             raise ValueError("num_draft_tokens must be at least 1")
@@ -828,6 +925,9 @@ class SpeculativeSession:
         self.max_len = max_len or min(target.context_length, draft.context_length)
         if self.max_len > min(target.context_length, draft.context_length):
             raise ValueError("max_len exceeds the context length of the target or the draft")
+        if kv_dtype != "bf16":  # (left for later: the verify step would set positions of an fp8 cache as it does here)
+            raise ValueError(f"kv_dtype={kv_dtype!r} with a draft model is not supported yet: speculative decoding "
+                             "runs on the bf16 cache only")
         self.target = DecodeSession(target, batch, self.max_len, use_graph, ragged=True)
         self.draft = DecodeSession(draft, batch, self.max_len, use_graph, ragged=True)
         self.device = dev = self.target.device

@@ -225,6 +225,7 @@ class TransformerLM(nn.Module):
         seed: int | None = None,
         draft_model: "TransformerLM | None" = None,
         num_draft_tokens: int = 4,
+        kv_dtype: str = "bf16",
     ) -> Tensor:
         """Autoregressive sampling (temperature, top-k, nucleus).  ``prompt``: ``[S]`` or ``[B, S]``.
 
@@ -246,9 +247,18 @@ class TransformerLM(nn.Module):
         output is this model's own, sampled output is distributed as this model's.  It implies the device sampler
         and cannot be combined with ``top_k`` or ``top_p`` (``ValueError``).  :meth:`truncated` gives a draft
         without a second checkpoint.
+
+        ``kv_dtype="fp8"`` keeps the KV cache as e4m3 rows with power-of-two scales (``DecodeSession(...,
+        kv_dtype="fp8")``: about half the cache bytes); it needs the KV-cache path and is not yet supported together
+        with ``draft_model`` (``ValueError``).
         """
         assert sampler in ("host", "device"), "sampler: 'host' or 'device'"
+        if kv_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"kv_dtype: 'bf16' or 'fp8', got {kv_dtype!r}")
         if draft_model is not None:
+            if kv_dtype != "bf16":
+                raise ValueError("kv_dtype='fp8' with draft_model is not supported yet: speculative decoding runs on "
+                                 "the bf16 cache only")
             return self._generate_speculative(prompt, max_new_tokens, temperature, top_p, eos_token_id, generator,
                                               top_k, seed, draft_model, num_draft_tokens)
         kw = dict(top_k=top_k, sampler=sampler, seed=seed)
@@ -258,21 +268,24 @@ class TransformerLM(nn.Module):
             if use_cache and longest + max_new_tokens <= self.context_length and max_new_tokens > 0:
                 from .generation import DecodeSession
 
-                sess = DecodeSession(self, len(prompt), max_len=longest + max_new_tokens, ragged=True)
+                sess = DecodeSession(self, len(prompt), max_len=longest + max_new_tokens, ragged=True,
+                                     kv_dtype=kv_dtype)
                 return sess.generate(list(prompt), max_new_tokens, temperature, top_p, eos_token_id, generator, **kw)
             # without the cache: one sequence at a time through the loop below (which stops at its EOS)
             return [self.generate(p.reshape(-1), max_new_tokens, temperature, top_p, eos_token_id, generator, use_cache,
-                                  **kw) for p in prompt]
+                                  kv_dtype=kv_dtype, **kw) for p in prompt]
         squeeze = prompt.dim() == 1
         ids = prompt.unsqueeze(0) if squeeze else prompt
         self._fence(self)  # the decode session packs / reads every weight up front
         if use_cache and ids.shape[1] + max_new_tokens <= self.context_length and max_new_tokens > 0:
             from .generation import DecodeSession
 
-            sess = DecodeSession(self, ids.shape[0], max_len=ids.shape[1] + max_new_tokens)
+            sess = DecodeSession(self, ids.shape[0], max_len=ids.shape[1] + max_new_tokens, kv_dtype=kv_dtype)
             out = sess.generate(ids, max_new_tokens, temperature, top_p, eos_token_id, generator, **kw)
             return out[0] if squeeze else out
         assert sampler == "host" or max_new_tokens <= 0, "sampler='device' needs the KV-cache path (use_cache, and " \
+            "prompt + max_new_tokens within context_length)"
+        assert kv_dtype == "bf16" or max_new_tokens <= 0, "kv_dtype='fp8' needs the KV-cache path (use_cache, and " \
             "prompt + max_new_tokens within context_length)"
         for _ in range(max_new_tokens):
             ctx = ids[:, -self.context_length :]

@@ -265,6 +265,12 @@ static void launch_d(const void* q, const void* k, const void* v, float* part, v
     if (out != nullptr) decode_combine_kernel<D><<<B * T * H, D, 0, s>>>(part, (__bf16*)out, ns);
 }
 
+// the combine alone: `rows` = B * T * H partial rows [nsplit][D + 2] -> bf16 out [rows][D] (kv_fp8.hip's decode step)
+void launch_decode_combine(const float* part, void* out, int rows, int D, int nsplit, hipStream_t s) {
+    if (D == 64) decode_combine_kernel<64><<<rows, 64, 0, s>>>(part, (__bf16*)out, nsplit);
+    else decode_combine_kernel<128><<<rows, 128, 0, s>>>(part, (__bf16*)out, nsplit);
+}
+
 void launch_decode_attn(const void* q, const void* k, const void* v, float* part, void* out, const int* pos,
                         int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax, float scale, hipStream_t s) {
     if (D == 64) launch_d<64>(q, k, v, part, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, s);

@@ -148,6 +148,18 @@ void launch_decode_attn(const void* q, const void* k, const void* v, float* part
                         int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax, float scale, hipStream_t s);
 void launch_kv_append(const void* qkv, long ld, void* qo, void* Kc, void* Vc, const float* cosT, const float* sinT,
                       const int* pos, int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax, hipStream_t s);
+void launch_decode_combine(const float* part, void* out, int rows, int D, int nsplit, hipStream_t s);
+// kv_fp8.hip (the fp8 KV cache: e4m3 bytes k8 / v8 [B, Hkv, Lmax, D] with one power-of-two fp32 scale per row,
+// ks / vs [B, Hkv, Lmax]; the contracts of launch_kv_append / launch_decode_attn otherwise).  launch_kv_dequant
+// writes rows [0, min(pos + T, Lmax)) of every K and V slab as bf16 into ko / vo [B, Hkv, Lmax, D].
+void launch_kv_append_fp8(const void* qkv, long ld, void* qo, void* k8, void* v8, float* ks, float* vs,
+                          const float* cosT, const float* sinT, const int* pos, int pos_stride, int B, int T, int H,
+                          int Hkv, int D, int Lmax, hipStream_t s);
+void launch_decode_attn_fp8(const void* q, const void* k8, const void* v8, const float* ks, const float* vs,
+                            float* part, void* out, const int* pos, int pos_stride, int B, int T, int H, int Hkv,
+                            int D, int Lmax, float scale, hipStream_t s);
+void launch_kv_dequant(const void* k8, const void* v8, const float* ks, const float* vs, void* ko, void* vo,
+                       const int* pos, int pos_stride, int B, int T, int Hkv, int D, int Lmax, hipStream_t s);
 // flash_attn_cache.hip (flash prefill over the cache: T new tokens per sequence, any T; `pos` as above)
 bool cache_attn_ok(int H, int Hkv, int D, int T, int Lmax);
 void launch_cache_attn(const void* q, const void* k, const void* v, void* out, const int* pos, int pos_stride, int B,

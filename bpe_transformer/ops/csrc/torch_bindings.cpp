@@ -1050,6 +1050,87 @@ at::Tensor cache_attn(const at::Tensor& q, const at::Tensor& kc, const at::Tenso
     return out;
 }
 
+// ---- fp8 KV cache (kv_fp8.hip): e4m3 bytes [B, Hkv, Lmax, D] + one fp32 scale per row [B, Hkv, Lmax]
+void check_cache8(const at::Tensor& c, const at::Tensor& sc, int64_t B, int64_t Hkv, const char* name) {
+    check_cuda(c, name);
+    check_cuda(sc, name);
+    TORCH_CHECK(c.scalar_type() == at::kFloat8_e4m3fn && c.dim() == 4 && c.is_contiguous(), "fp8 kv cache: ", name,
+                " must be a contiguous float8_e4m3fn [B, Hkv, Lmax, D] tensor");
+    TORCH_CHECK(c.size(0) == B && c.size(1) == Hkv, "fp8 kv cache: ", name, " batch / kv-head mismatch");
+    TORCH_CHECK(sc.scalar_type() == at::kFloat && sc.dim() == 3 && sc.is_contiguous() && sc.size(0) == B &&
+                    sc.size(1) == Hkv && sc.size(2) == c.size(2),
+                "fp8 kv cache: the scales of ", name, " must be a contiguous fp32 [B, Hkv, Lmax] tensor");
+    check_aligned(c, name);
+}
+
+at::Tensor kv_append_fp8(const at::Tensor& qkv, at::Tensor k8, at::Tensor v8, at::Tensor ks, at::Tensor vs,
+                         const at::Tensor& cos, const at::Tensor& sin, const at::Tensor& pos, int64_t B, int64_t T,
+                         int64_t H, bool use_rope) {
+    TORCH_CHECK(k8.dim() == 4, "kv_append_fp8: k8 must be [B, Hkv, Lmax, D]");
+    const int64_t Hkv = k8.size(1), Lmax = k8.size(2), D = k8.size(3);
+    TORCH_CHECK((D == 64 || D == 128) && Hkv > 0 && H % Hkv == 0, "kv_append_fp8: head dim 64/128, H multiple of Hkv");
+    check_qkv(qkv, B * T, (H + 2 * Hkv) * D, "qkv");
+    check_cache8(k8, ks, B, Hkv, "k8");
+    check_cache8(v8, vs, B, Hkv, "v8");
+    TORCH_CHECK(v8.sizes() == k8.sizes(), "kv_append_fp8: k / v cache shapes differ");
+    const int pstride = check_pos(pos, B);
+    if (use_rope)
+        TORCH_CHECK(cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
+                        sin.is_contiguous() && cos.size(0) >= Lmax && cos.size(1) == D / 2 && sin.sizes() == cos.sizes(),
+                    "kv_append_fp8: rope tables must be fp32 [>=Lmax, D/2]");
+    DevGuard g(qkv.device());
+    auto q = at::empty({B * T, H * D}, qkv.options());
+    launch_kv_append_fp8(qkv.data_ptr(), qkv.stride(0), q.data_ptr(), k8.data_ptr(), v8.data_ptr(),
+                         ks.data_ptr<float>(), vs.data_ptr<float>(), use_rope ? cos.data_ptr<float>() : nullptr,
+                         use_rope ? sin.data_ptr<float>() : nullptr, pos.data_ptr<int>(), pstride, (int)B, (int)T,
+                         (int)H, (int)Hkv, (int)D, (int)Lmax, cur_stream());
+    return q;
+}
+
+// decode_attn over the fp8 cache: the same contract, outputs and partials layout
+at::Tensor decode_attn_fp8(const at::Tensor& q, const at::Tensor& k8, const at::Tensor& v8, const at::Tensor& ks,
+                           const at::Tensor& vs, const at::Tensor& pos, int64_t H, double scale, bool combine,
+                           int64_t T) {
+    TORCH_CHECK(k8.dim() == 4, "decode_attn_fp8: k8 must be [B, Hkv, Lmax, D]");
+    const int64_t B = k8.size(0), Hkv = k8.size(1), Lmax = k8.size(2), D = k8.size(3);
+    TORCH_CHECK(decode_attn_ok((int)H, (int)Hkv, (int)D, (int)T),
+                "decode_attn_fp8: head dim 64/128, H a multiple of Hkv and (H / Hkv) * T <= 8 required");
+    check_cuda(q, "q");
+    TORCH_CHECK(q.scalar_type() == at::kBFloat16 && q.is_contiguous() && q.numel() == B * T * H * D,
+                "decode_attn_fp8: q must be contiguous bf16 [B*T, H*D]");
+    check_cache8(k8, ks, B, Hkv, "k8");
+    check_cache8(v8, vs, B, Hkv, "v8");
+    TORCH_CHECK(v8.sizes() == k8.sizes(), "decode_attn_fp8: k / v cache shapes differ");
+    const int pstride = check_pos(pos, B);
+    DevGuard g(q.device());
+    const int ns = decode_attn_splits((int)Lmax);
+    auto part = at::empty({B * T, H, ns, D + 2}, q.options().dtype(at::kFloat));
+    auto out = combine ? at::empty({B * T, H * D}, q.options()) : at::Tensor();
+    launch_decode_attn_fp8(q.data_ptr(), k8.data_ptr(), v8.data_ptr(), ks.data_ptr<float>(), vs.data_ptr<float>(),
+                           part.data_ptr<float>(), combine ? out.data_ptr() : nullptr, pos.data_ptr<int>(), pstride,
+                           (int)B, (int)T, (int)H, (int)Hkv, (int)D, (int)Lmax, (float)scale, cur_stream());
+    return combine ? out : part;
+}
+
+// rows [0, min(pos[b] + T, Lmax)) of every K and V slab -> bf16 k_out / v_out [B, Hkv, Lmax, D]; other rows untouched
+void kv_dequant(const at::Tensor& k8, const at::Tensor& v8, const at::Tensor& ks, const at::Tensor& vs,
+                const at::Tensor& pos, int64_t T, at::Tensor k_out, at::Tensor v_out) {
+    TORCH_CHECK(k8.dim() == 4 && T >= 0, "kv_dequant: k8 must be [B, Hkv, Lmax, D], T >= 0");
+    const int64_t B = k8.size(0), Hkv = k8.size(1), Lmax = k8.size(2), D = k8.size(3);
+    TORCH_CHECK(D % 16 == 0 && Lmax < (1LL << 31) && T < (1LL << 30), "kv_dequant: head dim multiple of 16");
+    check_cache8(k8, ks, B, Hkv, "k8");
+    check_cache8(v8, vs, B, Hkv, "v8");
+    check_cache(k_out, B, Hkv, "k_out");
+    check_cache(v_out, B, Hkv, "v_out");
+    TORCH_CHECK(v8.sizes() == k8.sizes() && k_out.sizes() == k8.sizes() && v_out.sizes() == k8.sizes(),
+                "kv_dequant: cache / output shapes differ");
+    const int pstride = check_pos(pos, B);
+    DevGuard g(k8.device());
+    launch_kv_dequant(k8.data_ptr(), v8.data_ptr(), ks.data_ptr<float>(), vs.data_ptr<float>(), k_out.data_ptr(),
+                      v_out.data_ptr(), pos.data_ptr<int>(), pstride, (int)B, (int)T, (int)Hkv, (int)D, (int)Lmax,
+                      cur_stream());
+}
+
 // Skinny-GEMM prologue / shape checks shared by decode_gemv and decode_qkv; returns the residual-sum output
 at::Tensor gemv_setup(GemvArgs& a, const at::Tensor& x, const c10::optional<at::Tensor>& xd,
                       const c10::optional<at::Tensor>& ln, double eps, const at::Tensor& w) {
@@ -1351,6 +1432,12 @@ TORCH_LIBRARY(bpe_hip, m) {
     m.def("decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor pos, int H, float scale, "
           "bool combine=True, int T=1) -> Tensor");
     m.def("decode_attn_proj(Tensor part, Tensor w) -> Tensor");
+    m.def("kv_append_fp8(Tensor qkv, Tensor(a!) k8, Tensor(b!) v8, Tensor(c!) k_scale, Tensor(d!) v_scale, Tensor cos, "
+          "Tensor sin, Tensor pos, int B, int T, int H, bool use_rope) -> Tensor");
+    m.def("decode_attn_fp8(Tensor q, Tensor k8, Tensor v8, Tensor k_scale, Tensor v_scale, Tensor pos, int H, "
+          "float scale, bool combine=True, int T=1) -> Tensor");
+    m.def("kv_dequant(Tensor k8, Tensor v8, Tensor k_scale, Tensor v_scale, Tensor pos, int T, Tensor(a!) k_out, "
+          "Tensor(b!) v_out) -> ()");
     m.def("cache_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor pos, int H, float scale, int T) -> Tensor");
     m.def("rmsnorm_fwd(Tensor x, Tensor w, float eps) -> (Tensor, Tensor)");
     m.def("add_rmsnorm_fwd(Tensor x, Tensor d, Tensor w, float eps) -> (Tensor, Tensor, Tensor)");
@@ -1461,6 +1548,9 @@ TORCH_LIBRARY_IMPL(bpe_hip, CUDA, m) {
     m.impl("decode_gemv", &decode_gemv);
     m.impl("decode_qkv", &decode_qkv);
     m.impl("decode_attn_proj", &decode_attn_proj);
+    m.impl("kv_append_fp8", &kv_append_fp8);
+    m.impl("decode_attn_fp8", &decode_attn_fp8);
+    m.impl("kv_dequant", &kv_dequant);
     m.impl("sample_logits", &sample_logits);
     m.impl("sample_step", &sample_step);
     m.impl("spec_verify", &spec_verify);

@@ -26,6 +26,23 @@ can be captured in a HIP graph.  The CPU versions are the oracle.
 (``[B]``: ragged batches, every sequence at its own length).  With ``[B]``
 everything above holds per sequence: sequence ``b`` is placed, rotated, dropped
 at ``Lmax`` and attended from ``pos[b]``.
+
+**fp8 cache** (``csrc/kv_fp8.hip``).  A cache row -- the ``D`` values of one
+(sequence, KV head, position), exactly what the bf16 cache would have held: K
+roped and rounded to bf16, V as is -- is stored as ``D`` ``float8_e4m3fn`` bytes
+(``k8``, ``v8 [B, Hkv, Lmax, D]``) and one fp32 scale (``k_scale``, ``v_scale
+[B, Hkv, Lmax]``).  The scale ``s`` is the smallest power of two with ``max|x| /
+s <= 448`` (:func:`kv_quantize_reference` states the corner cases), the bytes
+are ``e4m3_rne(x / s)`` and the value read back is ``q * s`` -- exact in fp32
+and representable in bf16.  So an fp8 cache *is* a bf16 cache that holds the
+dequantised values, and that is how its consumers are defined:
+
+* :func:`kv_append_fp8` is :func:`kv_append` with the K / V rows quantised (the
+  returned ``q`` is bit-identical);
+* :func:`decode_attention_fp8` (and ``decode_attention_partials_fp8``) is
+  :func:`decode_attention` on the dequantised caches, reading half the bytes;
+* :func:`kv_dequant` writes the valid rows of a K / V pair as bf16 into a
+  scratch pair, for :func:`prefill_attention` (``cache_attn``) to read.
 """
 
 from __future__ import annotations
@@ -215,3 +232,102 @@ def decode_qkv(x: Tensor, w: Tensor, k_cache: Tensor, v_cache: Tensor, cos: Tens
         return q, (s if xd is not None else None)
     qkv, s = decode_gemv_reference(x, w, xd, ln, eps)
     return kv_append_reference(qkv, k_cache, v_cache, cos, sin, pos, x.shape[0], 1, n_heads), s
+
+
+# ------------------------------------------------------------------ fp8 cache (csrc/kv_fp8.hip)
+FP8 = torch.float8_e4m3fn
+KV_FP8_MIN_SCALE = 2.0 ** -64
+
+
+def kv_quantize_reference(x: Tensor) -> tuple[Tensor, Tensor]:
+    """The definition of the fp8 cache format.  ``x [..., D]`` (bf16 values in any float dtype) -> (``float8_e4m3fn``
+    bytes ``[..., D]``, fp32 scales ``[...]``).  Per row, with ``a = max|x| = m 2^e`` (``m`` in ``[0.5, 1)``): ``s =
+    2^(e-9)`` if ``m <= 0.875`` else ``2^(e-8)``, the smallest power of two with ``a / s <= 448``; clamped below at
+    ``2^-64``; ``s = 1`` for an all-zero row; ``s = NaN`` for a row with a non-finite element (its bytes are
+    unspecified: NaN here).  Bytes: ``e4m3_rne(x * (1 / s))`` -- the product is exact and never exceeds 448."""
+    xf = x.float()
+    a = xf.abs().amax(-1)
+    m, e = torch.frexp(a)
+    s = torch.ldexp(torch.ones_like(a), torch.where(m <= 0.875, e - 9, e - 8))
+    s = s.clamp_min(KV_FP8_MIN_SCALE)
+    s = torch.where(a == 0, torch.ones_like(s), s)
+    s = torch.where(torch.isfinite(a), s, torch.full_like(s, math.nan))
+    q = (xf * (1.0 / s).unsqueeze(-1)).to(FP8)
+    return q, s
+
+
+def kv_dequantize_reference(q: Tensor, s: Tensor, dtype: torch.dtype = torch.bfloat16) -> Tensor:
+    """``q * s`` (exact in fp32, representable in bf16)."""
+    return (q.float() * s.float().unsqueeze(-1)).to(dtype)
+
+
+def kv_append_fp8(qkv: Tensor, k8: Tensor, v8: Tensor, k_scale: Tensor, v_scale: Tensor, cos: Tensor | None,
+                  sin: Tensor | None, pos: Tensor, batch: int, n_new: int, n_heads: int) -> Tensor:
+    """:func:`kv_append` into an fp8 cache: the rows it would have written to bf16 caches are quantised into ``k8`` /
+    ``v8 [B, Hkv, Lmax, D]`` with their scales in ``k_scale`` / ``v_scale [B, Hkv, Lmax]``; returns the same ``q``."""
+    if qkv.is_cuda:
+        use_rope = cos is not None
+        c = cos if use_rope else qkv.new_empty(0, dtype=torch.float32)
+        s = sin if use_rope else qkv.new_empty(0, dtype=torch.float32)
+        return ops().kv_append_fp8(qkv, k8, v8, k_scale, v_scale, c, s, pos, batch, n_new, n_heads, use_rope)
+    return kv_append_fp8_reference(qkv, k8, v8, k_scale, v_scale, cos, sin, pos, batch, n_new, n_heads)
+
+
+def kv_append_fp8_reference(qkv, k8, v8, k_scale, v_scale, cos, sin, pos, batch, n_new, n_heads) -> Tensor:
+    """:func:`kv_append_reference` into bf16-valued staging rows (``qkv``'s dtype rounded to bf16), which are then
+    quantised row by row; only the rows ``kv_append`` writes change."""
+    B, Hkv, Lmax, D = k8.shape
+    P = pos.reshape(-1).tolist()
+    P = P if _per_sequence(pos) else P * batch
+    kt = torch.zeros(B, Hkv, Lmax, D, dtype=torch.bfloat16, device=qkv.device)
+    vt = torch.zeros_like(kt)
+    q = kv_append_reference(qkv, kt, vt, cos, sin, pos, batch, n_new, n_heads)
+    for b, p0 in enumerate(P):
+        w = slice(p0, p0 + max(0, min(n_new, Lmax - p0)))
+        for t, t8, ts in ((kt, k8, k_scale), (vt, v8, v_scale)):
+            t8[b, :, w], ts[b, :, w] = kv_quantize_reference(t[b, :, w])
+    return q
+
+
+def decode_attention_fp8(q: Tensor, k8: Tensor, v8: Tensor, k_scale: Tensor, v_scale: Tensor, pos: Tensor,
+                         n_heads: int, scale: float | None = None, n_new: int = 1) -> Tensor:
+    """:func:`decode_attention` over an fp8 cache."""
+    D = k8.shape[-1]
+    scale = 1.0 / math.sqrt(D) if scale is None else scale
+    if q.is_cuda:
+        return ops().decode_attn_fp8(q.contiguous(), k8, v8, k_scale, v_scale, pos, n_heads, scale, True, n_new)
+    return decode_attention_fp8_reference(q, k8, v8, k_scale, v_scale, pos, n_heads, scale, n_new)
+
+
+def decode_attention_fp8_reference(q, k8, v8, k_scale, v_scale, pos, n_heads, scale=None, n_new: int = 1) -> Tensor:
+    """:func:`decode_attention_reference` on the dequantised caches (fp32 values, so nothing is rounded twice)."""
+    return decode_attention_reference(q, kv_dequantize_reference(k8, k_scale, torch.float32),
+                                      kv_dequantize_reference(v8, v_scale, torch.float32), pos, n_heads, scale, n_new)
+
+
+def decode_attention_partials_fp8(q: Tensor, k8: Tensor, v8: Tensor, k_scale: Tensor, v_scale: Tensor, pos: Tensor,
+                                  n_heads: int, scale: float | None = None, n_new: int = 1) -> Tensor:
+    """:func:`decode_attention_partials` over an fp8 cache: the same layout, for :func:`decode_attn_proj`."""
+    D = k8.shape[-1]
+    scale = 1.0 / math.sqrt(D) if scale is None else scale
+    if q.is_cuda:
+        return ops().decode_attn_fp8(q.contiguous(), k8, v8, k_scale, v_scale, pos, n_heads, scale, False, n_new)
+    assert n_new == 1
+    return decode_partials_reference(q, kv_dequantize_reference(k8, k_scale, torch.float32),
+                                     kv_dequantize_reference(v8, v_scale, torch.float32), pos, n_heads, scale)
+
+
+def kv_dequant(k8: Tensor, v8: Tensor, k_scale: Tensor, v_scale: Tensor, pos: Tensor, n_new: int, k_out: Tensor,
+               v_out: Tensor) -> None:
+    """Rows ``[0, min(pos[b] + n_new, Lmax))`` of every K and V slab, dequantised, into the bf16 ``k_out`` / ``v_out
+    [B, Hkv, Lmax, D]``; the rows past them are left as they are.  ``pos`` is read on the device."""
+    if k8.is_cuda:
+        ops().kv_dequant(k8, v8, k_scale, v_scale, pos, n_new, k_out, v_out)
+        return
+    B, _, Lmax, _ = k8.shape
+    P = pos.reshape(-1).tolist()
+    P = P if _per_sequence(pos) else P * B
+    for b, p0 in enumerate(P):
+        n = max(0, min(p0 + n_new, Lmax))
+        k_out[b, :, :n] = kv_dequantize_reference(k8[b, :, :n], k_scale[b, :, :n], k_out.dtype)
+        v_out[b, :, :n] = kv_dequantize_reference(v8[b, :, :n], v_scale[b, :, :n], v_out.dtype)

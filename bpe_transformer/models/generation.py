@@ -171,6 +171,19 @@ class KVCache:
         self._len = [0] * batch  # host mirror of pos (never read back), per sequence: all equal unless ragged
         self.max_len = max_len
         self.batch = batch
+        self._deq = None  # fp8: one layer's bf16 K / V scratch for cache_attn (allocated by the first long window)
+
+    def view(self, b: int | None = None) -> "KVView":
+        """What a forward pass runs on: the whole batch, or slot ``b`` alone."""
+        return KVView(self, b)
+
+    def dequant_scratch(self, n: int) -> tuple[Tensor, Tensor]:
+        """fp8: bf16 K / V ``[n, Hkv, Lmax, D]`` that ``kv_dequant`` fills for ``cache_attn``, one layer's worth,
+        reused by every layer.  Zero-filled once, so rows that were never written are finite, as in a bf16 cache."""
+        if self._deq is None:
+            self._deq = tuple(torch.zeros(self.k.shape[1:], device=self.k.device, dtype=torch.bfloat16)
+                              for _ in range(2))
+        return self._deq[0][:n], self._deq[1][:n]
 
     @property
     def length(self) -> int:
@@ -216,6 +229,54 @@ class KVCache:
 
         return (deq(self.k[layer, rows, :, :n], self.k_scale[layer, rows, :, :n], dtype),
                 deq(self.v[layer, rows, :, :n], self.v_scale[layer, rows, :, :n], dtype))
+
+
+class KVView:
+    """The cache as one pass over the layers sees it -- ``k`` / ``v [L, n, Hkv, Lmax, D]``, ``pos`` and, for fp8, the
+    row ``scales`` -- of the whole batch or of one slot (``cache.k[:, b:b+1]`` ...: contiguous slabs at the same
+    addresses, so a captured graph stays valid).  Every HIP op call that depends on the cache format is made here:
+    the engine appends and attends, and does not know what a row is stored as.  ``h`` is the HIP ops handle, ``rope``
+    the session's ``(cos, sin, use_rope)``."""
+
+    def __init__(self, cache: KVCache, b: int | None = None):
+        one = (lambda t: t) if b is None else (lambda t: t[:, b : b + 1])
+        self.cache = cache
+        self.k, self.v = one(cache.k), one(cache.v)
+        self.pos = cache.pos if b is None else cache.pos[b : b + 1]
+        self.scales = (one(cache.k_scale), one(cache.v_scale)) if cache.fp8 else None
+
+    def append(self, h, qkv: Tensor, li: int, T: int, H: int, rope) -> Tensor:
+        """RoPE and cache write of layer ``li``'s fused-QKV rows, ``T`` new tokens per sequence; returns the roped q."""
+        B = self.k.shape[1]
+        if self.scales is None:
+            return h.kv_append(qkv, self.k[li], self.v[li], rope[0], rope[1], self.pos, B, T, H, rope[2])
+        ks, vs = self.scales
+        return h.kv_append_fp8(qkv, self.k[li], self.v[li], ks[li], vs[li], rope[0], rope[1], self.pos, B, T, H, rope[2])
+
+    def attend(self, h, q: Tensor, li: int, T: int, H: int, kind: str, combine: bool = True) -> Tensor:
+        """Attention of the appended tokens over the cache as stored: ``kind`` ``"cache"`` (``cache_attn``; fp8: over
+        ``kv_dequant``'s scratch) or ``"decode"`` (``decode_attn``; ``combine=False``: its split partials)."""
+        k, v, pos = self.k[li], self.v[li], self.pos
+        scale = 1.0 / math.sqrt(k.shape[-1])
+        if self.scales is None:
+            if kind == "cache":
+                return h.cache_attn(q, k, v, pos, H, scale, T)
+            return h.decode_attn(q, k, v, pos, H, scale, combine, T)
+        ks, vs = self.scales[0][li], self.scales[1][li]
+        if kind == "cache":
+            kd, vd = self.cache.dequant_scratch(k.shape[0])
+            h.kv_dequant(k, v, ks, vs, pos, T, kd, vd)
+            return h.cache_attn(q, kd, vd, pos, H, scale, T)
+        return h.decode_attn_fp8(q, k, v, ks, vs, pos, H, scale, combine, T)
+
+    def decode_qkv(self, h, xr: Tensor, xd, ln1: Tensor, eps: float, wqkv: Tensor, li: int, H: int, rope):
+        """QKV step of the skinny decode route -> ``(q, x + xd)``: the fused ``decode_qkv`` (projection, RoPE, cache
+        write), or for fp8 ``decode_gemv`` with the plain epilogue followed by :meth:`append` (a row's amax spans
+        several workgroups of the fused epilogue)."""
+        if self.scales is None:
+            return h.decode_qkv(xr, xd, ln1, eps, wqkv, self.k[li], self.v[li], rope[0], rope[1], self.pos, H, rope[2])
+        qkv, s = h.decode_gemv(xr, xd, ln1, eps, wqkv, 0)
+        return self.append(h, qkv, li, 1, H, rope), s
 
 
 def _top_k_logits(logits: Tensor, top_k: int | None) -> Tensor:
@@ -290,7 +351,6 @@ class DecodeSession:
         self.cache = KVCache(len(model.layers), batch, self.Hkv, self.max_len, self.D, self.device, p.dtype, ragged,
                              kv_dtype)
         self.fp8 = self.cache.fp8
-        self._deq = None  # fp8: one layer's bf16 K / V scratch for cache_attn (allocated by the first long window)
         self.fast = self._fast_ok()
         self.use_graph = use_graph and self.fast
         # ragged: per-sequence advance of the decode step (1 = active), static so that the captured graph reads it
@@ -326,10 +386,10 @@ class DecodeSession:
                 f.w2.weight.detach(), layer.ln1.eps,
             ))
         rope = self.model.layers[0].attn.rope
-        if rope is not None:
-            self._cos, self._sin = rope.cos.float().contiguous(), rope.sin.float().contiguous()
-        else:  # the kernels take empty tables and use_rope = False
-            self._cos = self._sin = torch.empty(0, device=self.device, dtype=torch.float32)
+        if rope is not None:  # (cos, sin, use_rope) as the kernels take them
+            self._rope = (rope.cos.float().contiguous(), rope.sin.float().contiguous(), True)
+        else:  # empty tables and use_rope = False
+            self._rope = (*[torch.empty(0, device=self.device, dtype=torch.float32)] * 2, False)
 
     def reset(self) -> None:
         self.cache.reset()
@@ -374,7 +434,7 @@ class DecodeSession:
         if not self.fast:
             out = self._forward_reference(ids, step, rows)
         elif not self.use_graph:
-            out = self._forward_fast(ids, prefill=False, step=self._step)
+            out = self._forward_fast(ids, "decode", step=self._step)
         else:
             if self._graph is None:
                 self._capture()
@@ -402,8 +462,7 @@ class DecodeSession:
                 out.append(self._forward_reference(ids[:, t0 : t0 + w], [w] * B, rows, all_logits=True))
                 c.advance(rows, [w] * B)
             return torch.cat(out, 1)
-        out = [self._forward_fast(ids[:, t0 : t0 + w], prefill=kind == "flash", cache=kind == "cache",
-                                  all_logits=True).view(B, w, -1)
+        out = [self._forward_fast(ids[:, t0 : t0 + w], kind, all_logits=True).view(B, w, -1)
                for t0, w, kind in _append_plan(T, self.H // self.Hkv, max(c._len) > 0, self.prefill_chunk, not self.fp8)]
         c.advance(rows, [T] * B)
         return out[0] if len(out) == 1 else torch.cat(out, 1)
@@ -454,10 +513,7 @@ class DecodeSession:
             # window, every token attending the cache plus its own causal prefix; a window of up to 8 / G tokens
             # (speculative verification) is one decode_attn step (_append_plan)
             plan = _append_plan(T, G, max(cur) > 0, self.prefill_chunk, not self.fp8)
-            b = rows[0]
-            kv = None if B == self.batch else (c.k[:, b : b + 1], c.v[:, b : b + 1], c.pos[b : b + 1])
-            if kv is not None and self.fp8:
-                kv += (c.k_scale[:, b : b + 1], c.v_scale[:, b : b + 1])
+            kv = None if B == self.batch else c.view(rows[0])
         out = None
         for t0, w, kind in plan:
             # sequence i advances by the part of its length that falls in the chunk, and its logits come from
@@ -471,8 +527,7 @@ class DecodeSession:
                 if min(part) < w:
                     step = torch.tensor(part, dtype=torch.int32).to(self.device)
                     last = torch.tensor([max(p - 1, 0) for p in part]).to(self.device)
-                lg = self._forward_fast(ids[:, t0 : t0 + w], prefill=kind == "flash", step=step, last=last, kv=kv,
-                                        cache=kind == "cache")
+                lg = self._forward_fast(ids[:, t0 : t0 + w], kind, step=step, last=last, kv=kv)
             here = [i for i, p in enumerate(part) if p]  # sequences with a valid token in this chunk
             if len(here) == B:
                 out = lg
@@ -585,7 +640,7 @@ class DecodeSession:
         st["params"] = key
         if self.use_graph and st["key"] != key:
             def run():
-                logits = self._forward_fast(st["ids"], prefill=False, step=self._step)
+                logits = self._forward_fast(st["ids"], "decode", step=self._step)
                 sampling.sample_step(logits, *key[:3], st["rng"], st["ids"], st["out"], st["step"], st["done"], eos)
                 st["rng"][1:].add_(1)
 
@@ -612,7 +667,7 @@ class DecodeSession:
             return
         step = st["step"]
         if self.fast:
-            logits = self._forward_fast(st["ids"], prefill=False, step=self._step)
+            logits = self._forward_fast(st["ids"], "decode", step=self._step)
         else:  # the oracle math reads host lengths: the step comes back per token (no graph to keep fed here)
             rows = list(range(self.batch))
             n = [1] * self.batch if step is None else [int(x) for x in step.tolist()]
@@ -695,54 +750,38 @@ class DecodeSession:
         s = torch.cuda.Stream(device=self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):
-            self._forward_fast(self._static_ids, prefill=False, step=self._step)
+            self._forward_fast(self._static_ids, "decode", step=self._step)
         torch.cuda.current_stream(self.device).wait_stream(s)
         self.cache.pos.copy_(pos0)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self._static_logits = self._forward_fast(self._static_ids, prefill=False, step=self._step)
+            self._static_logits = self._forward_fast(self._static_ids, "decode", step=self._step)
         self.cache.pos.copy_(pos0)  # capture does not execute, but keep the invariant explicit
         self._graph = g
 
-    def _operands(self, kv):
-        """What both fast forwards run on: the HIP ops, (k, v, pos) -- ``kv`` or the whole cache -- and RoPE tables."""
+    def _hip(self):
+        """The HIP ops handle both fast forwards run on (the one seam: a test substitutes a spy here)."""
         from ..ops._ext import ops as hip
 
-        c = self.cache
-        return (hip(), *(kv[:3] if kv else (c.k, c.v, c.pos)), self._cos, self._sin, self._cos.numel() > 0)
+        return hip()
 
-    def _scales(self, kv):
-        """fp8: the (k_scale, v_scale) that go with ``_operands(kv)``'s (k, v)."""
-        return kv[3:] if kv else (self.cache.k_scale, self.cache.v_scale)
-
-    def _dequant_scratch(self, n: int):
-        """fp8: bf16 K / V ``[n, Hkv, Lmax, D]`` that ``kv_dequant`` fills for ``cache_attn``, one layer's worth,
-        reused by every layer.  Zero-filled once, so rows that were never written are finite, as in a bf16 cache."""
-        if self._deq is None:
-            shape = (self.batch, self.Hkv, self.max_len, self.D)
-            self._deq = tuple(torch.zeros(shape, device=self.device, dtype=torch.bfloat16) for _ in range(2))
-        return self._deq[0][:n], self._deq[1][:n]
-
-    def _forward_fast(self, ids: Tensor, prefill: bool, step: Tensor | None = None, last: Tensor | None = None,
-                      kv=None, cache: bool = False, all_logits: bool = False, advance: bool = True) -> Tensor:
-        """``prefill``: flash attention inside the window (empty cache); ``cache``: ``cache_attn`` over the cache
-        instead of ``decode_attn`` (a window of more than ``8 / G`` tokens); ``step``: device int32 advance per sequence instead of ``T``; ``last``: index of the token whose logits
-        each sequence returns instead of ``T - 1`` (both only where the sequences differ); ``kv``: the (k, v, pos)
-        to run on -- one slot's views of the cache instead of the whole; ``all_logits``: the logits of every position,
-        ``[B * T, V]``, instead of the last one's; ``advance=False`` leaves the position where it was (a speculative
-        round sets it after the verification)."""
-        if not prefill and ids.shape[1] == 1 and not all_logits and ids.shape[0] <= _GEMV_MAX_BATCH and self._gemv_fits(ids.shape[0]):
+    def _forward_fast(self, ids: Tensor, kind: str, step: Tensor | None = None, last: Tensor | None = None,
+                      kv: KVView | None = None, all_logits: bool = False, advance: bool = True) -> Tensor:
+        """``kind`` (``_append_plan``): ``"flash"``, flash attention inside the window (empty cache); ``"cache"``,
+        ``cache_attn`` over the cache (a window of more than ``8 / G`` tokens); ``"decode"``, ``decode_attn``.
+        ``step``: device int32 advance per sequence instead of ``T``; ``last``: index of the token whose logits
+        each sequence returns instead of ``T - 1`` (both only where the sequences differ); ``kv``: the view to run
+        on -- one slot's instead of the whole cache's; ``all_logits``: the logits of every position, ``[B * T, V]``,
+        instead of the last one's; ``advance=False`` leaves the position where it was (a speculative round sets it
+        after the verification)."""
+        kv = kv or self.cache.view()
+        if kind == "decode" and ids.shape[1] == 1 and not all_logits and ids.shape[0] <= _GEMV_MAX_BATCH and self._gemv_fits(ids.shape[0]):
             return self._decode_gemv(ids, step, kv)
-        h, kc, vc, pos, cos, sin, use_rope = self._operands(kv)
+        assert kind != "flash" or not self.fp8, "an fp8 session attends to the cache as stored (no flash prefill)"
+        h, rope = self._hip(), self._rope
         m = self.model
         B, T = ids.shape
         H, Hkv, D = self.H, self.Hkv, self.D
-        scale = 1.0 / math.sqrt(D)
-        if self.fp8:
-            assert not prefill, "an fp8 session attends to the cache as stored (no flash prefill)"
-            ksc, vsc = self._scales(kv)
-            if cache:
-                kd, vd = self._dequant_scratch(B)
         xr = m.token_embeddings(ids).reshape(B * T, -1)
         xd = None
         for li, (ln1, wqkv, wo, ln2, w13, w2, eps) in enumerate(self._w):
@@ -751,23 +790,12 @@ class DecodeSession:
             else:
                 xr, h1, _ = h.add_rmsnorm_fwd(xr, xd, ln1, eps)
             qkv = torch.matmul(h1, wqkv.t())
-            if prefill:
+            if kind == "flash":
                 q, k, v = qkv[:, : H * D], qkv[:, H * D : (H + Hkv) * D], qkv[:, (H + Hkv) * D :]
-                o, _ = h.fa_fwd(q, k, v, cos, sin, B, T, H, Hkv, D, True, use_rope, scale)
-                h.kv_append(qkv, kc[li], vc[li], cos, sin, pos, B, T, H, use_rope)
-            elif self.fp8:
-                q = h.kv_append_fp8(qkv, kc[li], vc[li], ksc[li], vsc[li], cos, sin, pos, B, T, H, use_rope)
-                if cache:
-                    h.kv_dequant(kc[li], vc[li], ksc[li], vsc[li], pos, T, kd, vd)
-                    o = h.cache_attn(q, kd, vd, pos, H, scale, T)
-                else:
-                    o = h.decode_attn_fp8(q, kc[li], vc[li], ksc[li], vsc[li], pos, H, scale, True, T)
+                o, _ = h.fa_fwd(q, k, v, rope[0], rope[1], B, T, H, Hkv, D, True, rope[2], 1.0 / math.sqrt(D))
+                kv.append(h, qkv, li, T, H, rope)
             else:
-                q = h.kv_append(qkv, kc[li], vc[li], cos, sin, pos, B, T, H, use_rope)
-                if cache:
-                    o = h.cache_attn(q, kc[li], vc[li], pos, H, scale, T)
-                else:
-                    o = h.decode_attn(q, kc[li], vc[li], pos, H, scale, True, T)
+                o = kv.attend(h, kv.append(h, qkv, li, T, H, rope), li, T, H, kind)
             g1 = torch.matmul(o, wo.t())
             xr, h2, _ = h.add_rmsnorm_fwd(xr, g1, ln2, eps)
             a = h.swiglu_fwd(torch.matmul(h2, w13.t()))
@@ -785,46 +813,36 @@ class DecodeSession:
         _, hf, _ = h.add_rmsnorm_fwd(xr, xd, fin.weight, fin.eps)
         logits = torch.matmul(hf, m.lm_head.weight.t())
         if advance:
-            pos.add_(T if step is None else step)
+            kv.pos.add_(T if step is None else step)
         return logits
 
     def _gemv_fits(self, m: int) -> bool:
         cfg = self.model.config
         return all(_gemv_ok(m, k) for k in (cfg.d_model, self.H * self.D, self._w[0][5].shape[1]))
 
-    def _decode_gemv(self, ids: Tensor, step: Tensor | None = None, kv=None) -> Tensor:
+    def _decode_gemv(self, ids: Tensor, step: Tensor | None, kv: KVView) -> Tensor:
         """Decode step for batch <= 16 on the fused skinny-GEMM kernels (``csrc/decode_gemv.hip``): per layer
         qkv (+RMSNorm, +RoPE, +cache write) -> split-K decode attention -> Wo (+ the split combine) -> [W1; W3]
         (+residual add, +RMSNorm, +SwiGLU) -> W2; the residual add of W2's output is folded into the next layer's
         QKV prologue: 5 launches per layer.  An fp8 cache takes 6: the QKV projection with the plain epilogue, then
         ``kv_append_fp8`` (RoPE, quantisation, cache write), and ``decode_attn_fp8``."""
-        h, kc, vc, pos, cos, sin, use_rope = self._operands(kv)
+        h, rope = self._hip(), self._rope
         m = self.model
         H = self.H
         B = ids.shape[0]
-        scale = 1.0 / math.sqrt(self.D)
-        if self.fp8:
-            ksc, vsc = self._scales(kv)
         xr = m.token_embeddings(ids).reshape(B, -1)
         xd = None
         for li, (ln1, wqkv, wo, ln2, w13, w2, eps) in enumerate(self._w):
-            if self.fp8:
-                qkv, s = h.decode_gemv(xr, xd, ln1, eps, wqkv, 0)
-                q = h.kv_append_fp8(qkv, kc[li], vc[li], ksc[li], vsc[li], cos, sin, pos, B, 1, H, use_rope)
-            else:
-                q, s = h.decode_qkv(xr, xd, ln1, eps, wqkv, kc[li], vc[li], cos, sin, pos, H, use_rope)
+            q, s = kv.decode_qkv(h, xr, xd, ln1, eps, wqkv, li, H, rope)
             if xd is not None:
                 xr = s
-            if self.fp8:
-                part = h.decode_attn_fp8(q, kc[li], vc[li], ksc[li], vsc[li], pos, H, scale, False)
-            else:
-                part = h.decode_attn(q, kc[li], vc[li], pos, H, scale, False)
+            part = kv.attend(h, q, li, 1, H, "decode", combine=False)
             g1 = h.decode_attn_proj(part, wo)  # the flash-decoding combine runs in Wo's prologue
             a, xr = h.decode_gemv(xr, g1, ln2, eps, w13, 1)
             xd, _ = h.decode_gemv(a, None, None, 0.0, w2, 0)
         fin = m.ln_final
         logits, _ = h.decode_gemv(xr, xd, fin.weight, fin.eps, m.lm_head.weight, 0)
-        pos.add_(1 if step is None else step)
+        kv.pos.add_(1 if step is None else step)
         return logits
 
     # ------------------------------------------------------------------ oracle path
@@ -937,7 +955,7 @@ class SpeculativeSession:
         if self.fast:  # the target's window must be one pass over the layers (no position moves inside the round)
             plan = _append_plan(K + 1, t.H // t.Hkv, True)
             assert len(plan) == 1, plan
-            self._win_cache = plan[0][2] == "cache"
+            self._win_kind = plan[0][2]
         i32 = dict(dtype=torch.int32, device=dev)
         self._st = {
             "win": torch.zeros(batch, K + 1, dtype=torch.long, device=dev),
@@ -956,7 +974,7 @@ class SpeculativeSession:
     def _decode_draft(self) -> Tensor:
         d, st = self.draft, self._st
         if d.fast:
-            return d._forward_fast(st["ids"], prefill=False, step=st["step_d"])
+            return d._forward_fast(st["ids"], "decode", step=st["step_d"])
         rows = list(range(self.batch))
         n = [int(x) for x in st["step_d"].tolist()]
         logits = d._forward_reference(st["ids"], n, rows)
@@ -967,8 +985,7 @@ class SpeculativeSession:
         t, st = self.target, self._st
         B, K = self.batch, self.K
         if t.fast:
-            return t._forward_fast(st["win"], prefill=False, cache=self._win_cache, all_logits=True,
-                                   advance=False).view(B, K + 1, -1)
+            return t._forward_fast(st["win"], self._win_kind, all_logits=True, advance=False).view(B, K + 1, -1)
         return t._forward_reference(st["win"], [0] * B, list(range(B)), all_logits=True)  # (0: no advance)
 
     def _round(self, temperature: float, eos: int, out: Tensor) -> None:

@@ -25,11 +25,32 @@
 //      small-batch decode step skips the combine launch: the output projection's prologue merges the partials
 //      (decode_gemv.hip, GemvArgs::part).
 // All of a chunk's K and V loads are issued at kernel entry (register-resident, <= 128 VGPRs at D = 128).
-#include "common.h"
+//
+// One kernel body serves both cache formats (kv_cache.h): the bf16 cache above, and the fp8 cache of kv_fp8.hip, e4m3
+// rows k8 / v8 [B, Hkv, Lmax, D] with one power-of-two fp32 scale each, ks / vs [B, Hkv, Lmax] -- half the bytes
+// per key: a thread loads its key's D bytes in D / 16 16-byte loads plus one scale, and 8 bytes per (key, 8-wide d)
+// of V.  k_scale[t] multiplies the score, v_scale[t] the probability p[r][t] (the row sum l takes the unscaled p).
+// Chunking, the empty-chunk rule, the partials layout and the combine do not depend on the format
+// (decode_combine_kernel and decode_attn_proj consume the partials of either).
+//
+// kv_append_kernel writes the bf16 cache; its fp8 counterpart (kv_fp8.hip) shares the index / RoPE prologue
+// (kv_cache.h, append_vec), so both return the same q.
+//
+// Resources (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage), scratch 0 in every kernel; MR 1 / 2 / 4 / 8:
+//   decode_attn_kernel<64, MR, Bf16Cache>   VGPRs 90 / 107 / 122 / 180   SGPRs 47 / 51 / 51 / 56   waves/SIMD 5 / 4 / 4 / 2
+//   decode_attn_kernel<128, MR, Bf16Cache>  VGPRs 154 / 168 / 200 / 242  SGPRs 61 / 67 / 72 / 66   waves/SIMD 3 / 3 / 2 / 2
+//   decode_attn_kernel<64, MR, Fp8Cache>    VGPRs 62 / 80 / 96 / 180     SGPRs 47 / 51 / 51 / 56   waves/SIMD 8 / 6 / 5 / 2
+//   decode_attn_kernel<128, MR, Fp8Cache>   VGPRs 94 / 112 / 120 / 180   SGPRs 61 / 67 / 72 / 66   waves/SIMD 5 / 4 / 4 / 2
+//   LDS bytes, either format: D 64: 2336 / 4640 / 9248 / 18464, D 128: 3616 / 7200 / 14368 / 28704
+//   kv_append_kernel VGPRs 44, SGPRs 69   kv_append_fp8_kernel VGPRs 44, SGPRs 79   kv_dequant_kernel VGPRs 29   (8 waves)
+// The format's scale loads and multiplies exist only in the Fp8Cache instantiations (`if constexpr`).
+#include "kv_cache.h"
 #include "kernels.h"
 
 namespace bpe {
 namespace dec {
+
+using namespace kvc;
 
 constexpr int CH = 256;  // keys per chunk (= threads per workgroup)
 
@@ -37,13 +58,21 @@ constexpr int CH = 256;  // keys per chunk (= threads per workgroup)
 // must be statically indexed (guide §5.4 rule 20: runtime-indexed register arrays go to scratch).  Row r is
 // new token t = r / G of the sequence and query head g = r % G of the kv head; with T new tokens at positions
 // p0 .. p0 + T - 1 (p0 = *pos, already in the cache), token t attends keys [0, p0 + t] (causal within the chunk).
-template <int D, int MR>
-__global__ void __launch_bounds__(256) decode_attn_kernel(const __bf16* __restrict__ q, const __bf16* __restrict__ Kc,
-                                                          const __bf16* __restrict__ Vc, float* __restrict__ part,
+// Fmt (kv_cache.h) is the cache format; Ks / Vs are read only where it has scales (null otherwise).  Both formats
+// run the same floating-point operations in the same order on the unpacked values; a key's scale multiplies its
+// finished score, a value's scale its probability, and no bf16 instruction sees either.
+template <int D, int MR, class Fmt>
+__global__ void __launch_bounds__(256) decode_attn_kernel(const __bf16* __restrict__ q, const void* __restrict__ Kc,
+                                                          const void* __restrict__ Vc, const float* __restrict__ Ks,
+                                                          const float* __restrict__ Vs, float* __restrict__ part,
                                                           const int* __restrict__ pos, int pstride, int H, int Hkv,
                                                           int Lmax, int nsplit, float scale, int T) {
-    constexpr int DV = D / 8;     // 16-byte vectors per row
-    constexpr int KP = 256 / DV;  // key partitions of the P.V step
+    typedef typename Fmt::elem elem;
+    typedef typename Fmt::KVec KVec;
+    typedef typename Fmt::VVec VVec;
+    constexpr int DV = D / 8;        // 8-element vectors per row
+    constexpr int NK = D / Fmt::KE;  // 16-byte registers of a key row
+    constexpr int KP = 256 / DV;     // key partitions of the P.V step
     __shared__ float qs[MR][D];
     __shared__ float ps[MR][CH];
     __shared__ float red[2][4];
@@ -68,22 +97,29 @@ __global__ void __launch_bounds__(256) decode_attn_kernel(const __bf16* __restri
         return;
     }
     const int n = min(CH, L - s0);
-    const long kvbase = ((long)bk * Lmax + s0) * D;
+    const long rowbase = (long)bk * Lmax + s0;  // first cache row of the chunk (its scale is at rowbase)
+    const long kvbase = rowbase * D;            // and its first element
     // every K and V load of the chunk is issued up front (latency-bound at small batch: the q staging, the
-    // score reductions and the softmax run while they are in flight)
+    // score reductions and the softmax run while they are in flight): the key's row (and scale), the value scale of
+    // key tid (folded into p below), and the V elements of this thread's (key partition, d vector) slots
     const bool ok = tid < n;
-    u16x8 kr[DV];
+    KVec kr[NK];
     {
-        const u16x8* kp = reinterpret_cast<const u16x8*>(Kc + kvbase + (long)tid * D);
+        const KVec* kp = reinterpret_cast<const KVec*>(Fmt::row(Kc, rowbase, tid, D));
 #pragma unroll
-        for (int v = 0; v < DV; ++v) kr[v] = ok ? kp[v] : u16x8{};
+        for (int v = 0; v < NK; ++v) kr[v] = ok ? kp[v] : KVec{};
+    }
+    [[maybe_unused]] float ksc = 0.f, vsc = 0.f;
+    if constexpr (Fmt::scaled) {
+        ksc = ok ? Ks[rowbase + tid] : 0.f;
+        vsc = ok ? Vs[rowbase + tid] : 0.f;
     }
     const int dv = tid % DV, kp = tid / DV;
-    u16x8 vr[CH / KP];
+    VVec vr[CH / KP];
 #pragma unroll
     for (int j = 0; j < CH / KP; ++j) {
         const int t = kp + KP * j;
-        vr[j] = t < n ? *reinterpret_cast<const u16x8*>(Vc + kvbase + (long)t * D + dv * 8) : u16x8{};
+        vr[j] = t < n ? *reinterpret_cast<const VVec*>(Fmt::row(Vc, rowbase, t, D) + dv * 8) : VVec{};
     }
     // query rows -> LDS (fp32, pre-scaled); rows >= R are zero
     for (int e = tid; e < MR * D; e += 256) {
@@ -93,29 +129,32 @@ __global__ void __launch_bounds__(256) decode_attn_kernel(const __bf16* __restri
                          : 0.f;
     }
     __syncthreads();
-    // 1. scores (key s0 + tid is visible to row r iff it is <= p0 + r / G)
+    // 1. scores: (sum_d q_d k_d) [* k_scale], d ascending (key s0 + tid is visible to row r iff it is <= p0 + r / G)
     {
         float s[MR];
 #pragma unroll
         for (int r = 0; r < MR; ++r) s[r] = 0.f;
         if (ok) {
 #pragma unroll
-            for (int v = 0; v < DV; ++v) {
-                const u16x8 t = kr[v];
+            for (int d = 0; d < D; d += Fmt::GR) {
+                float kx[Fmt::GR];
 #pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const float kx = bf2f(t[j]);
+                for (int i = 0; i < Fmt::GR; ++i) kx[i] = Fmt::key(kr, d + i);
 #pragma unroll
-                    for (int r = 0; r < MR; ++r) s[r] += qs[r][8 * v + j] * kx;
-                }
+                for (int r = 0; r < MR; ++r)
+#pragma unroll
+                    for (int i = 0; i < Fmt::GR; ++i) s[r] += qs[r][d + i] * kx[i];
             }
         }
         const int key = s0 + tid;
 #pragma unroll
-        for (int r = 0; r < MR; ++r) ps[r][tid] = (ok && key <= p0 + r / G) ? s[r] : -INFINITY;
-    }
-    __syncthreads();
-    // 2. per-row max / exp / sum over the chunk (a row with no visible key here: m = -inf, p = 0)
+        for (int r = 0; r < MR; ++r) {
+            if constexpr (Fmt::scaled) s[r] *= ksc;
+            ps[r][tid] = (ok && key <= p0 + r / G) ? s[r] : -INFINITY;
+        }
+    }    __syncthreads();
+    // 2. per-row max / exp / sum over the chunk (a row with no visible key here: m = -inf, p = 0); with scales ps
+    // takes p * v_scale, the sum l the plain p
     float mg[MR], lg[MR];
 #pragma unroll
     for (int r = 0; r < MR; ++r) {
@@ -124,7 +163,8 @@ __global__ void __launch_bounds__(256) decode_attn_kernel(const __bf16* __restri
         __syncthreads();
         m = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
         const float p = (tid < n && m != -INFINITY) ? __expf(ps[r][tid] - m) : 0.f;
-        ps[r][tid] = p;
+        if constexpr (Fmt::scaled) ps[r][tid] = p * vsc;
+        else ps[r][tid] = p;
         float sm = wave_sum(p);
         if (lane == 0) red[1][wv] = sm;
         __syncthreads();
@@ -142,12 +182,12 @@ __global__ void __launch_bounds__(256) decode_attn_kernel(const __bf16* __restri
     for (int jj = 0; jj < CH / KP; ++jj) {
         const int t = kp + KP * jj;
         if (t >= n) break;
-        const u16x8 vv = vr[jj];
+        const VVec vv = vr[jj];
 #pragma unroll
         for (int r = 0; r < MR; ++r) {
             const float p = ps[r][t];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) acc[r][j] += p * bf2f(vv[j]);
+            for (int j = 0; j < 8; ++j) acc[r][j] += p * Fmt::val(vv, j);
         }
     }
     // lanes that share dv differ by multiples of DV: butterfly over the wave's key partitions
@@ -199,39 +239,22 @@ __global__ void __launch_bounds__(D) decode_combine_kernel(const float* __restri
     reinterpret_cast<u16*>(out)[bh * D + d] = f2bf(Lsum > 0.f ? o / Lsum : 0.f);
 }
 
-// KV-cache append: fused-QKV rows [B*T, (H + 2*Hkv)*D] of T new tokens per sequence at positions
-// *pos .. *pos+T-1 -> RoPE'd q [B*T, H*D] and roped K / plain V written into the caches [B, Hkv, Lmax, D].
-// One thread per 16-byte vector (8 bf16); the rotation pairs (2i, 2i+1) never straddle a vector.
+// KV-cache append into the bf16 cache: append_vec's (kv_cache.h) vector goes to q [B*T, H*D] or, roped K / plain V,
+// into the caches [B, Hkv, Lmax, D].
 __global__ void __launch_bounds__(256) kv_append_kernel(const __bf16* __restrict__ qkv, long ld,
                                                         __bf16* __restrict__ qo, __bf16* __restrict__ Kc,
                                                         __bf16* __restrict__ Vc, const float* __restrict__ cosT,
                                                         const float* __restrict__ sinT, const int* __restrict__ pos,
                                                         int pstride, int T, int H, int Hkv, int D, int Lmax,
                                                         long total) {
-    const int dv = D / 8, W = (H + 2 * Hkv) * dv;
     const int pshared = pos[0];
     for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
-        const long r = idx / W;
-        const int c = (int)(idx % W), hh = c / dv, d0 = (c % dv) * 8;
-        const int b = (int)(r / T);
-        const int p = (pstride ? pos[b] : pshared) + (int)(r % T);  // per sequence, and so is the drop below
-        if (p >= Lmax) continue;  // cache full: nothing is written past the end
-        u16x8 x = *reinterpret_cast<const u16x8*>(qkv + r * ld + (long)hh * D + d0);
-        if (hh < H + Hkv && cosT != nullptr) {
-            const float* cs = cosT + (long)p * (D / 2) + d0 / 2;
-            const float* sn = sinT + (long)p * (D / 2) + d0 / 2;
-#pragma unroll
-            for (int j = 0; j < 8; j += 2) {
-                const float x1 = bf2f(x[j]), x2 = bf2f(x[j + 1]), cc = cs[j / 2], ss = sn[j / 2];
-                x[j] = f2bf(x1 * cc - x2 * ss);
-                x[j + 1] = f2bf(x1 * ss + x2 * cc);
-            }
-        }
+        AppendVec a;
+        if (!append_vec(a, idx, total, qkv, ld, cosT, sinT, pos, pstride, pshared, T, H, Hkv, D, Lmax)) continue;
         __bf16* dst;
-        if (hh < H) dst = qo + r * (long)H * D + (long)hh * D + d0;
-        else if (hh < H + Hkv) dst = Kc + (((long)b * Hkv + (hh - H)) * Lmax + p) * D + d0;
-        else dst = Vc + (((long)b * Hkv + (hh - H - Hkv)) * Lmax + p) * D + d0;
-        *reinterpret_cast<u16x8*>(dst) = x;
+        if (a.hh < H) dst = qo + a.r * (long)H * D + (long)a.hh * D + a.d0;
+        else dst = (a.hh < H + Hkv ? Kc : Vc) + a.row * D + a.d0;
+        *reinterpret_cast<u16x8*>(dst) = a.x;
     }
 }
 
@@ -248,15 +271,16 @@ bool decode_attn_ok(int H, int Hkv, int D, int T) {
     return (D == 64 || D == 128) && Hkv > 0 && H % Hkv == 0 && T >= 1 && G >= 1 && G * T <= 8;
 }
 
-template <int D>
-static void launch_d(const void* q, const void* k, const void* v, float* part, void* out, const int* pos,
-                     int pstride, int B, int T, int H, int Hkv, int Lmax, float scale, hipStream_t s) {
+template <int D, class Fmt>
+static void launch_d(const void* q, const void* k, const void* v, const float* ks, const float* vs, float* part,
+                     void* out, const int* pos, int pstride, int B, int T, int H, int Hkv, int Lmax, float scale,
+                     hipStream_t s) {
     const int ns = decode_attn_splits(Lmax);
     const int grid = B * Hkv * ns;
     const int R = (H / Hkv) * T;
 #define DEC(MR)                                                                                                   \
-    decode_attn_kernel<D, MR><<<grid, 256, 0, s>>>((const __bf16*)q, (const __bf16*)k, (const __bf16*)v, part, pos, \
-                                                   pstride, H, Hkv, Lmax, ns, scale, T)
+    decode_attn_kernel<D, MR, Fmt><<<grid, 256, 0, s>>>((const __bf16*)q, k, v, ks, vs, part, pos, pstride, H, Hkv, \
+                                                        Lmax, ns, scale, T)
     if (R <= 1) DEC(1);
     else if (R <= 2) DEC(2);
     else if (R <= 4) DEC(4);
@@ -265,16 +289,12 @@ static void launch_d(const void* q, const void* k, const void* v, float* part, v
     if (out != nullptr) decode_combine_kernel<D><<<B * T * H, D, 0, s>>>(part, (__bf16*)out, ns);
 }
 
-// the combine alone: `rows` = B * T * H partial rows [nsplit][D + 2] -> bf16 out [rows][D] (kv_fp8.hip's decode step)
-void launch_decode_combine(const float* part, void* out, int rows, int D, int nsplit, hipStream_t s) {
-    if (D == 64) decode_combine_kernel<64><<<rows, 64, 0, s>>>(part, (__bf16*)out, nsplit);
-    else decode_combine_kernel<128><<<rows, 128, 0, s>>>(part, (__bf16*)out, nsplit);
-}
-
-void launch_decode_attn(const void* q, const void* k, const void* v, float* part, void* out, const int* pos,
-                        int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax, float scale, hipStream_t s) {
-    if (D == 64) launch_d<64>(q, k, v, part, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, s);
-    else launch_d<128>(q, k, v, part, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, s);
+void launch_decode_attn(const void* q, const void* k, const void* v, const float* ks, const float* vs, float* part,
+                        void* out, const int* pos, int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax,
+                        float scale, hipStream_t s) {
+    const auto launch = ks != nullptr ? (D == 64 ? launch_d<64, Fp8Cache> : launch_d<128, Fp8Cache>)
+                                      : (D == 64 ? launch_d<64, Bf16Cache> : launch_d<128, Bf16Cache>);
+    launch(q, k, v, ks, vs, part, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, s);
 }
 
 void launch_kv_append(const void* qkv, long ld, void* qo, void* Kc, void* Vc, const float* cosT, const float* sinT,

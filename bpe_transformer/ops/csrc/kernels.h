@@ -141,23 +141,21 @@ struct FaArgs {
     const int* doc_end;
 };
 // decode_attn.hip (KV-cache serving path; `pos` = device int32 position of the first new token: sequence b reads
-// pos[b * pos_stride], i.e. pos_stride 0 = one position shared by the batch, 1 = one per sequence)
+// pos[b * pos_stride], i.e. pos_stride 0 = one position shared by the batch, 1 = one per sequence).
+// launch_decode_attn serves both cache formats: ks / vs null = bf16 K / V [B, Hkv, Lmax, D]; otherwise k / v are
+// e4m3 bytes of that shape with one power-of-two fp32 scale per row, ks / vs [B, Hkv, Lmax] (kv_fp8.hip).
 int decode_attn_splits(int Lmax);
 bool decode_attn_ok(int H, int Hkv, int D, int T);
-void launch_decode_attn(const void* q, const void* k, const void* v, float* part, void* out, const int* pos,
-                        int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax, float scale, hipStream_t s);
+void launch_decode_attn(const void* q, const void* k, const void* v, const float* ks, const float* vs, float* part,
+                        void* out, const int* pos, int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax,
+                        float scale, hipStream_t s);
 void launch_kv_append(const void* qkv, long ld, void* qo, void* Kc, void* Vc, const float* cosT, const float* sinT,
                       const int* pos, int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax, hipStream_t s);
-void launch_decode_combine(const float* part, void* out, int rows, int D, int nsplit, hipStream_t s);
-// kv_fp8.hip (the fp8 KV cache: e4m3 bytes k8 / v8 [B, Hkv, Lmax, D] with one power-of-two fp32 scale per row,
-// ks / vs [B, Hkv, Lmax]; the contracts of launch_kv_append / launch_decode_attn otherwise).  launch_kv_dequant
-// writes rows [0, min(pos + T, Lmax)) of every K and V slab as bf16 into ko / vo [B, Hkv, Lmax, D].
+// kv_fp8.hip (the fp8 KV cache; the contract of launch_kv_append otherwise).  launch_kv_dequant writes rows
+// [0, min(pos + T, Lmax)) of every K and V slab as bf16 into ko / vo [B, Hkv, Lmax, D].
 void launch_kv_append_fp8(const void* qkv, long ld, void* qo, void* k8, void* v8, float* ks, float* vs,
                           const float* cosT, const float* sinT, const int* pos, int pos_stride, int B, int T, int H,
                           int Hkv, int D, int Lmax, hipStream_t s);
-void launch_decode_attn_fp8(const void* q, const void* k8, const void* v8, const float* ks, const float* vs,
-                            float* part, void* out, const int* pos, int pos_stride, int B, int T, int H, int Hkv,
-                            int D, int Lmax, float scale, hipStream_t s);
 void launch_kv_dequant(const void* k8, const void* v8, const float* ks, const float* vs, void* ko, void* vo,
                        const int* pos, int pos_stride, int B, int T, int Hkv, int D, int Lmax, hipStream_t s);
 // flash_attn_cache.hip (flash prefill over the cache: T new tokens per sequence, any T; `pos` as above)

@@ -1,0 +1,108 @@
+// What the two KV-cache formats of the serving path share, and the little in which they differ (gfx950).
+//
+//   bf16   K / V [B, Hkv, Lmax, D] bf16 (K roped)
+//   fp8    the same rows as D e4m3 bytes plus one power-of-two fp32 scale per row, ks / vs [B, Hkv, Lmax]
+//          (kv_fp8.hip states the format)
+//
+// decode_attn_kernel (decode_attn.hip) is written once against a format policy -- Bf16Cache / Fp8Cache below: the
+// register types of a key row and of a V slot, where a row starts, element d of either as fp32, and whether a row
+// carries a scale.  The two append kernels (kv_append_kernel in decode_attn.hip, kv_append_fp8_kernel in kv_fp8.hip)
+// share append_vec: which 8 values a thread handles, RoPE'd, and where they go.
+#pragma once
+#include "common.h"
+
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+namespace bpe {
+namespace kvc {
+
+// two e4m3 bytes of `w` (the low or the high half) -> fp32 (v_cvt_pk_f32_fp8, exact)
+__device__ __forceinline__ f32x2 fp8x2(unsigned w, bool hi) {
+    return hi ? __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true) : __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
+}
+
+// A policy names the stored element (`elem`: a cache row is D of them), the 16-byte register of a key row (`KVec`,
+// KE elements) and the register that holds the 8 elements of a V slot (`VVec`); `key` / `val` give element d of a
+// key row / j of a V slot as fp32 (constant indices after unrolling; repeated conversions of one register fold).
+// `scaled`: a row has a scale, which the kernel loads and applies.
+// Two members are there for register allocation only (VGPR counts decide the occupancy here; decode_attn.hip's
+// table): `row`, the address of cache row rowbase + t in the association that instantiation allocates best with,
+// and `GR`, how many key elements the score loop converts before it runs over the query rows (a bf16 element is one
+// shift, an e4m3 word converts to four floats).  With the other format's choice of either, fp8 <64, 2> and <64, 4>
+// and bf16 <128, 2> each take a few more VGPRs and lose a wave per SIMD; no result depends on them.
+struct Bf16Cache {
+    static constexpr bool scaled = false;
+    typedef u16 elem;
+    typedef u16x8 KVec;
+    typedef u16x8 VVec;
+    static constexpr int KE = 8, GR = 1;
+    static __device__ __forceinline__ const elem* row(const void* c, long rowbase, int t, int D) {
+        return static_cast<const elem*>(c) + rowbase * D + (long)t * D;
+    }
+    static __device__ __forceinline__ float val(VVec v, int j) { return bf2f(v[j]); }
+    template <int N> static __device__ __forceinline__ float key(const KVec (&kr)[N], int d) {
+        return bf2f(kr[d / 8][d % 8]);
+    }
+};
+
+struct Fp8Cache {
+    static constexpr bool scaled = true;
+    typedef unsigned char elem;
+    typedef u32x4 KVec;
+    typedef u32x2 VVec;
+    static constexpr int KE = 16, GR = 4;
+    static __device__ __forceinline__ const elem* row(const void* c, long rowbase, int t, int D) {
+        return static_cast<const elem*>(c) + (rowbase + t) * D;
+    }
+    static __device__ __forceinline__ float byte(unsigned w, int i) { return fp8x2(w, i >= 2)[i % 2]; }
+    static __device__ __forceinline__ float val(VVec v, int j) { return byte(v[j / 4], j % 4); }
+    template <int N> static __device__ __forceinline__ float key(const KVec (&kr)[N], int d) {
+        return byte(kr[d / 16][(d % 16) / 4], d % 4);
+    }
+};
+
+// KV-cache append, the part both formats share.  Fused-QKV rows [B*T, (H + 2*Hkv)*D] (row stride ld) of T new tokens
+// per sequence at positions *pos .. *pos+T-1; one thread per 16-byte vector (8 bf16) of a row; the rotation pairs
+// (2i, 2i+1) never straddle a vector.  Vector `idx` of `total` is head hh (q heads, then K heads, then V heads) of
+// token row r, elements d0 .. d0 + 7, roped where q or K (cosT null: no RoPE), and, where K or V, belongs to cache
+// row `row` = (b * Hkv + kv head) * Lmax + position.
+struct AppendVec {
+    u16x8 x;
+    long r, row;
+    int hh, d0;
+};
+
+// -> false (a.x zero) when the thread has nothing to write: idx past the end, or the token's position at or past Lmax
+// (cache full: nothing is written past the end; per sequence, like the position itself).  `pshared` = pos[0].
+__device__ __forceinline__ bool append_vec(AppendVec& a, long idx, long total, const __bf16* __restrict__ qkv, long ld,
+                                           const float* __restrict__ cosT, const float* __restrict__ sinT,
+                                           const int* __restrict__ pos, int pstride, int pshared, int T, int H, int Hkv,
+                                           int D, int Lmax) {
+    a.x = u16x8{};
+    if (idx >= total) return false;
+    const int dv = D / 8, W = (H + 2 * Hkv) * dv;
+    a.r = idx / W;
+    const int c = (int)(idx % W);
+    a.hh = c / dv;
+    a.d0 = (c % dv) * 8;
+    const int b = (int)(a.r / T);
+    const int p = (pstride ? pos[b] : pshared) + (int)(a.r % T);
+    if (p >= Lmax) return false;
+    a.row = ((long)b * Hkv + (a.hh < H + Hkv ? a.hh - H : a.hh - H - Hkv)) * Lmax + p;
+    a.x = *reinterpret_cast<const u16x8*>(qkv + a.r * ld + (long)a.hh * D + a.d0);
+    if (a.hh < H + Hkv && cosT != nullptr) {
+        const float* cs = cosT + (long)p * (D / 2) + a.d0 / 2;
+        const float* sn = sinT + (long)p * (D / 2) + a.d0 / 2;
+#pragma unroll
+        for (int j = 0; j < 8; j += 2) {
+            const float x1 = bf2f(a.x[j]), x2 = bf2f(a.x[j + 1]), cc = cs[j / 2], ss = sn[j / 2];
+            a.x[j] = f2bf(x1 * cc - x2 * ss);
+            a.x[j + 1] = f2bf(x1 * ss + x2 * cc);
+        }
+    }
+    return true;
+}
+
+}  // namespace kvc
+}  // namespace bpe

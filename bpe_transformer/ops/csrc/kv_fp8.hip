@@ -13,194 +13,22 @@
 // score, a value's scale into its probability, without changing any rounding (barring underflow).
 //
 //   kv_append_fp8   kv_append_kernel (decode_attn.hip) with the K / V rows quantised: one thread per 8-element
-//                   vector, the D / 8 adjacent lanes of a row reduce the row's amax bits with lane shuffles (groups
-//                   are wave-aligned: 64 and 256 are multiples of D / 8), each lane stores its 8 bytes with one
-//                   vector store, lane 0 of the group stores the scale.  The roped q is that of kv_append, bit for bit.
-//   decode_attn_fp8 decode_attn_kernel with half the bytes per key: a thread loads its key's D bytes in D / 16
-//                   16-byte loads plus one fp32 scale, and 8 bytes per (key, 8-wide d) of V; every load is issued at
-//                   kernel entry.  k_scale[t] multiplies the score, v_scale[t] the probability p[r][t] (the row sum l
-//                   takes the unscaled p).  Partials layout, chunking, empty-chunk rule and combine are the bf16
-//                   kernel's (decode_combine_kernel and decode_attn_proj consume the partials unchanged).
+//                   vector (append_vec of kv_cache.h, shared with kv_append_kernel: the roped q is that of kv_append
+//                   by construction), the D / 8 adjacent lanes of a row reduce the row's amax bits with lane shuffles
+//                   (groups are wave-aligned: 64 and 256 are multiples of D / 8), each lane stores its 8 bytes with
+//                   one vector store, lane 0 of the group stores the scale.
 //   kv_dequant      rows [0, min(pos[b] + T, Lmax)) of each K and V slab -> bf16 scratch [B, Hkv, Lmax, D] (one
 //                   launch for both), rows past that untouched; pos is read on the device.  Feeds cache_attn for the
-//                   windows decode_attn_fp8 does not take (G * T >= 9).
-//
-// Resources (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage), scratch 0 in every kernel; the bf16
-// decode_attn_kernel next to it in brackets:
-//   decode_attn_fp8_kernel<64, MR>   MR 1 / 2 / 4 / 8:  VGPRs 62 / 80 / 96 / 180    (90 / 107 / 122 / 180)
-//   decode_attn_fp8_kernel<128, MR>  MR 1 / 2 / 4 / 8:  VGPRs 94 / 112 / 120 / 180  (154 / 168 / 200 / 242)
-//   kv_append_fp8_kernel  VGPRs 44     kv_dequant_kernel  VGPRs 29
-#include "common.h"
+//                   windows decode_attn does not take (G * T >= 9).
+// The decode attention over this cache is the Fp8Cache instantiation of decode_attn_kernel (decode_attn.hip, which
+// also holds the resource table of all these kernels).
+#include "kv_cache.h"
 #include "kernels.h"
-
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace bpe {
 namespace kv8 {
 
-constexpr int CH = 256;  // keys per chunk (= threads per workgroup), as decode_attn.hip
-
-// two e4m3 bytes of `w` (the low or the high half) -> fp32 (v_cvt_pk_f32_fp8, exact)
-__device__ __forceinline__ f32x2 fp8x2(unsigned w, bool hi) {
-    return hi ? __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true) : __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
-}
-
-// The decode_attn_kernel of decode_attn.hip (its comments hold here) reading the fp8 cache.  MR is a template
-// parameter for the same reason: per-row registers must be statically indexed.
-template <int D, int MR>
-__global__ void __launch_bounds__(256)
-decode_attn_fp8_kernel(const __bf16* __restrict__ q, const unsigned char* __restrict__ K8,
-                       const unsigned char* __restrict__ V8, const float* __restrict__ Ks,
-                       const float* __restrict__ Vs, float* __restrict__ part, const int* __restrict__ pos, int pstride,
-                       int H, int Hkv, int Lmax, int nsplit, float scale, int T) {
-    constexpr int DV = D / 8;     // 8-byte vectors per V row
-    constexpr int DK = D / 16;    // 16-byte vectors per K row
-    constexpr int KP = 256 / DV;  // key partitions of the P.V step
-    __shared__ float qs[MR][D];
-    __shared__ float ps[MR][CH];
-    __shared__ float red[2][4];
-    __shared__ float ob[4][MR][D];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int bk = blockIdx.x / nsplit, split = blockIdx.x % nsplit;  // bk = b * Hkv + hk
-    const int b = bk / Hkv, hk = bk % Hkv;
-    const int G = H / Hkv, R = G * T;
-    const int p0 = pos[b * pstride];
-    const int L = min(p0 + T, Lmax);
-    const int s0 = split * CH;
-    auto prow = [&](int r) {
-        return part + ((((long)b * T + r / G) * H + hk * G + r % G) * nsplit + split) * (D + 2);
-    };
-    if (s0 >= L) {  // uniform per workgroup: an empty chunk contributes nothing
-        if (tid < R) {
-            float* pr = prow(tid);
-            pr[D] = -INFINITY;
-            pr[D + 1] = 0.f;
-        }
-        return;
-    }
-    const int n = min(CH, L - s0);
-    const long rowbase = (long)bk * Lmax + s0;  // first cache row of the chunk: bytes at rowbase * D, scales at rowbase
-    // every load of the chunk is issued up front: the key's D bytes and scale, the value scale of key tid (folded
-    // into p below), and the V bytes of this thread's (key partition, d vector) slots
-    const bool ok = tid < n;
-    u32x4 kr[DK];
-    {
-        const u32x4* kp = reinterpret_cast<const u32x4*>(K8 + (rowbase + tid) * D);
-#pragma unroll
-        for (int v = 0; v < DK; ++v) kr[v] = ok ? kp[v] : u32x4{};
-    }
-    const float ksc = ok ? Ks[rowbase + tid] : 0.f;
-    const float vsc = ok ? Vs[rowbase + tid] : 0.f;
-    const int dv = tid % DV, kp = tid / DV;
-    u32x2 vr[CH / KP];
-#pragma unroll
-    for (int j = 0; j < CH / KP; ++j) {
-        const int t = kp + KP * j;
-        vr[j] = t < n ? *reinterpret_cast<const u32x2*>(V8 + (rowbase + t) * D + dv * 8) : u32x2{};
-    }
-    // query rows -> LDS (fp32, pre-scaled); rows >= R are zero
-    for (int e = tid; e < MR * D; e += 256) {
-        const int r = e / D, d = e % D;
-        qs[r][d] = r < R ? bf2f(reinterpret_cast<const u16*>(q)[((((long)b * T + r / G) * H) + hk * G + r % G) * D + d]) *
-                               scale
-                         : 0.f;
-    }
-    __syncthreads();
-    // 1. scores: (sum_d q_d k8_d) * k_scale (key s0 + tid is visible to row r iff it is <= p0 + r / G)
-    {
-        float s[MR];
-#pragma unroll
-        for (int r = 0; r < MR; ++r) s[r] = 0.f;
-        if (ok) {
-#pragma unroll
-            for (int v = 0; v < DK; ++v) {
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    const unsigned word = kr[v][w];
-                    const f32x2 lo = fp8x2(word, false), hi = fp8x2(word, true);
-                    const int d0 = 16 * v + 4 * w;
-#pragma unroll
-                    for (int r = 0; r < MR; ++r) {
-                        s[r] += qs[r][d0] * lo.x;
-                        s[r] += qs[r][d0 + 1] * lo.y;
-                        s[r] += qs[r][d0 + 2] * hi.x;
-                        s[r] += qs[r][d0 + 3] * hi.y;
-                    }
-                }
-            }
-        }
-        const int key = s0 + tid;
-#pragma unroll
-        for (int r = 0; r < MR; ++r) ps[r][tid] = (ok && key <= p0 + r / G) ? s[r] * ksc : -INFINITY;
-    }
-    __syncthreads();
-    // 2. per-row max / exp / sum over the chunk; ps takes p * v_scale, the sum l the plain p
-    float mg[MR], lg[MR];
-#pragma unroll
-    for (int r = 0; r < MR; ++r) {
-        float m = wave_max(ps[r][tid]);
-        if (lane == 0) red[0][wv] = m;
-        __syncthreads();
-        m = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
-        const float p = (tid < n && m != -INFINITY) ? __expf(ps[r][tid] - m) : 0.f;
-        ps[r][tid] = p * vsc;
-        float sm = wave_sum(p);
-        if (lane == 0) red[1][wv] = sm;
-        __syncthreads();
-        mg[r] = m;
-        lg[r] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-        __syncthreads();  // red[] reused by the next row
-    }
-    // 3. o[r][d] = sum_t (p[r][t] v_scale[t]) v8[t][d]; thread = (key partition kp, vector dv)
-    float acc[MR][8];
-#pragma unroll
-    for (int r = 0; r < MR; ++r)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[r][j] = 0.f;
-#pragma unroll
-    for (int jj = 0; jj < CH / KP; ++jj) {
-        const int t = kp + KP * jj;
-        if (t >= n) break;
-        const u32x2 vv = vr[jj];
-        const f32x2 v0 = fp8x2(vv.x, false), v1 = fp8x2(vv.x, true), v2 = fp8x2(vv.y, false), v3 = fp8x2(vv.y, true);
-        const float vf[8] = {v0.x, v0.y, v1.x, v1.y, v2.x, v2.y, v3.x, v3.y};
-#pragma unroll
-        for (int r = 0; r < MR; ++r) {
-            const float p = ps[r][t];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[r][j] += p * vf[j];
-        }
-    }
-    // lanes that share dv differ by multiples of DV: butterfly over the wave's key partitions
-#pragma unroll
-    for (int off = DV; off < 64; off <<= 1)
-#pragma unroll
-        for (int r = 0; r < MR; ++r)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc[r][j] += __shfl_xor(acc[r][j], off);
-    if (lane < DV) {
-#pragma unroll
-        for (int r = 0; r < MR; ++r)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) ob[wv][r][dv * 8 + j] = acc[r][j];
-    }
-    __syncthreads();
-    // 4. partial results per row: {o[D], m, l}
-    for (int e = tid; e < R * D; e += 256) {
-        const int r = e / D, dd = e % D;
-        prow(r)[dd] = ob[0][r][dd] + ob[1][r][dd] + ob[2][r][dd] + ob[3][r][dd];
-    }
-    if (tid < R) {  // the row statistics (registers, identical in every thread)
-        float m = mg[0], l = lg[0];
-#pragma unroll
-        for (int r = 1; r < MR; ++r)
-            if (tid == r) { m = mg[r]; l = lg[r]; }
-        float* pr = prow(tid);
-        pr[D] = m;
-        pr[D + 1] = l;
-    }
-}
+using namespace kvc;
 
 // Scale of a row from the largest |x| bits of its bf16 elements (integer order = magnitude order, and inf / NaN
 // sort above every finite value): -> s, and 1 / s in `inv`.
@@ -219,45 +47,28 @@ __device__ __forceinline__ float row_scale(unsigned amax16, float& inv) {
     return __uint_as_float((unsigned)sf << 23);
 }
 
-// kv_append_kernel with quantised K / V rows.  The loop bound is uniform per workgroup and every lane runs the
-// shuffles, so the D / 8 lanes of a row (same r, same head: all active or all skipped together) always find each
-// other; a lane with nothing to do carries zeros.
+// kv_append_kernel (decode_attn.hip) with quantised K / V rows.  The loop bound is uniform per workgroup and every
+// lane runs the shuffles, so the D / 8 lanes of a row (same r, same head: all active or all skipped together) always
+// find each other; a lane with nothing to do carries zeros.
 __global__ void __launch_bounds__(256)
 kv_append_fp8_kernel(const __bf16* __restrict__ qkv, long ld, __bf16* __restrict__ qo, unsigned char* __restrict__ K8,
                      unsigned char* __restrict__ V8, float* __restrict__ Ks, float* __restrict__ Vs,
                      const float* __restrict__ cosT, const float* __restrict__ sinT, const int* __restrict__ pos,
                      int pstride, int T, int H, int Hkv, int D, int Lmax, long total) {
-    const int dv = D / 8, W = (H + 2 * Hkv) * dv;
+    const int dv = D / 8;
     const int pshared = pos[0];
     for (long base = blockIdx.x * 256L; base < total; base += (long)gridDim.x * 256) {
-        const long idx = base + threadIdx.x;
-        const bool in = idx < total;
-        const long r = in ? idx / W : 0;
-        const int c = in ? (int)(idx % W) : 0, hh = c / dv, d0 = (c % dv) * 8;
-        const int b = (int)(r / T);
-        const int p = (pstride ? pos[b] : pshared) + (int)(r % T);
-        const bool act = in && p < Lmax;  // cache full: nothing is written past the end
-        u16x8 x = {};
-        if (act) {
-            x = *reinterpret_cast<const u16x8*>(qkv + r * ld + (long)hh * D + d0);
-            if (hh < H + Hkv && cosT != nullptr) {
-                const float* cs = cosT + (long)p * (D / 2) + d0 / 2;
-                const float* sn = sinT + (long)p * (D / 2) + d0 / 2;
-#pragma unroll
-                for (int j = 0; j < 8; j += 2) {
-                    const float x1 = bf2f(x[j]), x2 = bf2f(x[j + 1]), cc = cs[j / 2], ss = sn[j / 2];
-                    x[j] = f2bf(x1 * cc - x2 * ss);
-                    x[j + 1] = f2bf(x1 * ss + x2 * cc);
-                }
-            }
-        }
+        AppendVec a;
+        const bool act = append_vec(a, base + threadIdx.x, total, qkv, ld, cosT, sinT, pos, pstride, pshared, T, H,
+                                    Hkv, D, Lmax);
+        const u16x8 x = a.x;
         unsigned am = 0;
 #pragma unroll
         for (int j = 0; j < 8; ++j) am = max(am, (unsigned)(x[j] & 0x7fff));
         for (int off = 1; off < dv; off <<= 1) am = max(am, (unsigned)__shfl_xor((int)am, off));
         if (!act) continue;
-        if (hh < H) {
-            *reinterpret_cast<u16x8*>(qo + r * (long)H * D + (long)hh * D + d0) = x;
+        if (a.hh < H) {
+            *reinterpret_cast<u16x8*>(qo + a.r * (long)H * D + (long)a.hh * D + a.d0) = x;
             continue;
         }
         float inv;
@@ -267,10 +78,9 @@ kv_append_fp8_kernel(const __bf16* __restrict__ qkv, long ld, __bf16* __restrict
         w.x = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(bf2f(x[2]) * inv, bf2f(x[3]) * inv, (int)w.x, true);
         w.y = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(bf2f(x[4]) * inv, bf2f(x[5]) * inv, 0, false);
         w.y = (unsigned)__builtin_amdgcn_cvt_pk_fp8_f32(bf2f(x[6]) * inv, bf2f(x[7]) * inv, (int)w.y, true);
-        const bool isk = hh < H + Hkv;
-        const long row = ((long)b * Hkv + (isk ? hh - H : hh - H - Hkv)) * Lmax + p;
-        *reinterpret_cast<u32x2*>((isk ? K8 : V8) + row * D + d0) = w;
-        if (d0 == 0) (isk ? Ks : Vs)[row] = s;
+        const bool isk = a.hh < H + Hkv;
+        *reinterpret_cast<u32x2*>((isk ? K8 : V8) + a.row * D + a.d0) = w;
+        if (a.d0 == 0) (isk ? Ks : Vs)[a.row] = s;
     }
 }
 
@@ -313,32 +123,6 @@ kv_dequant_kernel(const unsigned char* __restrict__ K8, const unsigned char* __r
 }  // namespace bpe
 
 using namespace bpe::kv8;
-
-template <int D>
-static void launch_d(const void* q, const void* k8, const void* v8, const float* ks, const float* vs, float* part,
-                     void* out, const int* pos, int pstride, int B, int T, int H, int Hkv, int Lmax, float scale,
-                     hipStream_t s) {
-    const int ns = decode_attn_splits(Lmax);
-    const int grid = B * Hkv * ns;
-    const int R = (H / Hkv) * T;
-#define DEC(MR)                                                                                                    \
-    decode_attn_fp8_kernel<D, MR><<<grid, 256, 0, s>>>((const __bf16*)q, (const unsigned char*)k8,                  \
-                                                       (const unsigned char*)v8, ks, vs, part, pos, pstride, H, Hkv, \
-                                                       Lmax, ns, scale, T)
-    if (R <= 1) DEC(1);
-    else if (R <= 2) DEC(2);
-    else if (R <= 4) DEC(4);
-    else DEC(8);
-#undef DEC
-    if (out != nullptr) launch_decode_combine(part, out, B * T * H, D, ns, s);
-}
-
-void launch_decode_attn_fp8(const void* q, const void* k8, const void* v8, const float* ks, const float* vs,
-                            float* part, void* out, const int* pos, int pos_stride, int B, int T, int H, int Hkv,
-                            int D, int Lmax, float scale, hipStream_t s) {
-    if (D == 64) launch_d<64>(q, k8, v8, ks, vs, part, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, s);
-    else launch_d<128>(q, k8, v8, ks, vs, part, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, s);
-}
 
 void launch_kv_append_fp8(const void* qkv, long ld, void* qo, void* k8, void* v8, float* ks, float* vs,
                           const float* cosT, const float* sinT, const int* pos, int pos_stride, int B, int T, int H,

@@ -978,52 +978,113 @@ int check_pos(const at::Tensor& pos, int64_t B) {
     return pos.numel() == 1 ? 0 : 1;
 }
 
+// ---- fp8 KV cache (kv_fp8.hip): e4m3 bytes [B, Hkv, Lmax, D] + one fp32 scale per row [B, Hkv, Lmax]
+void check_cache8(const at::Tensor& c, const at::Tensor& sc, int64_t B, int64_t Hkv, const char* name) {
+    check_cuda(c, name);
+    check_cuda(sc, name);
+    TORCH_CHECK(c.scalar_type() == at::kFloat8_e4m3fn && c.dim() == 4 && c.is_contiguous(), "fp8 kv cache: ", name,
+                " must be a contiguous float8_e4m3fn [B, Hkv, Lmax, D] tensor");
+    TORCH_CHECK(c.size(0) == B && c.size(1) == Hkv, "fp8 kv cache: ", name, " batch / kv-head mismatch");
+    TORCH_CHECK(sc.scalar_type() == at::kFloat && sc.dim() == 3 && sc.is_contiguous() && sc.size(0) == B &&
+                    sc.size(1) == Hkv && sc.size(2) == c.size(2),
+                "fp8 kv cache: the scales of ", name, " must be a contiguous fp32 [B, Hkv, Lmax] tensor");
+    check_aligned(c, name);
+}
+
+// The K / V pair of an op named `op`: a bf16 cache (ks / vs null) or an fp8 cache with its scales
+void check_kv(const at::Tensor& k, const at::Tensor& v, const at::Tensor* ks, const at::Tensor* vs, int64_t B,
+              int64_t Hkv, const char* op) {
+    if (ks != nullptr) {
+        check_cache8(k, *ks, B, Hkv, "k8");
+        check_cache8(v, *vs, B, Hkv, "v8");
+    } else {
+        check_cache(k, B, Hkv, "k_cache");
+        check_cache(v, B, Hkv, "v_cache");
+    }
+    TORCH_CHECK(v.sizes() == k.sizes(), op, ": k / v cache shapes differ");
+}
+
 // qkv [B*T, (H + 2*Hkv)*D] rows of T new tokens at positions *pos.. -> roped q [B*T, H*D]; K (roped) and V are
-// written into the caches at those positions.
-at::Tensor kv_append(const at::Tensor& qkv, at::Tensor kc, at::Tensor vc, const at::Tensor& cos, const at::Tensor& sin,
-                     const at::Tensor& pos, int64_t B, int64_t T, int64_t H, bool use_rope) {
+// written into the caches at those positions -- as they are, or (ks / vs given) quantised row by row.
+at::Tensor kv_append_impl(const char* op, const at::Tensor& qkv, at::Tensor& kc, at::Tensor& vc, at::Tensor* ks,
+                          at::Tensor* vs, const at::Tensor& cos, const at::Tensor& sin, const at::Tensor& pos,
+                          int64_t B, int64_t T, int64_t H, bool use_rope) {
+    TORCH_CHECK(kc.dim() == 4, op, ": the k cache must be [B, Hkv, Lmax, D]");
     const int64_t Hkv = kc.size(1), Lmax = kc.size(2), D = kc.size(3);
-    TORCH_CHECK(D % 8 == 0 && H % Hkv == 0, "kv_append: head dim multiple of 8, H multiple of Hkv");
+    if (ks != nullptr) {  // (a row's amax is reduced over the D / 8 lanes of one wave)
+        TORCH_CHECK((D == 64 || D == 128) && Hkv > 0 && H % Hkv == 0, op, ": head dim 64/128, H multiple of Hkv");
+    } else {
+        TORCH_CHECK(D % 8 == 0 && Hkv > 0 && H % Hkv == 0, op, ": head dim multiple of 8, H multiple of Hkv");
+    }
     check_qkv(qkv, B * T, (H + 2 * Hkv) * D, "qkv");
-    check_cache(kc, B, Hkv, "k_cache");
-    check_cache(vc, B, Hkv, "v_cache");
-    TORCH_CHECK(vc.sizes() == kc.sizes(), "kv_append: k / v cache shapes differ");
+    check_kv(kc, vc, ks, vs, B, Hkv, op);
     const int pstride = check_pos(pos, B);
     if (use_rope)
         TORCH_CHECK(cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
                         sin.is_contiguous() && cos.size(0) >= Lmax && cos.size(1) == D / 2 && sin.sizes() == cos.sizes(),
-                    "kv_append: rope tables must be fp32 [>=Lmax, D/2]");
+                    op, ": rope tables must be fp32 [>=Lmax, D/2]");
     DevGuard g(qkv.device());
     auto q = at::empty({B * T, H * D}, qkv.options());
-    launch_kv_append(qkv.data_ptr(), qkv.stride(0), q.data_ptr(), kc.data_ptr(), vc.data_ptr(),
-                     use_rope ? cos.data_ptr<float>() : nullptr, use_rope ? sin.data_ptr<float>() : nullptr,
-                     pos.data_ptr<int>(), pstride, (int)B, (int)T, (int)H, (int)Hkv, (int)D, (int)Lmax, cur_stream());
+    const float* c = use_rope ? cos.data_ptr<float>() : nullptr;
+    const float* sn = use_rope ? sin.data_ptr<float>() : nullptr;
+    if (ks != nullptr)
+        launch_kv_append_fp8(qkv.data_ptr(), qkv.stride(0), q.data_ptr(), kc.data_ptr(), vc.data_ptr(),
+                             ks->data_ptr<float>(), vs->data_ptr<float>(), c, sn, pos.data_ptr<int>(), pstride, (int)B,
+                             (int)T, (int)H, (int)Hkv, (int)D, (int)Lmax, cur_stream());
+    else
+        launch_kv_append(qkv.data_ptr(), qkv.stride(0), q.data_ptr(), kc.data_ptr(), vc.data_ptr(), c, sn,
+                         pos.data_ptr<int>(), pstride, (int)B, (int)T, (int)H, (int)Hkv, (int)D, (int)Lmax,
+                         cur_stream());
     return q;
+}
+
+at::Tensor kv_append(const at::Tensor& qkv, at::Tensor kc, at::Tensor vc, const at::Tensor& cos, const at::Tensor& sin,
+                     const at::Tensor& pos, int64_t B, int64_t T, int64_t H, bool use_rope) {
+    return kv_append_impl("kv_append", qkv, kc, vc, nullptr, nullptr, cos, sin, pos, B, T, H, use_rope);
+}
+
+at::Tensor kv_append_fp8(const at::Tensor& qkv, at::Tensor k8, at::Tensor v8, at::Tensor ks, at::Tensor vs,
+                         const at::Tensor& cos, const at::Tensor& sin, const at::Tensor& pos, int64_t B, int64_t T,
+                         int64_t H, bool use_rope) {
+    return kv_append_impl("kv_append_fp8", qkv, k8, v8, &ks, &vs, cos, sin, pos, B, T, H, use_rope);
 }
 
 // q [B, H*D] (roped) attends to the first *pos + 1 cache rows -> [B, H*D]
 // combine = false: return the split partials [B*T, H, nsplit, D + 2] (o, m, l) for decode_attn_proj instead.
 // T new tokens per sequence (q rows b * T + t, already appended at positions *pos .. *pos + T - 1).
-at::Tensor decode_attn(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc, const at::Tensor& pos,
-                       int64_t H, double scale, bool combine, int64_t T) {
+// ks / vs given: an fp8 cache; the same contract, outputs and partials layout.
+at::Tensor decode_attn_impl(const char* op, const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc,
+                            const at::Tensor* ks, const at::Tensor* vs, const at::Tensor& pos, int64_t H, double scale,
+                            bool combine, int64_t T) {
+    TORCH_CHECK(kc.dim() == 4, op, ": the k cache must be [B, Hkv, Lmax, D]");
     const int64_t B = kc.size(0), Hkv = kc.size(1), Lmax = kc.size(2), D = kc.size(3);
-    TORCH_CHECK(decode_attn_ok((int)H, (int)Hkv, (int)D, (int)T),
-                "decode_attn: head dim 64/128, H a multiple of Hkv and (H / Hkv) * T <= 8 required");
+    TORCH_CHECK(decode_attn_ok((int)H, (int)Hkv, (int)D, (int)T), op,
+                ": head dim 64/128, H a multiple of Hkv and (H / Hkv) * T <= 8 required");
     check_cuda(q, "q");
-    TORCH_CHECK(q.scalar_type() == at::kBFloat16 && q.is_contiguous() && q.numel() == B * T * H * D,
-                "decode_attn: q must be contiguous bf16 [B*T, H*D]");
-    check_cache(kc, B, Hkv, "k_cache");
-    check_cache(vc, B, Hkv, "v_cache");
-    TORCH_CHECK(vc.sizes() == kc.sizes(), "decode_attn: k / v cache shapes differ");
+    TORCH_CHECK(q.scalar_type() == at::kBFloat16 && q.is_contiguous() && q.numel() == B * T * H * D, op,
+                ": q must be contiguous bf16 [B*T, H*D]");
+    check_kv(kc, vc, ks, vs, B, Hkv, op);
     const int pstride = check_pos(pos, B);
     DevGuard g(q.device());
     const int ns = decode_attn_splits((int)Lmax);
     auto part = at::empty({B * T, H, ns, D + 2}, q.options().dtype(at::kFloat));
     auto out = combine ? at::empty({B * T, H * D}, q.options()) : at::Tensor();
-    launch_decode_attn(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), part.data_ptr<float>(),
-                       combine ? out.data_ptr() : nullptr, pos.data_ptr<int>(), pstride, (int)B, (int)T, (int)H,
-                       (int)Hkv, (int)D, (int)Lmax, (float)scale, cur_stream());
+    launch_decode_attn(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), ks ? ks->data_ptr<float>() : nullptr,
+                       vs ? vs->data_ptr<float>() : nullptr, part.data_ptr<float>(), combine ? out.data_ptr() : nullptr,
+                       pos.data_ptr<int>(), pstride, (int)B, (int)T, (int)H, (int)Hkv, (int)D, (int)Lmax, (float)scale,
+                       cur_stream());
     return combine ? out : part;
+}
+
+at::Tensor decode_attn(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc, const at::Tensor& pos,
+                       int64_t H, double scale, bool combine, int64_t T) {
+    return decode_attn_impl("decode_attn", q, kc, vc, nullptr, nullptr, pos, H, scale, combine, T);
+}
+
+at::Tensor decode_attn_fp8(const at::Tensor& q, const at::Tensor& k8, const at::Tensor& v8, const at::Tensor& ks,
+                           const at::Tensor& vs, const at::Tensor& pos, int64_t H, double scale, bool combine,
+                           int64_t T) {
+    return decode_attn_impl("decode_attn_fp8", q, k8, v8, &ks, &vs, pos, H, scale, combine, T);
 }
 
 // Flash prefill over the cache (flash_attn_cache.hip): q [B*T, H*D] (roped, rows b * T + t, already appended at
@@ -1048,68 +1109,6 @@ at::Tensor cache_attn(const at::Tensor& q, const at::Tensor& kc, const at::Tenso
     launch_cache_attn(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(), pos.data_ptr<int>(), pstride, (int)B,
                       (int)T, (int)H, (int)Hkv, (int)D, (int)Lmax, (float)scale, cur_stream());
     return out;
-}
-
-// ---- fp8 KV cache (kv_fp8.hip): e4m3 bytes [B, Hkv, Lmax, D] + one fp32 scale per row [B, Hkv, Lmax]
-void check_cache8(const at::Tensor& c, const at::Tensor& sc, int64_t B, int64_t Hkv, const char* name) {
-    check_cuda(c, name);
-    check_cuda(sc, name);
-    TORCH_CHECK(c.scalar_type() == at::kFloat8_e4m3fn && c.dim() == 4 && c.is_contiguous(), "fp8 kv cache: ", name,
-                " must be a contiguous float8_e4m3fn [B, Hkv, Lmax, D] tensor");
-    TORCH_CHECK(c.size(0) == B && c.size(1) == Hkv, "fp8 kv cache: ", name, " batch / kv-head mismatch");
-    TORCH_CHECK(sc.scalar_type() == at::kFloat && sc.dim() == 3 && sc.is_contiguous() && sc.size(0) == B &&
-                    sc.size(1) == Hkv && sc.size(2) == c.size(2),
-                "fp8 kv cache: the scales of ", name, " must be a contiguous fp32 [B, Hkv, Lmax] tensor");
-    check_aligned(c, name);
-}
-
-at::Tensor kv_append_fp8(const at::Tensor& qkv, at::Tensor k8, at::Tensor v8, at::Tensor ks, at::Tensor vs,
-                         const at::Tensor& cos, const at::Tensor& sin, const at::Tensor& pos, int64_t B, int64_t T,
-                         int64_t H, bool use_rope) {
-    TORCH_CHECK(k8.dim() == 4, "kv_append_fp8: k8 must be [B, Hkv, Lmax, D]");
-    const int64_t Hkv = k8.size(1), Lmax = k8.size(2), D = k8.size(3);
-    TORCH_CHECK((D == 64 || D == 128) && Hkv > 0 && H % Hkv == 0, "kv_append_fp8: head dim 64/128, H multiple of Hkv");
-    check_qkv(qkv, B * T, (H + 2 * Hkv) * D, "qkv");
-    check_cache8(k8, ks, B, Hkv, "k8");
-    check_cache8(v8, vs, B, Hkv, "v8");
-    TORCH_CHECK(v8.sizes() == k8.sizes(), "kv_append_fp8: k / v cache shapes differ");
-    const int pstride = check_pos(pos, B);
-    if (use_rope)
-        TORCH_CHECK(cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
-                        sin.is_contiguous() && cos.size(0) >= Lmax && cos.size(1) == D / 2 && sin.sizes() == cos.sizes(),
-                    "kv_append_fp8: rope tables must be fp32 [>=Lmax, D/2]");
-    DevGuard g(qkv.device());
-    auto q = at::empty({B * T, H * D}, qkv.options());
-    launch_kv_append_fp8(qkv.data_ptr(), qkv.stride(0), q.data_ptr(), k8.data_ptr(), v8.data_ptr(),
-                         ks.data_ptr<float>(), vs.data_ptr<float>(), use_rope ? cos.data_ptr<float>() : nullptr,
-                         use_rope ? sin.data_ptr<float>() : nullptr, pos.data_ptr<int>(), pstride, (int)B, (int)T,
-                         (int)H, (int)Hkv, (int)D, (int)Lmax, cur_stream());
-    return q;
-}
-
-// decode_attn over the fp8 cache: the same contract, outputs and partials layout
-at::Tensor decode_attn_fp8(const at::Tensor& q, const at::Tensor& k8, const at::Tensor& v8, const at::Tensor& ks,
-                           const at::Tensor& vs, const at::Tensor& pos, int64_t H, double scale, bool combine,
-                           int64_t T) {
-    TORCH_CHECK(k8.dim() == 4, "decode_attn_fp8: k8 must be [B, Hkv, Lmax, D]");
-    const int64_t B = k8.size(0), Hkv = k8.size(1), Lmax = k8.size(2), D = k8.size(3);
-    TORCH_CHECK(decode_attn_ok((int)H, (int)Hkv, (int)D, (int)T),
-                "decode_attn_fp8: head dim 64/128, H a multiple of Hkv and (H / Hkv) * T <= 8 required");
-    check_cuda(q, "q");
-    TORCH_CHECK(q.scalar_type() == at::kBFloat16 && q.is_contiguous() && q.numel() == B * T * H * D,
-                "decode_attn_fp8: q must be contiguous bf16 [B*T, H*D]");
-    check_cache8(k8, ks, B, Hkv, "k8");
-    check_cache8(v8, vs, B, Hkv, "v8");
-    TORCH_CHECK(v8.sizes() == k8.sizes(), "decode_attn_fp8: k / v cache shapes differ");
-    const int pstride = check_pos(pos, B);
-    DevGuard g(q.device());
-    const int ns = decode_attn_splits((int)Lmax);
-    auto part = at::empty({B * T, H, ns, D + 2}, q.options().dtype(at::kFloat));
-    auto out = combine ? at::empty({B * T, H * D}, q.options()) : at::Tensor();
-    launch_decode_attn_fp8(q.data_ptr(), k8.data_ptr(), v8.data_ptr(), ks.data_ptr<float>(), vs.data_ptr<float>(),
-                           part.data_ptr<float>(), combine ? out.data_ptr() : nullptr, pos.data_ptr<int>(), pstride,
-                           (int)B, (int)T, (int)H, (int)Hkv, (int)D, (int)Lmax, (float)scale, cur_stream());
-    return combine ? out : part;
 }
 
 // rows [0, min(pos[b] + T, Lmax)) of every K and V slab -> bf16 k_out / v_out [B, Hkv, Lmax, D]; other rows untouched

@@ -56,12 +56,23 @@ from . import reference as F
 from ._ext import ops
 
 
+def _rope_args(x: Tensor, cos: Tensor | None, sin: Tensor | None) -> tuple[Tensor, Tensor, bool]:
+    """``(cos, sin, use_rope)`` as the HIP ops take them: empty tables and ``False`` where there is no RoPE."""
+    if cos is not None:
+        return cos, sin, True
+    e = x.new_empty(0, dtype=torch.float32)
+    return e, e, False
+
+
+def _scale(cache: Tensor, scale: float | None) -> float:
+    """The softmax scale: ``1 / sqrt(D)`` of the cache's head dim unless given."""
+    return 1.0 / math.sqrt(cache.shape[-1]) if scale is None else scale
+
+
 def kv_append(qkv: Tensor, k_cache: Tensor, v_cache: Tensor, cos: Tensor | None, sin: Tensor | None, pos: Tensor,
               batch: int, n_new: int, n_heads: int) -> Tensor:
     if qkv.is_cuda:
-        use_rope = cos is not None
-        c = cos if use_rope else qkv.new_empty(0, dtype=torch.float32)
-        s = sin if use_rope else qkv.new_empty(0, dtype=torch.float32)
+        c, s, use_rope = _rope_args(qkv, cos, sin)
         return ops().kv_append(qkv, k_cache, v_cache, c, s, pos, batch, n_new, n_heads, use_rope)
     return kv_append_reference(qkv, k_cache, v_cache, cos, sin, pos, batch, n_new, n_heads)
 
@@ -96,8 +107,7 @@ def decode_attention(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, n
                      scale: float | None = None, n_new: int = 1) -> Tensor:
     """Attention of ``n_new`` new tokens per sequence (``q [B*n_new, H*D]``, already appended to the caches at
     positions ``pos .. pos + n_new - 1``) over the cache; token t sees keys ``0 .. pos + t``."""
-    D = k_cache.shape[-1]
-    scale = 1.0 / math.sqrt(D) if scale is None else scale
+    scale = _scale(k_cache, scale)
     if q.is_cuda:
         return ops().decode_attn(q.contiguous(), k_cache, v_cache, pos, n_heads, scale, True, n_new)
     return decode_attention_reference(q, k_cache, v_cache, pos, n_heads, scale, n_new)
@@ -130,8 +140,7 @@ def prefill_attention(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, 
     ``q [B*n_new, H*D]`` already appended at ``pos .. pos + n_new - 1``, token t sees keys ``0 .. pos + t`` -- for
     any ``n_new`` (MFMA flash attention whose keys are the cache slabs), where ``decode_attention`` takes at most
     ``8 / G`` tokens.  The row of a token at or past ``Lmax`` is unspecified."""
-    D = k_cache.shape[-1]
-    scale = 1.0 / math.sqrt(D) if scale is None else scale
+    scale = _scale(k_cache, scale)
     if q.is_cuda:
         return ops().cache_attn(q.contiguous(), k_cache, v_cache, pos, n_heads, scale, n_new)
     return decode_attention_reference(q, k_cache, v_cache, pos, n_heads, scale, n_new)
@@ -142,8 +151,7 @@ def decode_attention_partials(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: 
     """Split-K decode attention without the combine: fp32 ``[B, H, nsplit, D + 2]`` = (o, m, l) per 256-key chunk
     (natural-log units), consumed by :func:`decode_attn_proj`.  A chunk past the valid length has ``m = -inf`` and
     ``l = 0``; its ``o`` part is unspecified (the GPU kernel leaves it unwritten) and every consumer skips it."""
-    D = k_cache.shape[-1]
-    scale = 1.0 / math.sqrt(D) if scale is None else scale
+    scale = _scale(k_cache, scale)
     if q.is_cuda:
         return ops().decode_attn(q.contiguous(), k_cache, v_cache, pos, n_heads, scale, False)
     return decode_partials_reference(q, k_cache, v_cache, pos, n_heads, scale)
@@ -225,9 +233,7 @@ def decode_qkv(x: Tensor, w: Tensor, k_cache: Tensor, v_cache: Tensor, cos: Tens
     sequence ``m`` at ``pos[m]``; a row at ``Lmax`` or past it writes nothing, and its query row is unspecified
     (as for :func:`kv_append`)."""
     if x.is_cuda:
-        use_rope = cos is not None
-        c = cos if use_rope else x.new_empty(0, dtype=torch.float32)
-        sn = sin if use_rope else x.new_empty(0, dtype=torch.float32)
+        c, sn, use_rope = _rope_args(x, cos, sin)
         q, s = ops().decode_qkv(x, xd, ln, eps, w, k_cache, v_cache, c, sn, pos, n_heads, use_rope)
         return q, (s if xd is not None else None)
     qkv, s = decode_gemv_reference(x, w, xd, ln, eps)
@@ -266,9 +272,7 @@ def kv_append_fp8(qkv: Tensor, k8: Tensor, v8: Tensor, k_scale: Tensor, v_scale:
     """:func:`kv_append` into an fp8 cache: the rows it would have written to bf16 caches are quantised into ``k8`` /
     ``v8 [B, Hkv, Lmax, D]`` with their scales in ``k_scale`` / ``v_scale [B, Hkv, Lmax]``; returns the same ``q``."""
     if qkv.is_cuda:
-        use_rope = cos is not None
-        c = cos if use_rope else qkv.new_empty(0, dtype=torch.float32)
-        s = sin if use_rope else qkv.new_empty(0, dtype=torch.float32)
+        c, s, use_rope = _rope_args(qkv, cos, sin)
         return ops().kv_append_fp8(qkv, k8, v8, k_scale, v_scale, c, s, pos, batch, n_new, n_heads, use_rope)
     return kv_append_fp8_reference(qkv, k8, v8, k_scale, v_scale, cos, sin, pos, batch, n_new, n_heads)
 
@@ -292,8 +296,7 @@ def kv_append_fp8_reference(qkv, k8, v8, k_scale, v_scale, cos, sin, pos, batch,
 def decode_attention_fp8(q: Tensor, k8: Tensor, v8: Tensor, k_scale: Tensor, v_scale: Tensor, pos: Tensor,
                          n_heads: int, scale: float | None = None, n_new: int = 1) -> Tensor:
     """:func:`decode_attention` over an fp8 cache."""
-    D = k8.shape[-1]
-    scale = 1.0 / math.sqrt(D) if scale is None else scale
+    scale = _scale(k8, scale)
     if q.is_cuda:
         return ops().decode_attn_fp8(q.contiguous(), k8, v8, k_scale, v_scale, pos, n_heads, scale, True, n_new)
     return decode_attention_fp8_reference(q, k8, v8, k_scale, v_scale, pos, n_heads, scale, n_new)
@@ -308,8 +311,7 @@ def decode_attention_fp8_reference(q, k8, v8, k_scale, v_scale, pos, n_heads, sc
 def decode_attention_partials_fp8(q: Tensor, k8: Tensor, v8: Tensor, k_scale: Tensor, v_scale: Tensor, pos: Tensor,
                                   n_heads: int, scale: float | None = None, n_new: int = 1) -> Tensor:
     """:func:`decode_attention_partials` over an fp8 cache: the same layout, for :func:`decode_attn_proj`."""
-    D = k8.shape[-1]
-    scale = 1.0 / math.sqrt(D) if scale is None else scale
+    scale = _scale(k8, scale)
     if q.is_cuda:
         return ops().decode_attn_fp8(q.contiguous(), k8, v8, k_scale, v_scale, pos, n_heads, scale, False, n_new)
     assert n_new == 1

@@ -188,15 +188,15 @@ class _Spy:
 
 def _watch(monkeypatch, sess):
     """-> (list of ``_forward_fast`` calls, spy on the attention ops) from here on."""
-    calls, fwd, operands = [], sess._forward_fast, sess._operands
-    spy = _Spy(operands(None)[0])
+    calls, fwd = [], sess._forward_fast
+    spy = _Spy(sess._hip())
 
     def forward(ids, *a, **kw):
         calls.append(tuple(ids.shape))
         return fwd(ids, *a, **kw)
 
     monkeypatch.setattr(sess, "_forward_fast", forward)
-    monkeypatch.setattr(sess, "_operands", lambda kv: (spy, *operands(kv)[1:]))
+    monkeypatch.setattr(sess, "_hip", lambda: spy)
     return calls, spy
 
 

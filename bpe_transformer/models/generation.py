@@ -41,10 +41,11 @@ v_scale: [num_layers, B, Hkv, Lmax]``), ``(D + 4) / (2 D)`` of the bytes, which
 is what the memory-bound decode attention reads.  It behaves as a bf16 cache
 that holds the dequantised rows (``ops/decode.py`` states the format).  Every
 step is ``kv_append_fp8`` + attention over the cache as stored --
-``decode_attn_fp8``, or ``kv_dequant`` + ``cache_attn`` for windows of more
-than ``8 / G`` tokens -- and the flash prefill is not used, so a prompt token
-sees the quantised keys of its own window too, whatever the chunking.  Not
-available with a draft model yet.
+``decode_attn_fp8``, or ``cache_attn_fp8`` (the MFMA ``cache_attn`` reading the
+e4m3 rows and their scales directly) for windows of more than ``8 / G`` tokens
+-- with the launch count of the bf16 cache and no scratch.  The flash prefill
+is not used, so a prompt token sees the quantised keys of its own window too,
+whatever the chunking.  Not available with a draft model yet.
 
 On the CPU, in fp32, or with the reference ablations (post-norm, no RMSNorm,
 non-SwiGLU FFN) the same session runs the oracle math over the same cache.
@@ -171,19 +172,10 @@ class KVCache:
         self._len = [0] * batch  # host mirror of pos (never read back), per sequence: all equal unless ragged
         self.max_len = max_len
         self.batch = batch
-        self._deq = None  # fp8: one layer's bf16 K / V scratch for cache_attn (allocated by the first long window)
 
     def view(self, b: int | None = None) -> "KVView":
         """What a forward pass runs on: the whole batch, or slot ``b`` alone."""
         return KVView(self, b)
-
-    def dequant_scratch(self, n: int) -> tuple[Tensor, Tensor]:
-        """fp8: bf16 K / V ``[n, Hkv, Lmax, D]`` that ``kv_dequant`` fills for ``cache_attn``, one layer's worth,
-        reused by every layer.  Zero-filled once, so rows that were never written are finite, as in a bf16 cache."""
-        if self._deq is None:
-            self._deq = tuple(torch.zeros(self.k.shape[1:], device=self.k.device, dtype=torch.bfloat16)
-                              for _ in range(2))
-        return self._deq[0][:n], self._deq[1][:n]
 
     @property
     def length(self) -> int:
@@ -254,8 +246,8 @@ class KVView:
         return h.kv_append_fp8(qkv, self.k[li], self.v[li], ks[li], vs[li], rope[0], rope[1], self.pos, B, T, H, rope[2])
 
     def attend(self, h, q: Tensor, li: int, T: int, H: int, kind: str, combine: bool = True) -> Tensor:
-        """Attention of the appended tokens over the cache as stored: ``kind`` ``"cache"`` (``cache_attn``; fp8: over
-        ``kv_dequant``'s scratch) or ``"decode"`` (``decode_attn``; ``combine=False``: its split partials)."""
+        """Attention of the appended tokens over the cache as stored: ``kind`` ``"cache"`` (``cache_attn``; fp8:
+        ``cache_attn_fp8``) or ``"decode"`` (``decode_attn``; ``combine=False``: its split partials)."""
         k, v, pos = self.k[li], self.v[li], self.pos
         scale = 1.0 / math.sqrt(k.shape[-1])
         if self.scales is None:
@@ -264,9 +256,7 @@ class KVView:
             return h.decode_attn(q, k, v, pos, H, scale, combine, T)
         ks, vs = self.scales[0][li], self.scales[1][li]
         if kind == "cache":
-            kd, vd = self.cache.dequant_scratch(k.shape[0])
-            h.kv_dequant(k, v, ks, vs, pos, T, kd, vd)
-            return h.cache_attn(q, kd, vd, pos, H, scale, T)
+            return h.cache_attn_fp8(q, k, v, ks, vs, pos, H, scale, T)
         return h.decode_attn_fp8(q, k, v, ks, vs, pos, H, scale, combine, T)
 
     def decode_qkv(self, h, xr: Tensor, xd, ln1: Tensor, eps: float, wqkv: Tensor, li: int, H: int, rope):
@@ -324,7 +314,7 @@ class DecodeSession:
     ``kv_dtype="fp8"`` keeps the cache as e4m3 rows with one power-of-two scale each (``csrc/kv_fp8.hip``;
     ``ops/decode.py`` states the format): ``(D + 4) / (2 D)`` of the bf16 cache's bytes.  Every step appends with
     ``kv_append_fp8`` and attends to the cache as stored, its own window included -- ``decode_attn_fp8`` up to ``8 /
-    G`` tokens, ``kv_dequant`` into a one-layer bf16 scratch + ``cache_attn`` beyond; the flash prefill is never used,
+    G`` tokens, ``cache_attn_fp8`` (``cache_attn`` reading the e4m3 rows directly) beyond; the flash prefill is never used,
     so prefill, chunked prefill and decode have one semantics, that of a bf16 cache holding the dequantised rows.  At
     batch <= 8 the QKV projection is ``decode_gemv`` followed by ``kv_append_fp8`` (a row's amax spans several
     workgroups of the fused ``decode_qkv`` epilogue): 6 launches per layer instead of 5.

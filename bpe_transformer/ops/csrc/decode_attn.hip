@@ -43,6 +43,9 @@
 //   decode_attn_kernel<128, MR, Fp8Cache>   VGPRs 94 / 112 / 120 / 180   SGPRs 61 / 67 / 72 / 66   waves/SIMD 5 / 4 / 4 / 2
 //   LDS bytes, either format: D 64: 2336 / 4640 / 9248 / 18464, D 128: 3616 / 7200 / 14368 / 28704
 //   kv_append_kernel VGPRs 44, SGPRs 69   kv_append_fp8_kernel VGPRs 44, SGPRs 79   kv_dequant_kernel VGPRs 29   (8 waves)
+//   cache_attn_kernel<64 / 128, Bf16Cache>  VGPRs 118 / 176   SGPRs 43 / 43   LDS 32768 / 65536   waves/SIMD 4 / 2
+//   cache_attn_kernel<64 / 128, Fp8Cache>   VGPRs 122 / 184   SGPRs 52 / 54   LDS 25104 / 49680   waves/SIMD 4 / 2
+//     (flash_attn_cache.hip)
 // The format's scale loads and multiplies exist only in the Fp8Cache instantiations (`if constexpr`).
 #include "kv_cache.h"
 #include "kernels.h"

@@ -170,6 +170,36 @@ __device__ __forceinline__ void dma_tile64_buf(const __bf16* base, int nbytes, c
 #endif
 }
 
+// Byte tiles (the e4m3 KV cache, flash_attn_cache.hip): 64 rows of RB8 = 64 (D = 64) or 128 (D = 128) bytes, with one
+// fp32 scale per row.  A (b, kv head) slab is contiguous, so such a tile is one block of 64 * RB8 bytes, and its LDS
+// image is a STAGING image that only a conversion pass reads (16 bytes per lane, lane-linear: conflict-free as it
+// is), never an MFMA operand: the DMA copies it as it lies, and the swizzle (swz<2 * RB8>) is applied where the
+// converted bf16 chunks are written.  So 64-byte rows need no sigma of their own.  `nbytes` is the extent of the
+// resource as in dma_tile64_buf: bytes at or past it read as zeros.
+template <int NW, int RB8>
+__device__ __forceinline__ void dma_bytes64_buf(const unsigned char* base, int nbytes, int r0, char* img, int w,
+                                                int l) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    constexpr int CPW = 64 * RB8 / (NW * 1024);  // wave-instructions per wave, 1 KB each
+    static_assert(CPW >= 1, "a byte tile is at least one wave-instruction per wave");
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, nbytes, 0x00020000);
+    const unsigned soff = (unsigned)r0 * RB8;
+#pragma unroll
+    for (int i = 0; i < CPW; ++i)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)(img + 1024 * (CPW * w + i)), 16,
+                                                 (unsigned)(1024 * (CPW * w + i) + 16 * l), soff, 0, 0);
+#endif
+}
+
+// The 64 fp32 row scales of a tile, rows r0 .. r0 + 63 of `base` -> img[0 .. 63]: one wave-instruction of one dword
+// per lane (call it from one wave).  `nbytes` = 4 * rows: the scale of a row at or past the extent reads as zero.
+__device__ __forceinline__ void dma_scales64_buf(const float* base, int nbytes, int r0, char* img, int l) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, nbytes, 0x00020000);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_void_t*)img, 4, (unsigned)(4 * l), (unsigned)r0 * 4u, 0, 0);
+#endif
+}
+
 // Prologue priority.  A workgroup that starts while its CU's other waves run their MFMA loops is the youngest there,
 // and VALU issue goes by priority, then age (MI355X_MICROARCH, two waves per SIMD, item 2): its prologue -- ~200 VALU
 // of index math (integer divisions by the grid's shape) and address set-up before the first load can issue --

@@ -25,8 +25,30 @@
 //   * pos is read on the device (stride 0: shared, 1: per sequence) and the grid depends on B, Hkv, G * T only:
 //     the launch is shape-static.  No atomics, no split of the key range: deterministic.  A very long cache with a
 //     tiny T has few workgroups; that case stays on decode_attn (models/generation.py routes it).
+//
+// The kernel body is written once against the cache format (kv_cache.h: Bf16Cache / Fp8Cache).  Over the e4m3 cache
+// (kv_fp8.hip: rows of D bytes, one power-of-two fp32 scale each) the result is, bit for bit, that of the bf16
+// instantiation on the cache kv_dequant would write -- DESIGN (a) of the two that give those bits: a per-tile
+// conversion pass.  The 64 x D byte tile and its 64 K and 64 V scales come by LDS-DMA into a staging image (fa_common.h
+// dma_bytes64_buf / dma_scales64_buf; extents L * D and L * 4 bytes, so bytes AND scales from row L on read as zeros
+// -- a stale NaN scale there would otherwise reach the output through 0 * NaN; a NaN scale below L is a non-finite
+// row of the sequence and gives NaN as in the bf16 cache).  All four waves then convert it with kv_dequant's own
+// arithmetic, f2bf(e4m3 * s), into the swizzled bf16 image the DMA of the bf16 instantiation would have left, and
+// everything after that is the same code on the same bits.  Taken because it is the one whose equality with the
+// two-launch route needs no argument about the MFMA's internal products, and it keeps every LDS read of the MFMA
+// loop as measured for the bf16 kernel; design (b) -- e4m3 fragments converted at read time, scales folded into the
+// score and the probability -- saves the extra barrier and the LDS round trip and is the next step if the
+// conversion pass shows as the cost (docs/performance.md, "fp8 KV cache", has the measurement).
+//   One case is handled apart, and there the two routes differ: a V row below L whose scale is NaN.  In the bf16
+//   image its NaN meets P = 0 inside the MFMA and reaches the queries of the tile that the causal mask hides it from;
+//   here the row is converted to zeros and the queries that do see it get NaN in the epilogue (convert_tile).
+//   Pipeline: the staging image is single and the bf16 image is single; together they are the double buffer.  Per
+//   tile: convert staging -> image, barrier, request tile t + 1 into the staging (every wave is past its conversion
+//   reads), MFMA work on the image, closing barrier (drains the DMA; the image is free again).  One barrier more per
+//   tile than bf16.  LDS at D 128: 2 x 16 KB images + 2 x 8 KB staging + 512 B scales = 48.5 KB (bf16: 64 KB).
 #include "fa_common.h"
 #include "kernels.h"
+#include "kv_cache.h"
 
 namespace bpe {
 namespace fa {
@@ -34,18 +56,117 @@ namespace cache {
 
 constexpr float RESCALE_THRESHOLD = 8.0f;  // log2 units, as fa_fwd_kernel
 
+// The row scales of a cache format as a kernel argument: nothing for bf16 (an empty last argument, so that
+// instantiation's argument layout and code are those of the kernel before it took a format), two pointers for fp8.
+template <class C> struct Scales {};
+template <> struct Scales<kvc::Fp8Cache> {
+    const float* k;
+    const float* v;
+};
+
+// Dynamic LDS of an instantiation: bf16 K / V [2][64][D] each; fp8 one bf16 image and one byte staging image each,
+// then the 64 K and 64 V scales and the first non-finite V row (one int).
+template <int D, class C> constexpr size_t lds_bytes() {
+    return C::scaled ? (size_t)2 * 64 * D * 2 + 2 * 64 * D + 512 + 16 : (size_t)4 * 64 * D * 2;
+}
+
+// 16 staged e4m3 bytes of a row and the row's scale -> the two 16-byte chunks of bf16 that kv_dequant_kernel
+// (kv_fp8.hip) writes for them: the same conversions, the same product, the same rounding.
+__device__ __forceinline__ void dequant16(u32x4 w, float s, u16x8& lo, u16x8& hi) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const f32x2 a = kvc::fp8x2(w[i], false), c = kvc::fp8x2(w[i], true);
+        lo[4 * i] = f2bf(a.x * s); lo[4 * i + 1] = f2bf(a.y * s);
+        lo[4 * i + 2] = f2bf(c.x * s); lo[4 * i + 3] = f2bf(c.y * s);
+        const f32x2 e = kvc::fp8x2(w[2 + i], false), g = kvc::fp8x2(w[2 + i], true);
+        hi[4 * i] = f2bf(e.x * s); hi[4 * i + 1] = f2bf(e.y * s);
+        hi[4 * i + 2] = f2bf(g.x * s); hi[4 * i + 3] = f2bf(g.y * s);
+    }
+}
+
+// The conversion pass of one operand: staging [64][D] bytes + scales [64] -> the swizzled bf16 image swz<2 * D>.
+// Thread tid takes the 16-byte pieces tid, tid + 256, ...: lane-linear 16-byte reads, and the 8 lanes of a
+// ds_write_b128 group write 8 distinct 16-byte slots of one 256-byte bank row (two 128-byte rows that share sigma at
+// D 64, one 256-byte row at D 128; the chunks 2 j ^ sigma of a row all have the parity of sigma).
+// `vbad` (V only, else null): a V row whose scale is not finite -- a non-finite row of the sequence itself -- is
+// written as zeros and its key index (n0 + row) is min-ed into *vbad instead: inside the MFMA its NaN would reach
+// every query of the tile, 0 * NaN, also those the causal mask hides it from.  The epilogue gives NaN to exactly the
+// queries that see the row.  (A non-finite K row needs nothing: its scores are masked by a select.)
 template <int D>
+__device__ __forceinline__ void convert_tile(const char* st, const char* sc, char* img, int tid, int n0 = 0,
+                                             int* vbad = nullptr) {
+    constexpr int PR = D / 16;  // 16-byte pieces per row
+#pragma unroll
+    for (int i = 0; i < D / 64; ++i) {
+        const int e = tid + 256 * i, r = e / PR, j = e % PR;
+        const u32x4 w = *reinterpret_cast<const u32x4*>(st + 16 * e);
+        const float s = *reinterpret_cast<const float*>(sc + 4 * r);
+        u16x8 lo, hi;
+        dequant16(w, s, lo, hi);
+        if (vbad != nullptr && !(fabsf(s) < INFINITY)) {
+            lo = u16x8{};
+            hi = u16x8{};
+            if (j == 0) atomicMin(vbad, n0 + r);
+        }
+        *reinterpret_cast<u16x8*>(img + swz<2 * D>(r, 2 * j)) = lo;
+        *reinterpret_cast<u16x8*>(img + swz<2 * D>(r, 2 * j + 1)) = hi;
+    }
+}
+
+// Requests tile n0 .. n0 + 63 of both operands by LDS-DMA: bf16 into buffer `buf` of the K and of the V pair; fp8
+// into the staging images, with the tile's scales (waves 0 and 1, one wave-instruction each).
+template <int D, class C> struct Request;
+
+template <int D> struct Request<D, kvc::Bf16Cache> {
+    static constexpr int RB = 2 * D, TILE = 64 * RB;
+    const __bf16 *kbase, *vbase;
+    int sbytes, wu;
+    char* smem;
+    DmaVoff<4, RB> vo;
+    __device__ __forceinline__ Request(const u16* k, const u16* v, int nbytes, char* lds, Scales<kvc::Bf16Cache>,
+                                       long, int, int w, int l)
+        : kbase((const __bf16*)k), vbase((const __bf16*)v), sbytes(nbytes), wu(w), smem(lds), vo(dma_voff<4, RB>(D, w, l)) {}
+    __device__ __forceinline__ void operator()(int n0, int buf) const {
+        dma_tile64_buf<4, RB>(kbase, sbytes, vo, n0, D, smem + buf * TILE, wu);
+        dma_tile64_buf<4, RB>(vbase, sbytes, vo, n0, D, smem + (2 + buf) * TILE, wu);
+    }
+};
+
+template <int D> struct Request<D, kvc::Fp8Cache> {
+    static constexpr int TILE = 64 * 2 * D;
+    const unsigned char *kbase, *vbase;
+    const float *ks, *vs;  // the slab's scales
+    int sbytes, scbytes, wu, l;
+    char* st;  // K staging; V staging, K scales and V scales follow
+    __device__ __forceinline__ Request(const unsigned char* k, const unsigned char* v, int nbytes, char* lds,
+                                       Scales<kvc::Fp8Cache> sc, long row0, int nsc, int w, int lane)
+        : kbase(k), vbase(v), ks(sc.k + row0), vs(sc.v + row0), sbytes(nbytes), scbytes(nsc), wu(w), l(lane),
+          st(lds + 2 * TILE) {}
+    __device__ __forceinline__ void operator()(int n0, int) const {
+        dma_bytes64_buf<4, D>(kbase, sbytes, n0, st, wu, l);
+        dma_bytes64_buf<4, D>(vbase, sbytes, n0, st + TILE / 2, wu, l);
+        if (wu == 0) dma_scales64_buf(ks, scbytes, n0, st + TILE, l);
+        if (wu == 1) dma_scales64_buf(vs, scbytes, n0, st + TILE + 256, l);
+    }
+};
+
+template <int D, class C>
 __global__ void __launch_bounds__(256, 2)
-cache_attn_kernel(const __bf16* __restrict__ Q, const __bf16* __restrict__ Kc, const __bf16* __restrict__ Vc,
-                  __bf16* __restrict__ O, const int* __restrict__ pos, int pstride, int H, int Hkv, int Lmax, int T,
-                  float scale_log2, int nqb) {
+cache_attn_kernel(const __bf16* __restrict__ Q, const typename C::elem* __restrict__ Kc,
+                  const typename C::elem* __restrict__ Vc, __bf16* __restrict__ O, const int* __restrict__ pos,
+                  int pstride, int H, int Hkv, int Lmax, int T, float scale_log2, int nqb, Scales<C> sc) {
     constexpr int RB = D * 2;      // bytes per LDS row
     constexpr int TILE = 64 * RB;  // bytes per 64-key tile
     constexpr int KS = D / 16;     // k-steps over the head dim
     constexpr int DT = D / 32;     // 32-wide d tiles of O
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* Ks = smem;             // [2][64][D]
-    char* Vs = smem + 2 * TILE;  // [2][64][D]
+    char* Ks = smem;                                // bf16 [2][64][D]; fp8: the K image, then the V image
+    char* Vs = smem + (C::scaled ? 1 : 2) * TILE;   // bf16 [2][64][D]
+    char* Kst = smem + 2 * TILE;                    // fp8: staged bytes [64][D] of K, of V, then the scales
+    char* Vst = Kst + TILE / 2;
+    char* Ksc = Vst + TILE / 2;
+    char* Vsc = Ksc + 256;
+    int* vbad = reinterpret_cast<int*>(Vsc + 256);  // fp8: the first V row with a non-finite scale
 
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, l31 = l & 31, hh = l >> 5;
     const int wu = __builtin_amdgcn_readfirstlane(w);
@@ -76,12 +197,14 @@ cache_attn_kernel(const __bf16* __restrict__ Q, const __bf16* __restrict__ Kc, c
     const int lim_hi = min(p0 + min(qw0 + 31, R - 1) / G, L - 1);
     const int ntiles = (min(p0 + min(q0 + 127, R - 1) / G, L - 1) + 64) / 64;  // >= 1
 
-    const __bf16* kbase = Kc + (long)bk * Lmax * D;
-    const __bf16* vbase = Vc + (long)bk * Lmax * D;
-    const int sbytes = L * D * 2;  // extent of both buffer resources: rows >= L read as zeros
-    const DmaVoff<4, RB> vo = dma_voff<4, RB>(D, wu, l);
-    dma_tile64_buf<4, RB>(kbase, sbytes, vo, 0, D, Ks, wu);
-    dma_tile64_buf<4, RB>(vbase, sbytes, vo, 0, D, Vs, wu);
+    const typename C::elem* kbase = Kc + (long)bk * Lmax * D;
+    const typename C::elem* vbase = Vc + (long)bk * Lmax * D;
+    const int sbytes = L * D * (int)sizeof(typename C::elem);  // extent of both resources: rows >= L read as zeros
+    if constexpr (C::scaled) {
+        if (tid == 0) *vbad = 0x7fffffff;
+    }
+    const Request<D, C> request{kbase, vbase, sbytes, smem, sc, (long)bk * Lmax, L * 4, wu, l};
+    request(0, 0);
 
     // Q fragments (B operand of S^T = K.Q^T), softmax scale * log2(e) folded in
     bf16x8 qf[KS];
@@ -104,10 +227,18 @@ cache_attn_kernel(const __bf16* __restrict__ Q, const __bf16* __restrict__ Kc, c
 
     __syncthreads();
     for (int t = 0; t < ntiles; ++t) {
-        const int cur = t & 1, n0 = t * 64;
-        if (t + 1 < ntiles) {  // buffer cur ^ 1 was last read in tile t - 1, before its closing barrier
-            dma_tile64_buf<4, RB>(kbase, sbytes, vo, n0 + 64, D, Ks + (cur ^ 1) * TILE, wu);
-            dma_tile64_buf<4, RB>(vbase, sbytes, vo, n0 + 64, D, Vs + (cur ^ 1) * TILE, wu);
+        const int cur = C::scaled ? 0 : t & 1, n0 = t * 64;
+        if constexpr (!C::scaled) {
+            // buffer cur ^ 1 was last read in tile t - 1, before its closing barrier
+            if (t + 1 < ntiles) request(n0 + 64, cur ^ 1);
+        } else {
+            // every wave converts, whether it has work in this tile or not.  The images were last read in tile
+            // t - 1, before its closing barrier, which also drained this tile's DMA; the staging is requested again
+            // only after the barrier below, when no wave reads it any more.
+            convert_tile<D>(Kst, Ksc, Ks, tid);
+            convert_tile<D>(Vst, Vsc, Vs, tid, n0, vbad);
+            __syncthreads();
+            if (t + 1 < ntiles) request(n0 + 64, 0);
         }
         if (wave_on && n0 <= lim_hi) {
             const char* Kt = Ks + cur * TILE;
@@ -186,7 +317,12 @@ cache_attn_kernel(const __bf16* __restrict__ Q, const __bf16* __restrict__ Kc, c
 
     // ---- epilogue: O = O^T / l, query on the lane, 4 consecutive d per register group
     if (qrow < R) {
-        const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
+        float inv = l_run > 0.f ? 1.f / l_run : 0.f;
+        if constexpr (C::scaled) {
+            // a visible non-finite V row: the whole output row is NaN, as p * NaN gives for every d (the last
+            // conversion pass, and with it the last atomicMin, lies before a barrier this wave has passed)
+            if (*vbad <= lim) inv = __uint_as_float(0x7fc00000u);
+        }
         __bf16* op = O + (((long)b * T + tok) * H + head) * D;
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt)
@@ -208,23 +344,41 @@ using namespace bpe::fa;
 
 // T new tokens per sequence over the cache: any T, the G heads of a kv head share a workgroup's rows.  The slab
 // extent (Lmax rows of D bf16) is a 32-bit byte count of the buffer resources.
-bool cache_attn_ok(int H, int Hkv, int D, int T, int Lmax) {
+static bool cache_shape_ok(int H, int Hkv, int D, int T, int Lmax) {
     const int G = Hkv > 0 ? H / Hkv : 0;
     return (D == 64 || D == 128) && Hkv > 0 && H % Hkv == 0 && G >= 1 && G <= 8 && T >= 1 && Lmax >= 1 &&
-           (long)Lmax * D * 2 < (1L << 31) && (long)G * T < (1L << 30);
+           (long)G * T < (1L << 30);
 }
 
-template <int D>
-static void cache_launch(const void* q, const void* k, const void* v, void* out, const int* pos, int pstride, int B,
-                         int T, int H, int Hkv, int Lmax, float scale, hipStream_t s) {
+bool cache_attn_ok(int H, int Hkv, int D, int T, int Lmax) {
+    return cache_shape_ok(H, Hkv, D, T, Lmax) && (long)Lmax * D * 2 < (1L << 31);
+}
+
+// The e4m3 cache: the 32-bit extents are Lmax * D bytes of a slab and Lmax * 4 bytes of its scales.
+bool cache_attn_fp8_ok(int H, int Hkv, int D, int T, int Lmax) {
+    return cache_shape_ok(H, Hkv, D, T, Lmax) && (long)Lmax * D < (1L << 31) && (long)Lmax * 4 < (1L << 31);
+}
+
+template <int D, class C>
+static void cache_launch(const void* q, const void* k, const void* v, cache::Scales<C> sc, void* out, const int* pos,
+                         int pstride, int B, int T, int H, int Hkv, int Lmax, float scale, hipStream_t s) {
+    typedef const typename C::elem* cptr;
     const int nqb = ((H / Hkv) * T + 127) / 128;
-    cache::cache_attn_kernel<D><<<nqb * B * Hkv, 256, (size_t)4 * 64 * D * 2, s>>>(
-        (const __bf16*)q, (const __bf16*)k, (const __bf16*)v, (__bf16*)out, pos, pstride, H, Hkv, Lmax, T,
-        scale * LOG2E, nqb);
+    cache::cache_attn_kernel<D, C><<<nqb * B * Hkv, 256, cache::lds_bytes<D, C>(), s>>>(
+        (const __bf16*)q, (cptr)k, (cptr)v, (__bf16*)out, pos, pstride, H, Hkv, Lmax, T, scale * LOG2E, nqb, sc);
 }
 
 void launch_cache_attn(const void* q, const void* k, const void* v, void* out, const int* pos, int pos_stride, int B,
                        int T, int H, int Hkv, int D, int Lmax, float scale, hipStream_t s) {
-    if (D == 64) cache_launch<64>(q, k, v, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, s);
-    else cache_launch<128>(q, k, v, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, s);
+    const cache::Scales<kvc::Bf16Cache> none{};
+    if (D == 64) cache_launch<64, kvc::Bf16Cache>(q, k, v, none, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, s);
+    else cache_launch<128, kvc::Bf16Cache>(q, k, v, none, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, s);
+}
+
+void launch_cache_attn_fp8(const void* q, const void* k8, const void* v8, const float* ks, const float* vs, void* out,
+                           const int* pos, int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax, float scale,
+                           hipStream_t s) {
+    const cache::Scales<kvc::Fp8Cache> sc{ks, vs};
+    if (D == 64) cache_launch<64, kvc::Fp8Cache>(q, k8, v8, sc, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, s);
+    else cache_launch<128, kvc::Fp8Cache>(q, k8, v8, sc, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, s);
 }

@@ -162,6 +162,12 @@ void launch_kv_dequant(const void* k8, const void* v8, const float* ks, const fl
 bool cache_attn_ok(int H, int Hkv, int D, int T, int Lmax);
 void launch_cache_attn(const void* q, const void* k, const void* v, void* out, const int* pos, int pos_stride, int B,
                        int T, int H, int Hkv, int D, int Lmax, float scale, hipStream_t s);
+// the same kernel over the fp8 cache (k8 / v8 e4m3 bytes, ks / vs their row scales): bit for bit launch_cache_attn on
+// what launch_kv_dequant writes
+bool cache_attn_fp8_ok(int H, int Hkv, int D, int T, int Lmax);
+void launch_cache_attn_fp8(const void* q, const void* k8, const void* v8, const float* ks, const float* vs, void* out,
+                           const int* pos, int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax, float scale,
+                           hipStream_t s);
 
 // decode_gemv.hip (M <= 16 token rows; epi 0 plain, 1 SwiGLU over [W1; W3], 2 fused QKV + RoPE + KV-cache write)
 struct GemvArgs {

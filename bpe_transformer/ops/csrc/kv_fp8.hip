@@ -17,11 +17,12 @@
 //                   by construction), the D / 8 adjacent lanes of a row reduce the row's amax bits with lane shuffles
 //                   (groups are wave-aligned: 64 and 256 are multiples of D / 8), each lane stores its 8 bytes with
 //                   one vector store, lane 0 of the group stores the scale.
-//   kv_dequant      rows [0, min(pos[b] + T, Lmax)) of each K and V slab -> bf16 scratch [B, Hkv, Lmax, D] (one
-//                   launch for both), rows past that untouched; pos is read on the device.  Feeds cache_attn for the
-//                   windows decode_attn does not take (G * T >= 9).
-// The decode attention over this cache is the Fp8Cache instantiation of decode_attn_kernel (decode_attn.hip, which
-// also holds the resource table of all these kernels).
+//   kv_dequant      rows [0, min(pos[b] + T, Lmax)) of each K and V slab -> a caller's bf16 pair [B, Hkv, Lmax, D]
+//                   (one launch for both), rows past that untouched; pos is read on the device.  A utility, and the
+//                   oracle of cache_attn's fp8 instantiation, which is bit for bit cache_attn on what this writes.
+// The attention over this cache is the Fp8Cache instantiation of decode_attn_kernel (decode_attn.hip, which also
+// holds the resource table of all these kernels) for G * T <= 8 query rows per kv head and that of cache_attn_kernel
+// (flash_attn_cache.hip: e4m3 tiles converted into the bf16 LDS image) beyond; no session dequantises into memory.
 #include "kv_cache.h"
 #include "kernels.h"
 

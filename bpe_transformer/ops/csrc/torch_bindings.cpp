@@ -1111,6 +1111,31 @@ at::Tensor cache_attn(const at::Tensor& q, const at::Tensor& kc, const at::Tenso
     return out;
 }
 
+// cache_attn over the fp8 cache as stored (k8 / v8 e4m3 bytes [B, Hkv, Lmax, D], k_scale / v_scale [B, Hkv, Lmax]):
+// bit for bit kv_dequant into a zeroed bf16 pair followed by cache_attn, in one launch and with no scratch.
+at::Tensor cache_attn_fp8(const at::Tensor& q, const at::Tensor& k8, const at::Tensor& v8, const at::Tensor& ks,
+                          const at::Tensor& vs, const at::Tensor& pos, int64_t H, double scale, int64_t T) {
+    TORCH_CHECK(k8.dim() == 4, "cache_attn_fp8: k8 must be [B, Hkv, Lmax, D]");
+    const int64_t B = k8.size(0), Hkv = k8.size(1), Lmax = k8.size(2), D = k8.size(3);
+    TORCH_CHECK(H > 0 && T > 0 && H < (1 << 16) && T < (1 << 24) && Lmax < (1LL << 31) &&
+                    cache_attn_fp8_ok((int)H, (int)Hkv, (int)D, (int)T, (int)Lmax),
+                "cache_attn_fp8: head dim 64/128, H a multiple of Hkv with H / Hkv <= 8, T >= 1 and a cache slab "
+                "below 2 GiB required");
+    check_cuda(q, "q");
+    TORCH_CHECK(q.scalar_type() == at::kBFloat16 && q.is_contiguous() && q.numel() == B * T * H * D,
+                "cache_attn_fp8: q must be contiguous bf16 [B*T, H*D]");
+    check_cache8(k8, ks, B, Hkv, "k8");
+    check_cache8(v8, vs, B, Hkv, "v8");
+    TORCH_CHECK(v8.sizes() == k8.sizes(), "cache_attn_fp8: k / v cache shapes differ");
+    const int pstride = check_pos(pos, B);
+    DevGuard g(q.device());
+    auto out = at::empty({B * T, H * D}, q.options());
+    launch_cache_attn_fp8(q.data_ptr(), k8.data_ptr(), v8.data_ptr(), ks.data_ptr<float>(), vs.data_ptr<float>(),
+                          out.data_ptr(), pos.data_ptr<int>(), pstride, (int)B, (int)T, (int)H, (int)Hkv, (int)D,
+                          (int)Lmax, (float)scale, cur_stream());
+    return out;
+}
+
 // rows [0, min(pos[b] + T, Lmax)) of every K and V slab -> bf16 k_out / v_out [B, Hkv, Lmax, D]; other rows untouched
 void kv_dequant(const at::Tensor& k8, const at::Tensor& v8, const at::Tensor& ks, const at::Tensor& vs,
                 const at::Tensor& pos, int64_t T, at::Tensor k_out, at::Tensor v_out) {
@@ -1438,6 +1463,8 @@ TORCH_LIBRARY(bpe_hip, m) {
     m.def("kv_dequant(Tensor k8, Tensor v8, Tensor k_scale, Tensor v_scale, Tensor pos, int T, Tensor(a!) k_out, "
           "Tensor(b!) v_out) -> ()");
     m.def("cache_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor pos, int H, float scale, int T) -> Tensor");
+    m.def("cache_attn_fp8(Tensor q, Tensor k8, Tensor v8, Tensor k_scale, Tensor v_scale, Tensor pos, int H, "
+          "float scale, int T) -> Tensor");
     m.def("rmsnorm_fwd(Tensor x, Tensor w, float eps) -> (Tensor, Tensor)");
     m.def("add_rmsnorm_fwd(Tensor x, Tensor d, Tensor w, float eps) -> (Tensor, Tensor, Tensor)");
     m.def("rmsnorm_bwd(Tensor dy, Tensor x, Tensor w, Tensor rstd, Tensor? dres=None, Tensor(a!)? dw_acc=None) -> "
@@ -1544,6 +1571,7 @@ TORCH_LIBRARY_IMPL(bpe_hip, CUDA, m) {
     m.impl("kv_append", &kv_append);
     m.impl("decode_attn", &decode_attn);
     m.impl("cache_attn", &cache_attn);
+    m.impl("cache_attn_fp8", &cache_attn_fp8);
     m.impl("decode_gemv", &decode_gemv);
     m.impl("decode_qkv", &decode_qkv);
     m.impl("decode_attn_proj", &decode_attn_proj);

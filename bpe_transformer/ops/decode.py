@@ -41,8 +41,12 @@ dequantised values, and that is how its consumers are defined:
   returned ``q`` is bit-identical);
 * :func:`decode_attention_fp8` (and ``decode_attention_partials_fp8``) is
   :func:`decode_attention` on the dequantised caches, reading half the bytes;
+* :func:`prefill_attention_fp8` (``cache_attn_fp8``) is
+  :func:`prefill_attention` on the dequantised caches, computed from the e4m3
+  rows as stored: on the GPU bit for bit :func:`kv_dequant` into a zeroed pair
+  followed by :func:`prefill_attention`, in one launch and with no scratch;
 * :func:`kv_dequant` writes the valid rows of a K / V pair as bf16 into a
-  scratch pair, for :func:`prefill_attention` (``cache_attn``) to read.
+  caller's pair -- a utility, and the oracle of that equality.
 """
 
 from __future__ import annotations
@@ -306,6 +310,16 @@ def decode_attention_fp8_reference(q, k8, v8, k_scale, v_scale, pos, n_heads, sc
     """:func:`decode_attention_reference` on the dequantised caches (fp32 values, so nothing is rounded twice)."""
     return decode_attention_reference(q, kv_dequantize_reference(k8, k_scale, torch.float32),
                                       kv_dequantize_reference(v8, v_scale, torch.float32), pos, n_heads, scale, n_new)
+
+
+def prefill_attention_fp8(q: Tensor, k8: Tensor, v8: Tensor, k_scale: Tensor, v_scale: Tensor, pos: Tensor,
+                          n_heads: int, scale: float | None = None, n_new: int = 1) -> Tensor:
+    """:func:`prefill_attention` over an fp8 cache (``csrc/flash_attn_cache.hip``, the ``Fp8Cache`` instantiation):
+    any ``n_new``, the e4m3 rows and their scales read as stored."""
+    scale = _scale(k8, scale)
+    if q.is_cuda:
+        return ops().cache_attn_fp8(q.contiguous(), k8, v8, k_scale, v_scale, pos, n_heads, scale, n_new)
+    return decode_attention_fp8_reference(q, k8, v8, k_scale, v_scale, pos, n_heads, scale, n_new)
 
 
 def decode_attention_partials_fp8(q: Tensor, k8: Tensor, v8: Tensor, k_scale: Tensor, v_scale: Tensor, pos: Tensor,

@@ -10,10 +10,14 @@ one in the same process, alternating over ``--rounds`` rounds (median and min of
 fp8 attention kernel alone.  ``--long-context`` replaces the model by the regime the fp8 cache is for: a Llama-shaped
 model cut to ``--layers`` layers (d 2048, 32 query / 4 KV heads, D 64), ``max_len`` 4096 and a prompt that nearly
 fills it (``4096 - tokens - 2``), batch 64 by default.
+``--weight-dtype fp8`` adds, in the same alternating way, the fp8-weight session (``DecodeSession(weight_dtype="fp8")``)
+against the bf16 one: median, min and max of each over the rounds, the ratio of the medians and both sessions'
+projection-weight bytes.
 Random-init weights, synthetic prompts; one JSON line per configuration.
 
     python benchmarks/decode_bench.py --model gpt2-small --batch 1 8 64 --prompt 128 --tokens 256
     python benchmarks/decode_bench.py --kv-dtype fp8 --long-context --batch 64 --tokens 64
+    python benchmarks/decode_bench.py --weight-dtype fp8 --model llama-1.1b --batch 1 8 64
 """
 import argparse
 import json
@@ -79,6 +83,25 @@ def fp8_arm(model, sess, ids, prompt, tokens, rounds, graph, chunk):
     }
 
 
+def w8_arm(model, sess, ids, prompt, tokens, rounds, graph, chunk):
+    """bf16- and fp8-weight sessions alternating in this process -> the extra fields of the JSON line."""
+    B = ids.shape[0]
+    w8 = DecodeSession(model, B, max_len=sess.max_len, use_graph=graph, weight_dtype="fp8", prefill_chunk=chunk)
+    t = {"bf16": [], "fp8": []}
+    for _ in range(rounds):
+        t["bf16"].append(time_decode(sess, ids, prompt, tokens))
+        t["fp8"].append(time_decode(w8, ids, prompt, tokens))
+    med = lambda x: sorted(x)[len(x) // 2]  # noqa: E731
+    mmm = lambda x: [round(med(x) * 1e3, 4), round(min(x) * 1e3, 4), round(max(x) * 1e3, 4)]  # noqa: E731
+    return {
+        "w_rounds": rounds,
+        "bf16w_decode_ms_per_step_median_min_max": mmm(t["bf16"]),
+        "fp8w_decode_ms_per_step_median_min_max": mmm(t["fp8"]),
+        "fp8w_over_bf16w": round(med(t["fp8"]) / med(t["bf16"]), 4),
+        "bf16_weight_bytes": sess.weight_nbytes(), "fp8_weight_bytes": w8.weight_nbytes(),
+    }
+
+
 def ragged_lengths(batch, prompt):
     """Prompt lengths over [prompt / 4, prompt], fixed seed; the longest is ``prompt`` itself."""
     g = torch.Generator().manual_seed(1234)
@@ -112,7 +135,10 @@ def main():
                     help="also time a ragged session: prompt lengths spread over [prompt/4, prompt]")
     ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: also time the fp8-cache session against the bf16 one, alternating in this process")
-    ap.add_argument("--rounds", type=int, default=5, help="alternating rounds of the --kv-dtype fp8 comparison")
+    ap.add_argument("--weight-dtype", choices=["bf16", "fp8"], default="bf16",
+                    help="fp8: also time the fp8-weight session against the bf16 one, alternating in this process")
+    ap.add_argument("--rounds", type=int, default=5,
+                    help="alternating rounds of the --kv-dtype fp8 / --weight-dtype fp8 comparisons")
     ap.add_argument("--long-context", action="store_true",
                     help="Llama-shaped model cut to --layers layers, max_len 4096, a prompt that nearly fills it")
     ap.add_argument("--layers", type=int, default=4)
@@ -171,6 +197,8 @@ def main():
             }
             if a.kv_dtype == "fp8":
                 out.update(fp8_arm(model, sess, ids, a.prompt, a.tokens, a.rounds, not a.no_graph, chunk))
+            if a.weight_dtype == "fp8":
+                out.update(w8_arm(model, sess, ids, a.prompt, a.tokens, a.rounds, not a.no_graph, chunk))
             if a.ragged:
                 lengths = ragged_lengths(B, a.prompt)
                 rs = DecodeSession(model, B, max_len=max_len, use_graph=not a.no_graph, ragged=True)

@@ -47,8 +47,25 @@ e4m3 rows and their scales directly) for windows of more than ``8 / G`` tokens
 is not used, so a prompt token sees the quantised keys of its own window too,
 whatever the chunking.  Not available with a draft model yet.
 
+**fp8 weights** (``weight_dtype="fp8"``, opt-in): the projection matrices --
+``[Wq; Wk; Wv]``, ``Wo``, ``[W1; W3]``, ``W2`` and the LM head -- are held as
+``float8_e4m3fn`` rows with one power-of-two fp32 scale per output feature
+(``ops/decode.py: weight_quantize``, the row format of the fp8 cache), ``(K +
+4) / (2 K)`` of the bf16 bytes; embeddings and norm weights stay bf16.  A
+session with fp8 weights is a bf16 session on a model whose projection weights
+are the dequantised rows -- bit for bit, on every path.  The batch <= 8 decode
+step streams the e4m3 rows in the skinny GEMMs (``csrc/decode_gemv.hip``),
+which is where the halved bytes count.  Every other step -- flash prefill,
+``cache_attn`` appends, ``decode_attn`` windows of more than one token,
+``score``, batch > 8 -- dequantises each matrix into one session-owned bf16
+scratch (``w_dequant``) just before its library GEMM, so there it costs a
+launch and a write per matrix.  Composes with ``kv_dtype="fp8"``, ``ragged``,
+``prefill_chunk``, the device sampler and the graph (the scratch is static).
+Not available with a draft model yet.
+
 On the CPU, in fp32, or with the reference ablations (post-norm, no RMSNorm,
-non-SwiGLU FFN) the same session runs the oracle math over the same cache.
+non-SwiGLU FFN) the same session runs the oracle math over the same cache
+(with fp8 weights: on a copy of the model that holds the dequantised rows).
 
 **One engine, two position layouts.**  The host side is written once, as "the
 first ``n[i]`` tokens of ``ids[i]`` go to sequence ``rows[i]``", and every
@@ -84,6 +101,7 @@ its own new tokens -- and are overwritten as the sequence grows.
 
 from __future__ import annotations
 
+import copy
 import math
 import os
 
@@ -259,14 +277,42 @@ class KVView:
             return h.cache_attn_fp8(q, k, v, ks, vs, pos, H, scale, T)
         return h.decode_attn_fp8(q, k, v, ks, vs, pos, H, scale, combine, T)
 
-    def decode_qkv(self, h, xr: Tensor, xd, ln1: Tensor, eps: float, wqkv: Tensor, li: int, H: int, rope):
+    def decode_qkv(self, h, xr: Tensor, xd, ln1: Tensor, eps: float, wqkv: Tensor, li: int, H: int, rope, ws=()):
         """QKV step of the skinny decode route -> ``(q, x + xd)``: the fused ``decode_qkv`` (projection, RoPE, cache
         write), or for fp8 ``decode_gemv`` with the plain epilogue followed by :meth:`append` (a row's amax spans
-        several workgroups of the fused epilogue)."""
+        several workgroups of the fused epilogue).  ``ws``: ``(w_scale,)`` when ``wqkv`` is an e4m3 matrix."""
         if self.scales is None:
-            return h.decode_qkv(xr, xd, ln1, eps, wqkv, self.k[li], self.v[li], rope[0], rope[1], self.pos, H, rope[2])
-        qkv, s = h.decode_gemv(xr, xd, ln1, eps, wqkv, 0)
+            return h.decode_qkv(xr, xd, ln1, eps, wqkv, self.k[li], self.v[li], rope[0], rope[1], self.pos, H, rope[2],
+                                *ws)
+        qkv, s = h.decode_gemv(xr, xd, ln1, eps, wqkv, 0, *ws)
         return self.append(h, qkv, li, 1, H, rope), s
+
+
+_W8_PROJECTIONS = (("attn", ("q_proj", "k_proj", "v_proj", "output_proj")), ("ffn", ("w1", "w2", "w3")))
+
+
+def _dequantised_copy(model):
+    """A copy of ``model`` whose five projection families -- Wq / Wk / Wv, Wo, W1 / W3, W2 and the LM head -- hold
+    ``weight_dequantize(weight_quantize(W))`` in the model's dtype: what a session with fp8 weights computes with.
+    (Rows are quantised one by one, so the separate matrices give what the concatenated ones do.)  Embeddings and norm
+    weights are the originals' values; a tied embedding is untied, the head alone being quantised."""
+    from ..ops.decode import weight_dequantize, weight_quantize
+
+    def deq(lin) -> None:
+        w = lin.weight.detach()
+        lin.weight = torch.nn.Parameter(weight_dequantize(*weight_quantize(w), w.dtype), requires_grad=False)
+
+    m = copy.deepcopy(model)
+    for layer in m.layers:
+        for part, names in _W8_PROJECTIONS:
+            for name in names:
+                lin = getattr(getattr(layer, part), name, None)
+                if lin is not None:
+                    deq(lin)
+    if m.lm_head.weight is m.token_embeddings.weight:
+        m.token_embeddings.weight = torch.nn.Parameter(m.token_embeddings.weight.detach().clone(), requires_grad=False)
+    deq(m.lm_head)
+    return m
 
 
 def _top_k_logits(logits: Tensor, top_k: int | None) -> Tensor:
@@ -318,11 +364,23 @@ class DecodeSession:
     so prefill, chunked prefill and decode have one semantics, that of a bf16 cache holding the dequantised rows.  At
     batch <= 8 the QKV projection is ``decode_gemv`` followed by ``kv_append_fp8`` (a row's amax spans several
     workgroups of the fused ``decode_qkv`` epilogue): 6 launches per layer instead of 5.
+
+    ``weight_dtype="fp8"`` holds ``[Wq; Wk; Wv]``, ``Wo``, ``[W1; W3]``, ``W2`` and the LM head as e4m3 rows with one
+    power-of-two scale per output feature (``ops/decode.py: weight_quantize``), ``(K + 4) / (2 K)`` of the bf16 bytes,
+    and no bf16 copy of them; embeddings and norm weights stay bf16.  The session is a bf16 session on a model whose
+    projection weights are the dequantised rows, bit for bit.  The batch <= 8 decode step streams the e4m3 rows in
+    the skinny GEMMs; prefill, appends, ``score`` and batch > 8 dequantise each matrix into one static bf16 scratch
+    (sized for the largest, reused in stream order) just before its GEMM, and pay for that.  Off the fast path the
+    session runs the oracle math on a copy of the model that holds the dequantised rows.  No draft model yet.
     """
 
     def __init__(self, model, batch: int, max_len: int | None = None, use_graph: bool = True, ragged: bool = False,
-                 prefill_chunk: int | None = None, kv_dtype: str = "bf16"):
+                 prefill_chunk: int | None = None, kv_dtype: str = "bf16", weight_dtype: str = "bf16"):
         assert prefill_chunk is None or prefill_chunk >= 1, "prefill_chunk: a positive number of tokens, or None"
+        if weight_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"weight_dtype: 'bf16' or 'fp8', got {weight_dtype!r}")
+        self.weight_dtype = weight_dtype
+        self.w8 = weight_dtype == "fp8"
         self.model = model
         self.ragged = ragged
         self.prefill_chunk = prefill_chunk
@@ -350,6 +408,8 @@ class DecodeSession:
         self._samp = None  # the device sampler's buffers and graph (_sampler_state)
         if self.fast:
             self._prepare_weights()
+        elif self.w8:  # the definition of the feature: the oracle math on the dequantised model
+            self.model = _dequantised_copy(model)
 
     # ------------------------------------------------------------------ setup
     def _fast_ok(self) -> bool:
@@ -365,21 +425,44 @@ class DecodeSession:
         return self.D in ops.attention.SUPPORTED_HEAD_DIMS and G in (1, 2, 4, 8) and self.H % self.Hkv == 0
 
     def _prepare_weights(self) -> None:
+        """``_w``: per layer ``(ln1, wqkv, wo, ln2, w13, w2, eps)``; ``_head``: the LM head.  A projection is ``(w,)``
+        (bf16) or ``(w8, w_scale)`` (fp8 weights: no bf16 copy is kept) -- the trailing arguments of its skinny op."""
+        from ..ops.decode import weight_quantize
         from .fused_block import _cat_weights
 
+        pack = (lambda w: weight_quantize(w.detach())) if self.w8 else (lambda w: (w.detach(),))
         self._w = []
         for layer in self.model.layers:
             a, f = layer.attn, layer.ffn
             self._w.append((
-                layer.ln1.weight.detach(), _cat_weights([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight]),
-                a.output_proj.weight.detach(), layer.ln2.weight.detach(), _cat_weights([f.w1.weight, f.w3.weight]),
-                f.w2.weight.detach(), layer.ln1.eps,
+                layer.ln1.weight.detach(), pack(_cat_weights([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight])),
+                pack(a.output_proj.weight), layer.ln2.weight.detach(), pack(_cat_weights([f.w1.weight, f.w3.weight])),
+                pack(f.w2.weight), layer.ln1.eps,
             ))
+        self._head = pack(self.model.lm_head.weight)
+        self._wscratch = None
+        if self.w8:  # one bf16 scratch for the wide steps, sized for the largest matrix (static: graph-safe)
+            n = max(w[0].numel() for lw in self._w for w in (lw[1], lw[2], lw[4], lw[5]))
+            self._wscratch = torch.empty(max(n, self._head[0].numel()), device=self.device, dtype=torch.bfloat16)
         rope = self.model.layers[0].attn.rope
         if rope is not None:  # (cos, sin, use_rope) as the kernels take them
             self._rope = (rope.cos.float().contiguous(), rope.sin.float().contiguous(), True)
         else:  # empty tables and use_rope = False
             self._rope = (*[torch.empty(0, device=self.device, dtype=torch.float32)] * 2, False)
+
+    def _wide(self, h, w) -> Tensor:
+        """The bf16 matrix of projection ``w`` for a library GEMM: itself, or (fp8 weights) dequantised into the
+        session's scratch, which the next call overwrites -- stream order keeps the GEMM in between safe."""
+        if len(w) == 1:
+            return w[0]
+        out = self._wscratch[: w[0].numel()].view(w[0].shape)
+        h.w_dequant(w[0], w[1], out)
+        return out
+
+    def weight_nbytes(self) -> int:
+        """Bytes of the session's projection weights (fp8: bytes and scales; the scratch is not counted)."""
+        ws = [w for lw in self._w for w in (lw[1], lw[2], lw[4], lw[5])] + [self._head] if self.fast else []
+        return sum(t.numel() * t.element_size() for w in ws for t in w)
 
     def reset(self) -> None:
         self.cache.reset()
@@ -779,17 +862,17 @@ class DecodeSession:
                 h1, _ = h.rmsnorm_fwd(xr, ln1, eps)
             else:
                 xr, h1, _ = h.add_rmsnorm_fwd(xr, xd, ln1, eps)
-            qkv = torch.matmul(h1, wqkv.t())
+            qkv = torch.matmul(h1, self._wide(h, wqkv).t())
             if kind == "flash":
                 q, k, v = qkv[:, : H * D], qkv[:, H * D : (H + Hkv) * D], qkv[:, (H + Hkv) * D :]
                 o, _ = h.fa_fwd(q, k, v, rope[0], rope[1], B, T, H, Hkv, D, True, rope[2], 1.0 / math.sqrt(D))
                 kv.append(h, qkv, li, T, H, rope)
             else:
                 o = kv.attend(h, kv.append(h, qkv, li, T, H, rope), li, T, H, kind)
-            g1 = torch.matmul(o, wo.t())
+            g1 = torch.matmul(o, self._wide(h, wo).t())
             xr, h2, _ = h.add_rmsnorm_fwd(xr, g1, ln2, eps)
-            a = h.swiglu_fwd(torch.matmul(h2, w13.t()))
-            xd = torch.matmul(a, w2.t())
+            a = h.swiglu_fwd(torch.matmul(h2, self._wide(h, w13).t()))
+            xd = torch.matmul(a, self._wide(h, w2).t())
         if all_logits:
             pass
         elif T > 1 and last is not None:  # ragged: each sequence's own last valid token
@@ -801,21 +884,22 @@ class DecodeSession:
             xd = xd.view(B, T, -1)[:, -1].contiguous()
         fin = m.ln_final
         _, hf, _ = h.add_rmsnorm_fwd(xr, xd, fin.weight, fin.eps)
-        logits = torch.matmul(hf, m.lm_head.weight.t())
+        logits = torch.matmul(hf, self._wide(h, self._head).t())
         if advance:
             kv.pos.add_(T if step is None else step)
         return logits
 
     def _gemv_fits(self, m: int) -> bool:
         cfg = self.model.config
-        return all(_gemv_ok(m, k) for k in (cfg.d_model, self.H * self.D, self._w[0][5].shape[1]))
+        return all(_gemv_ok(m, k) for k in (cfg.d_model, self.H * self.D, self._w[0][5][0].shape[1]))
 
     def _decode_gemv(self, ids: Tensor, step: Tensor | None, kv: KVView) -> Tensor:
         """Decode step for batch <= 16 on the fused skinny-GEMM kernels (``csrc/decode_gemv.hip``): per layer
         qkv (+RMSNorm, +RoPE, +cache write) -> split-K decode attention -> Wo (+ the split combine) -> [W1; W3]
         (+residual add, +RMSNorm, +SwiGLU) -> W2; the residual add of W2's output is folded into the next layer's
         QKV prologue: 5 launches per layer.  An fp8 cache takes 6: the QKV projection with the plain epilogue, then
-        ``kv_append_fp8`` (RoPE, quantisation, cache write), and ``decode_attn_fp8``."""
+        ``kv_append_fp8`` (RoPE, quantisation, cache write), and ``decode_attn_fp8``.  fp8 weights: the same launches,
+        every projection called with its ``(w8, w_scale)`` pair."""
         h, rope = self._hip(), self._rope
         m = self.model
         H = self.H
@@ -823,15 +907,15 @@ class DecodeSession:
         xr = m.token_embeddings(ids).reshape(B, -1)
         xd = None
         for li, (ln1, wqkv, wo, ln2, w13, w2, eps) in enumerate(self._w):
-            q, s = kv.decode_qkv(h, xr, xd, ln1, eps, wqkv, li, H, rope)
+            q, s = kv.decode_qkv(h, xr, xd, ln1, eps, wqkv[0], li, H, rope, wqkv[1:])
             if xd is not None:
                 xr = s
             part = kv.attend(h, q, li, 1, H, "decode", combine=False)
-            g1 = h.decode_attn_proj(part, wo)  # the flash-decoding combine runs in Wo's prologue
-            a, xr = h.decode_gemv(xr, g1, ln2, eps, w13, 1)
-            xd, _ = h.decode_gemv(a, None, None, 0.0, w2, 0)
+            g1 = h.decode_attn_proj(part, *wo)  # the flash-decoding combine runs in Wo's prologue
+            a, xr = h.decode_gemv(xr, g1, ln2, eps, w13[0], 1, *w13[1:])
+            xd, _ = h.decode_gemv(a, None, None, 0.0, w2[0], 0, *w2[1:])
         fin = m.ln_final
-        logits, _ = h.decode_gemv(xr, xd, fin.weight, fin.eps, m.lm_head.weight, 0)
+        logits, _ = h.decode_gemv(xr, xd, fin.weight, fin.eps, self._head[0], 0, *self._head[1:])
         kv.pos.add_(1 if step is None else step)
         return logits
 

@@ -226,6 +226,7 @@ class TransformerLM(nn.Module):
         draft_model: "TransformerLM | None" = None,
         num_draft_tokens: int = 4,
         kv_dtype: str = "bf16",
+        weight_dtype: str = "bf16",
     ) -> Tensor:
         """Autoregressive sampling (temperature, top-k, nucleus).  ``prompt``: ``[S]`` or ``[B, S]``.
 
@@ -251,11 +252,21 @@ class TransformerLM(nn.Module):
         ``kv_dtype="fp8"`` keeps the KV cache as e4m3 rows with power-of-two scales (``DecodeSession(...,
         kv_dtype="fp8")``: about half the cache bytes); it needs the KV-cache path and is not yet supported together
         with ``draft_model`` (``ValueError``).
+
+        ``weight_dtype="fp8"`` decodes with the projection matrices held as e4m3 rows with power-of-two scales
+        (``DecodeSession(..., weight_dtype="fp8")``: about half the weight bytes a decode step streams).  The output
+        is that of this call on a model whose projection weights are the dequantised rows.  It needs the KV-cache
+        path and is not yet supported together with ``draft_model`` (``ValueError``).
         """
         assert sampler in ("host", "device"), "sampler: 'host' or 'device'"
         if kv_dtype not in ("bf16", "fp8"):
             raise ValueError(f"kv_dtype: 'bf16' or 'fp8', got {kv_dtype!r}")
+        if weight_dtype not in ("bf16", "fp8"):
+            raise ValueError(f"weight_dtype: 'bf16' or 'fp8', got {weight_dtype!r}")
         if draft_model is not None:
+            if weight_dtype != "bf16":
+                raise ValueError("weight_dtype='fp8' with draft_model is not supported yet: speculative decoding runs "
+                                 "on bf16 weights only")
             if kv_dtype != "bf16":
                 raise ValueError("kv_dtype='fp8' with draft_model is not supported yet: speculative decoding runs on "
                                  "the bf16 cache only")
@@ -269,24 +280,27 @@ class TransformerLM(nn.Module):
                 from .generation import DecodeSession
 
                 sess = DecodeSession(self, len(prompt), max_len=longest + max_new_tokens, ragged=True,
-                                     kv_dtype=kv_dtype)
+                                     kv_dtype=kv_dtype, weight_dtype=weight_dtype)
                 return sess.generate(list(prompt), max_new_tokens, temperature, top_p, eos_token_id, generator, **kw)
             # without the cache: one sequence at a time through the loop below (which stops at its EOS)
             return [self.generate(p.reshape(-1), max_new_tokens, temperature, top_p, eos_token_id, generator, use_cache,
-                                  kv_dtype=kv_dtype, **kw) for p in prompt]
+                                  kv_dtype=kv_dtype, weight_dtype=weight_dtype, **kw) for p in prompt]
         squeeze = prompt.dim() == 1
         ids = prompt.unsqueeze(0) if squeeze else prompt
         self._fence(self)  # the decode session packs / reads every weight up front
         if use_cache and ids.shape[1] + max_new_tokens <= self.context_length and max_new_tokens > 0:
             from .generation import DecodeSession
 
-            sess = DecodeSession(self, ids.shape[0], max_len=ids.shape[1] + max_new_tokens, kv_dtype=kv_dtype)
+            sess = DecodeSession(self, ids.shape[0], max_len=ids.shape[1] + max_new_tokens, kv_dtype=kv_dtype,
+                                 weight_dtype=weight_dtype)
             out = sess.generate(ids, max_new_tokens, temperature, top_p, eos_token_id, generator, **kw)
             return out[0] if squeeze else out
         assert sampler == "host" or max_new_tokens <= 0, "sampler='device' needs the KV-cache path (use_cache, and " \
             "prompt + max_new_tokens within context_length)"
         assert kv_dtype == "bf16" or max_new_tokens <= 0, "kv_dtype='fp8' needs the KV-cache path (use_cache, and " \
             "prompt + max_new_tokens within context_length)"
+        assert weight_dtype == "bf16" or max_new_tokens <= 0, "weight_dtype='fp8' needs the KV-cache path (use_cache, " \
+            "and prompt + max_new_tokens within context_length)"
         for _ in range(max_new_tokens):
             ctx = ids[:, -self.context_length :]
             # (sampling is not document-masked: hidden_states takes explicit bounds only, never doc_mask_token)

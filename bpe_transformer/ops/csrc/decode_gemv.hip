@@ -20,9 +20,19 @@
 // latency overlaps the input read / normalization; the rest streams 4 vectors in flight.
 // Prologue variant (GemvArgs::part): the input rows are the split-K decode attention's partial (o, m, l)
 // triples, merged here -- the output projection absorbs the flash-decoding combine launch.
+//
+// fp8 weights (GemvArgs::wscale, the W8 template switch of both kernels): W is e4m3 bytes [N][K] (row stride ldw
+// bytes) with one power-of-two fp32 scale per row (the row format of the fp8 KV cache, kv_fp8.hip), half the
+// bytes of the stream.  Element-to-lane mapping and accumulation order are those of the bf16 body: a lane loads
+// the same 8 elements as 8 bytes, converts them exactly (v_cvt_pk_f32_fp8; for the MFMA A fragment the upper halves
+// packed into bf16, v_perm_b32), and accumulates the unscaled bytes; the row's scale multiplies the finished fp32
+// dot once (VALU kernel: after the lane reduction; MFMA kernel: the C rows as they go to LDS).  A power of two
+// commutes with every rounding on the way while nothing leaves the fp32 normal range, so the result is bit for
+// bit that of the bf16 kernel on the dequantised rows, at one multiply per row instead of one per element.
+// w_dequant writes such a matrix out as bf16, for the callers that hand it to a library GEMM.
 #include <cstdlib>
 
-#include "common.h"
+#include "kv_cache.h"
 #include "kernels.h"
 
 namespace bpe {
@@ -33,6 +43,35 @@ namespace gv {
 __device__ __forceinline__ u16x8 wload(const u16* p) {
     return __builtin_nontemporal_load(reinterpret_cast<const u16x8*>(p));
 }
+
+// The 8 weight elements a lane loads at once, as stored: 16 B of bf16, or (W8) 8 B of e4m3.
+template <bool W8> struct Wt;
+template <> struct Wt<false> {
+    typedef u16 E;
+    typedef u16x8 V;
+    static __device__ __forceinline__ V load(const E* p) { return wload(p); }
+    static __device__ __forceinline__ float f(V v, int e) { return bf2f(v[e]); }
+    static __device__ __forceinline__ bf16x8 frag(V v) { return __builtin_bit_cast(bf16x8, v); }
+};
+template <> struct Wt<true> {
+    typedef unsigned char E;
+    typedef u32x2 V;
+    static __device__ __forceinline__ V load(const E* p) {
+        return __builtin_nontemporal_load(reinterpret_cast<const V*>(p));
+    }
+    // element e as fp32, unscaled (constant e after unrolling; repeated conversions of one word fold)
+    static __device__ __forceinline__ float f(V v, int e) { return kvc::fp8x2(v[e / 4], (e % 4) >= 2)[e % 2]; }
+    // the 8 elements as a bf16 MFMA fragment, unscaled: an e4m3 value is a bf16 value, so the upper half of its fp32
+    static __device__ __forceinline__ bf16x8 frag(V v) {
+        u32x4 r;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const f32x2 p = kvc::fp8x2(v[i / 2], i & 1);
+            r[i] = (__float_as_uint(p.y) & 0xffff0000u) | (__float_as_uint(p.x) >> 16);  // one v_perm_b32
+        }
+        return __builtin_bit_cast(bf16x8, r);
+    }
+};
 
 constexpr int LPR = 16;  // lanes per weight row
 constexpr int RPW = 4;   // rows per wave
@@ -99,9 +138,11 @@ __device__ __forceinline__ void gemv_prologue_rows(const GemvArgs& a, u16* hs, i
 }
 
 // RAG (epilogue 2 only): one position per row (GemvArgs::pos_stride == 1).  A template switch, so that the
-// shared-position instantiation is the code it was before positions could differ.
-template <int MM, int EPI, bool RAG = false>
+// shared-position instantiation is the code it was before positions could differ.  W8: e4m3 weight rows with a
+// scale each (the header states the scheme); likewise a switch, and the bf16 instantiations are the code they were.
+template <int MM, int EPI, bool RAG = false, bool W8 = false>
 __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
+    typedef Wt<W8> WT;
     extern __shared__ __attribute__((aligned(16))) u16 hs[];  // [MM][K] normalized input rows (bf16)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int K = a.K, nv = K / 8;
@@ -119,14 +160,16 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
         n = blockIdx.x * 16 + wslot;
         valid = n < a.N;
     }
-    const u16* wr = reinterpret_cast<const u16*>(a.W) + (long)(valid ? n : 0) * a.ldw;
+    const typename WT::E* wr = reinterpret_cast<const typename WT::E*>(a.W) + (long)(valid ? n : 0) * a.ldw;
+    float ws = 1.f;  // W8: the row's scale, in flight with the weights
+    if constexpr (W8) ws = valid ? a.wscale[n] : 1.f;
     // the first PF weight vectors are in flight while the prologue reads and normalizes the input rows: the
     // decode step is latency-bound, and the weight stream does not depend on the prologue
-    u16x8 wp[PF];
+    typename WT::V wp[PF];
 #pragma unroll
     for (int u = 0; u < PF; ++u) {
         const int i = l16 + LPR * u;
-        wp[u] = (valid && i < nv) ? wload(wr + 8 * i) : u16x8{};
+        wp[u] = (valid && i < nv) ? WT::load(wr + 8 * i) : typename WT::V{};
     }
     // ---- prologue: rows M..MM-1 of the (rounded-up) LDS tile are zero, rows < M from the shared prologue
     for (int m = a.M + wv; m < MM; m += 4)
@@ -146,15 +189,15 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
             for (int m = 0; m < MM; ++m) {
                 const u16x8 hv = *reinterpret_cast<const u16x8*>(hs + (long)m * K + 8 * i);
 #pragma unroll
-                for (int e = 0; e < 8; ++e) acc[m] += bf2f(wp[u][e]) * bf2f(hv[e]);
+                for (int e = 0; e < 8; ++e) acc[m] += WT::f(wp[u], e) * bf2f(hv[e]);
             }
         }
         for (int i0 = l16 + LPR * PF; i0 < nv; i0 += LPR * UNR) {
-            u16x8 w[UNR];
+            typename WT::V w[UNR];
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
                 const int i = i0 + LPR * u;
-                w[u] = i < nv ? wload(wr + 8 * i) : u16x8{};
+                w[u] = i < nv ? WT::load(wr + 8 * i) : typename WT::V{};
             }
 #pragma unroll
             for (int u = 0; u < UNR; ++u) {
@@ -164,7 +207,7 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
                 for (int m = 0; m < MM; ++m) {
                     const u16x8 hv = *reinterpret_cast<const u16x8*>(hs + (long)m * K + 8 * i);
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) acc[m] += bf2f(w[u][e]) * bf2f(hv[e]);
+                    for (int e = 0; e < 8; ++e) acc[m] += WT::f(w[u], e) * bf2f(hv[e]);
                 }
             }
         }
@@ -173,6 +216,7 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
     for (int m = 0; m < MM; ++m) {
 #pragma unroll
         for (int off = LPR / 2; off > 0; off >>= 1) acc[m] += __shfl_xor(acc[m], off);
+        if constexpr (W8) acc[m] *= ws;
     }
     // ---- epilogues (lane l16 == 0 of each row holds the dots; partners are one row slot apart = 16 lanes)
     if constexpr (EPI == 0) {
@@ -255,8 +299,9 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
 // tokens at one k would otherwise hit the same banks).
 constexpr int MF_PF = 8;  // k-steps (32 each) of W in flight per wave
 
-template <int EPI, bool RAG = false>
+template <int EPI, bool RAG = false, bool W8 = false>
 __global__ void __launch_bounds__(256) gemv_mfma_kernel(const GemvArgs a) {
+    typedef Wt<W8> WT;
     extern __shared__ __attribute__((aligned(16))) u16 hs[];  // [M][K + 8] input rows, then float red[4][16][17]
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int K = a.K, ldh = K + 8, nks = K / 32;
@@ -274,14 +319,33 @@ __global__ void __launch_bounds__(256) gemv_mfma_kernel(const GemvArgs a) {
         n = blockIdx.x * 16 + r16;
         valid = n < a.N;
     }
-    const u16* wr = reinterpret_cast<const u16*>(a.W) + (long)(valid ? n : 0) * a.ldw + 8 * kq;
+    const typename WT::E* wr = reinterpret_cast<const typename WT::E*>(a.W) + (long)(valid ? n : 0) * a.ldw + 8 * kq;
+    // W8: the scales of the C rows this lane will hold (4 kq + i, the row mapping above), in flight with the weights
+    float ws[4] = {1.f, 1.f, 1.f, 1.f};
+    if constexpr (W8) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int r = 4 * kq + i;
+            int nr;
+            bool vr;
+            if constexpr (EPI == 1) {
+                const int F = a.N / 2, j = j0 + (r & 7);
+                vr = j < F;
+                nr = r < 8 ? j : F + j;
+            } else {
+                nr = blockIdx.x * 16 + r;
+                vr = nr < a.N;
+            }
+            ws[i] = vr ? a.wscale[nr] : 1.f;
+        }
+    }
     // wave wv owns k-steps [ks0, ks1) (K split in quarters)
     const int per = (nks + 3) / 4, ks0 = min(nks, wv * per), ks1 = min(nks, ks0 + per);
-    u16x8 wp[MF_PF];
+    typename WT::V wp[MF_PF];
 #pragma unroll
     for (int u = 0; u < MF_PF; ++u) {
         const int ks = ks0 + u;
-        wp[u] = (valid && ks < ks1) ? wload(wr + 32 * ks) : u16x8{};
+        wp[u] = (valid && ks < ks1) ? WT::load(wr + 32 * ks) : typename WT::V{};
     }
     gemv_prologue_rows(a, hs, ldh, tid);
     __syncthreads();
@@ -294,26 +358,25 @@ __global__ void __launch_bounds__(256) gemv_mfma_kernel(const GemvArgs a) {
         const int ks = ks0 + u;
         if (ks >= ks1) break;
         const u16x8 bv = tok ? *reinterpret_cast<const u16x8*>(hb + 32 * ks) : u16x8{};
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wp[u]),
-                                                      __builtin_bit_cast(bf16x8, bv), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(WT::frag(wp[u]), __builtin_bit_cast(bf16x8, bv), acc, 0, 0, 0);
     }
     for (int ks = ks0 + MF_PF; ks < ks1; ks += 4) {
-        u16x8 w4[4];
+        typename WT::V w4[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u)
-            w4[u] = (valid && ks + u < ks1) ? wload(wr + 32 * (ks + u)) : u16x8{};
+            w4[u] = (valid && ks + u < ks1) ? WT::load(wr + 32 * (ks + u)) : typename WT::V{};
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             if (ks + u >= ks1) break;
             const u16x8 bv = tok ? *reinterpret_cast<const u16x8*>(hb + 32 * (ks + u)) : u16x8{};
-            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w4[u]),
-                                                          __builtin_bit_cast(bf16x8, bv), acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(WT::frag(w4[u]), __builtin_bit_cast(bf16x8, bv), acc, 0, 0,
+                                                          0);
         }
     }
     // ---- sum the 4 waves' partial tiles: C[row = 4 kq + i][col = r16]
     float* red = reinterpret_cast<float*>(hs + (long)a.M * ldh);  // [4][16][17]
 #pragma unroll
-    for (int i = 0; i < 4; ++i) red[(wv * 16 + 4 * kq + i) * 17 + r16] = acc[i];
+    for (int i = 0; i < 4; ++i) red[(wv * 16 + 4 * kq + i) * 17 + r16] = W8 ? acc[i] * ws[i] : acc[i];
     __syncthreads();
     const int r = tid >> 4, m = tid & 15;  // output tile element (weight row r, token m)
     float c = 0.f, cp = 0.f;
@@ -358,6 +421,23 @@ __global__ void __launch_bounds__(256) gemv_mfma_kernel(const GemvArgs a) {
     }
 }
 
+// e4m3 rows [N][K] (row stride ldw bytes) and their scales -> bf16 [N][K] (contiguous): one thread per 8 elements,
+// an 8-byte load and a 16-byte store.  q * s is exact in fp32 and representable in bf16 (kv_fp8.hip).
+__global__ void __launch_bounds__(256)
+w_dequant_kernel(const unsigned char* __restrict__ W8, long ldw, const float* __restrict__ ws, u16* __restrict__ out,
+                 int kv, long total) {
+    for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const long n = idx / kv;
+        const int k0 = (int)(idx % kv) * 8;
+        const u32x2 w = Wt<true>::load(W8 + n * ldw + k0);
+        const float s = ws[n];
+        u16x8 o;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) o[e] = f2bf(Wt<true>::f(w, e) * s);
+        *reinterpret_cast<u16x8*>(out + n * (long)kv * 8 + k0) = o;
+    }
+}
+
 }  // namespace gv
 }  // namespace bpe
 
@@ -379,20 +459,20 @@ bool gemv_ok(int M, int K) {
     return gemv_lds_bytes(M, K) <= 160 * 1024 || mfma_fits(M, K);
 }
 
-template <int MM, int EPI, bool RAG>
+template <int MM, int EPI, bool RAG, bool W8>
 static void launch_mm(const GemvArgs& a, int grid, size_t lds, hipStream_t s) {
     if (lds > 64 * 1024)
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_kernel<MM, EPI, RAG>),
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_kernel<MM, EPI, RAG, W8>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    gemv_kernel<MM, EPI, RAG><<<grid, 256, lds, s>>>(a);
+    gemv_kernel<MM, EPI, RAG, W8><<<grid, 256, lds, s>>>(a);
 }
 
-template <int EPI, bool RAG = false>
+template <int EPI, bool RAG, bool W8>
 static void launch_epi(const GemvArgs& a, int grid, size_t lds, hipStream_t s) {
-    if (a.M <= 1) launch_mm<1, EPI, RAG>(a, grid, lds, s);
-    else if (a.M <= 2) launch_mm<2, EPI, RAG>(a, grid, lds, s);
-    else if (a.M <= 4) launch_mm<4, EPI, RAG>(a, grid, lds, s);
-    else launch_mm<8, EPI, RAG>(a, grid, lds, s);
+    if (a.M <= 1) launch_mm<1, EPI, RAG, W8>(a, grid, lds, s);
+    else if (a.M <= 2) launch_mm<2, EPI, RAG, W8>(a, grid, lds, s);
+    else if (a.M <= 4) launch_mm<4, EPI, RAG, W8>(a, grid, lds, s);
+    else launch_mm<8, EPI, RAG, W8>(a, grid, lds, s);
 }
 
 // decode rows from which the MFMA variant runs (BPE_GEMV_MFMA_MIN_M, default 2)
@@ -404,26 +484,40 @@ static int mfma_min_m() {
     return v;
 }
 
-template <int EPI, bool RAG = false>
+template <int EPI, bool RAG, bool W8>
 static void launch_mfma(const GemvArgs& a, int grid, hipStream_t s) {
     const size_t lds = gemv_mfma_lds_bytes(a.M, a.K);
     if (lds > 64 * 1024)
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_mfma_kernel<EPI, RAG>),
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_mfma_kernel<EPI, RAG, W8>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    gemv_mfma_kernel<EPI, RAG><<<grid, 256, lds, s>>>(a);
+    gemv_mfma_kernel<EPI, RAG, W8><<<grid, 256, lds, s>>>(a);
 }
 
-void launch_gemv(const GemvArgs& a, int epi, hipStream_t s) {
+template <bool W8>
+static void launch_w(const GemvArgs& a, int epi, hipStream_t s) {
     if ((a.M >= mfma_min_m() || a.M > 8 || gemv_lds_bytes(a.M, a.K) > 160 * 1024) && mfma_fits(a.M, a.K)) {
-        if (epi == 1) launch_mfma<1>(a, (a.N / 2 + 7) / 8, s);
-        else if (epi == 2 && a.pos_stride != 0) launch_mfma<2, true>(a, (a.N + 15) / 16, s);
-        else if (epi == 2) launch_mfma<2>(a, (a.N + 15) / 16, s);
-        else launch_mfma<0>(a, (a.N + 15) / 16, s);
+        if (epi == 1) launch_mfma<1, false, W8>(a, (a.N / 2 + 7) / 8, s);
+        else if (epi == 2 && a.pos_stride != 0) launch_mfma<2, true, W8>(a, (a.N + 15) / 16, s);
+        else if (epi == 2) launch_mfma<2, false, W8>(a, (a.N + 15) / 16, s);
+        else launch_mfma<0, false, W8>(a, (a.N + 15) / 16, s);
         return;
     }
     const size_t lds = gemv_lds_bytes(a.M, a.K);
-    if (epi == 1) launch_epi<1>(a, (a.N / 2 + 7) / 8, lds, s);
-    else if (epi == 2 && a.pos_stride != 0) launch_epi<2, true>(a, (a.N + 15) / 16, lds, s);
-    else if (epi == 2) launch_epi<2>(a, (a.N + 15) / 16, lds, s);
-    else launch_epi<0>(a, (a.N + 15) / 16, lds, s);
+    if (epi == 1) launch_epi<1, false, W8>(a, (a.N / 2 + 7) / 8, lds, s);
+    else if (epi == 2 && a.pos_stride != 0) launch_epi<2, true, W8>(a, (a.N + 15) / 16, lds, s);
+    else if (epi == 2) launch_epi<2, false, W8>(a, (a.N + 15) / 16, lds, s);
+    else launch_epi<0, false, W8>(a, (a.N + 15) / 16, lds, s);
+}
+
+void launch_gemv(const GemvArgs& a, int epi, hipStream_t s) {
+    if (a.wscale != nullptr) launch_w<true>(a, epi, s);
+    else launch_w<false>(a, epi, s);
+}
+
+void launch_w_dequant(const void* w8, long ldw, const float* ws, void* out, long N, int K, hipStream_t s) {
+    const long total = N * (K / 8);
+    if (total <= 0) return;
+    const long want = (total + 255) / 256;
+    const int grid = (int)(want < 8192 ? want : 8192);
+    w_dequant_kernel<<<grid, 256, 0, s>>>((const unsigned char*)w8, ldw, ws, (u16*)out, K / 8, total);
 }

@@ -177,8 +177,9 @@ struct GemvArgs {
     const __bf16* ln;  // optional RMSNorm weight [K]
     float eps;
     __bf16* xsum;      // optional: x + xd written here [M][K] (workgroup 0)
-    const __bf16* W;   // weight [N][K] (row stride ldw)
+    const __bf16* W;   // weight [N][K] (row stride ldw); with wscale: e4m3 bytes (row stride ldw bytes, % 8 == 0)
     long ldw;
+    const float* wscale;  // optional: fp8 weights -- one power-of-two scale per row [N] (nullptr: bf16 weights)
     int N, K, M;
     __bf16* y;         // output [M][N] (epi 1: [M][N/2]; epi 2: q part [M][H*D]), row stride ldy
     long ldy;
@@ -195,6 +196,8 @@ struct GemvArgs {
 size_t gemv_lds_bytes(int M, int K);
 bool gemv_ok(int M, int K);
 void launch_gemv(const GemvArgs& a, int epi, hipStream_t s);
+// e4m3 weight rows [N][K] (row stride ldw bytes, K % 8 == 0) and their scales [N] -> contiguous bf16 [N][K]
+void launch_w_dequant(const void* w8, long ldw, const float* ws, void* out, long N, int K, hipStream_t s);
 
 // sample.hip (token sampling, one workgroup per logits row [B][V], row stride V).  Either `u` (given uniforms [B])
 // or `rng` (device (seed, count): Philox in the kernel) is set; neither = u 0.5.  `res` [B] takes the tokens

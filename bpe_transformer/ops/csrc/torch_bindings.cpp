@@ -1155,24 +1155,41 @@ void kv_dequant(const at::Tensor& k8, const at::Tensor& v8, const at::Tensor& ks
                       cur_stream());
 }
 
-// Skinny-GEMM prologue / shape checks shared by decode_gemv and decode_qkv; returns the residual-sum output
-at::Tensor gemv_setup(GemvArgs& a, const at::Tensor& x, const c10::optional<at::Tensor>& xd,
-                      const c10::optional<at::Tensor>& ln, double eps, const at::Tensor& w) {
-    check_cuda(x, "x");
-    TORCH_CHECK(x.scalar_type() == at::kBFloat16 && w.scalar_type() == at::kBFloat16, "decode gemv: bf16 required");
-    TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1 && x.stride(0) % 8 == 0, "decode gemv: x must be [M, K] row-major");
-    TORCH_CHECK(w.dim() == 2 && w.stride(1) == 1 && w.stride(0) % 8 == 0 && w.size(1) == x.size(1),
-                "decode gemv: weight must be row-major [N, K]");
-    const int M = (int)x.size(0), K = (int)x.size(1);
-    TORCH_CHECK(gemv_ok(M, K), "decode gemv: 1 <= M <= 8 rows (<= 16 with K % 32 == 0) and K % 8 == 0 required");
-    check_aligned(x, "x");
+// The weight of a skinny GEMM into GemvArgs: bf16 [N, K], or with w_scale float8_e4m3fn [N, K] bytes plus one fp32
+// scale per row (either way a row stride that is a multiple of 8 elements and a 16-byte-aligned base)
+void gemv_weight(GemvArgs& a, const at::Tensor& w, const c10::optional<at::Tensor>& w_scale, int64_t K) {
+    check_cuda(w, "w");
+    TORCH_CHECK(w.dim() == 2 && w.stride(1) == 1 && w.stride(0) % 8 == 0 && w.size(1) == K,
+                "decode gemv: weight must be row-major [N, K] with a row stride that is a multiple of 8");
     check_aligned(w, "w");
-    a = GemvArgs{};
-    a.x = (const __bf16*)x.data_ptr();
-    a.ldx = x.stride(0);
     a.W = (const __bf16*)w.data_ptr();
     a.ldw = w.stride(0);
     a.N = (int)w.size(0);
+    if (w_scale.has_value() && w_scale->defined()) {
+        check_cuda(*w_scale, "w_scale");
+        TORCH_CHECK(w.scalar_type() == at::kFloat8_e4m3fn, "decode gemv: with w_scale the weight must be float8_e4m3fn");
+        TORCH_CHECK(w_scale->scalar_type() == at::kFloat && w_scale->dim() == 1 && w_scale->is_contiguous() &&
+                        w_scale->size(0) == w.size(0), "decode gemv: w_scale must be a contiguous fp32 [N] tensor");
+        a.wscale = w_scale->data_ptr<float>();
+    } else {
+        TORCH_CHECK(w.scalar_type() == at::kBFloat16, "decode gemv: bf16 required");
+    }
+}
+
+// Skinny-GEMM prologue / shape checks shared by decode_gemv and decode_qkv; returns the residual-sum output
+at::Tensor gemv_setup(GemvArgs& a, const at::Tensor& x, const c10::optional<at::Tensor>& xd,
+                      const c10::optional<at::Tensor>& ln, double eps, const at::Tensor& w,
+                      const c10::optional<at::Tensor>& w_scale) {
+    check_cuda(x, "x");
+    TORCH_CHECK(x.scalar_type() == at::kBFloat16, "decode gemv: bf16 required");
+    TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1 && x.stride(0) % 8 == 0, "decode gemv: x must be [M, K] row-major");
+    const int M = (int)x.size(0), K = (int)x.size(1);
+    TORCH_CHECK(gemv_ok(M, K), "decode gemv: 1 <= M <= 8 rows (<= 16 with K % 32 == 0) and K % 8 == 0 required");
+    check_aligned(x, "x");
+    a = GemvArgs{};
+    gemv_weight(a, w, w_scale, K);
+    a.x = (const __bf16*)x.data_ptr();
+    a.ldx = x.stride(0);
     a.K = K;
     a.M = M;
     a.eps = (float)eps;
@@ -1196,10 +1213,10 @@ at::Tensor gemv_setup(GemvArgs& a, const at::Tensor& x, const c10::optional<at::
 // y = RMSNorm(x (+ xd)) W^T (epi 0) or SwiGLU over [W1; W3] (epi 1); returns (y, x + xd or an empty tensor)
 std::tuple<at::Tensor, at::Tensor> decode_gemv(const at::Tensor& x, const c10::optional<at::Tensor>& xd,
                                                const c10::optional<at::Tensor>& ln, double eps, const at::Tensor& w,
-                                               int64_t epi) {
+                                               int64_t epi, const c10::optional<at::Tensor>& w_scale) {
     TORCH_CHECK(epi == 0 || epi == 1, "decode_gemv: epi must be 0 (plain) or 1 (SwiGLU)");
     GemvArgs a;
-    auto xsum = gemv_setup(a, x, xd, ln, eps, w);
+    auto xsum = gemv_setup(a, x, xd, ln, eps, w, w_scale);
     TORCH_CHECK(epi == 0 || a.N % 2 == 0, "decode_gemv: SwiGLU needs an even number of rows");
     DevGuard g(x.device());
     auto y = at::empty({(int64_t)a.M, epi == 1 ? a.N / 2 : a.N}, x.options());
@@ -1210,27 +1227,22 @@ std::tuple<at::Tensor, at::Tensor> decode_gemv(const at::Tensor& x, const c10::o
 }
 
 // output projection of the decode attention straight from its split partials: y = combine(part) W^T
-at::Tensor decode_attn_proj(const at::Tensor& part, const at::Tensor& w) {
+at::Tensor decode_attn_proj(const at::Tensor& part, const at::Tensor& w, const c10::optional<at::Tensor>& w_scale) {
     check_cuda(part, "part");
     TORCH_CHECK(part.scalar_type() == at::kFloat && part.dim() == 4 && part.is_contiguous(),
                 "decode_attn_proj: part must be the fp32 [B, H, nsplit, D + 2] partials of decode_attn");
     const int64_t B = part.size(0), H = part.size(1), ns = part.size(2), D = part.size(3) - 2;
-    TORCH_CHECK(w.scalar_type() == at::kBFloat16 && w.dim() == 2 && w.stride(1) == 1 && w.stride(0) % 8 == 0 &&
-                    w.size(1) == H * D, "decode_attn_proj: weight must be row-major bf16 [N, H*D]");
     TORCH_CHECK(D % 8 == 0 && gemv_ok((int)B, (int)(H * D)), "decode_attn_proj: 1 <= B <= 16 and D % 8 == 0");
-    check_aligned(w, "w");
-    DevGuard g(part.device());
     GemvArgs a{};
+    gemv_weight(a, w, w_scale, H * D);
+    DevGuard g(part.device());
     a.part = part.data_ptr<float>();
     a.nsplit = (int)ns;
     a.H = (int)H;
     a.D = (int)D;
-    a.W = (const __bf16*)w.data_ptr();
-    a.ldw = w.stride(0);
-    a.N = (int)w.size(0);
     a.K = (int)(H * D);
     a.M = (int)B;
-    auto y = at::empty({B, a.N}, w.options());
+    auto y = at::empty({B, a.N}, part.options().dtype(at::kBFloat16));
     a.y = (__bf16*)y.data_ptr();
     a.ldy = y.stride(0);
     launch_gemv(a, 0, cur_stream());
@@ -1241,9 +1253,10 @@ at::Tensor decode_attn_proj(const at::Tensor& part, const at::Tensor& w) {
 std::tuple<at::Tensor, at::Tensor> decode_qkv(const at::Tensor& x, const c10::optional<at::Tensor>& xd,
                                               const c10::optional<at::Tensor>& ln, double eps, const at::Tensor& w,
                                               at::Tensor kc, at::Tensor vc, const at::Tensor& cos,
-                                              const at::Tensor& sin, const at::Tensor& pos, int64_t H, bool use_rope) {
+                                              const at::Tensor& sin, const at::Tensor& pos, int64_t H, bool use_rope,
+                                              const c10::optional<at::Tensor>& w_scale) {
     GemvArgs a;
-    auto xsum = gemv_setup(a, x, xd, ln, eps, w);
+    auto xsum = gemv_setup(a, x, xd, ln, eps, w, w_scale);
     const int64_t B = a.M, Hkv = kc.size(1), Lmax = kc.size(2), D = kc.size(3);
     check_cache(kc, B, Hkv, "k_cache");
     check_cache(vc, B, Hkv, "v_cache");
@@ -1270,6 +1283,26 @@ std::tuple<at::Tensor, at::Tensor> decode_qkv(const at::Tensor& x, const c10::op
     a.vc = (__bf16*)vc.data_ptr();
     launch_gemv(a, 2, cur_stream());
     return {q, xsum};
+}
+
+// e4m3 weight rows [N, K] (row stride a multiple of 8 bytes) and their scales [N] -> the caller's contiguous bf16
+// [N, K]: what the wide steps of an fp8-weight session hand to the library GEMMs
+void w_dequant(const at::Tensor& w8, const at::Tensor& w_scale, at::Tensor out) {
+    check_cuda(w8, "w8");
+    check_cuda(w_scale, "w_scale");
+    check_cuda(out, "out");
+    TORCH_CHECK(w8.scalar_type() == at::kFloat8_e4m3fn && w8.dim() == 2 && w8.stride(1) == 1 && w8.stride(0) % 8 == 0 &&
+                    w8.size(1) % 8 == 0, "w_dequant: w8 must be row-major float8_e4m3fn [N, K], K and the row stride "
+                "multiples of 8");
+    TORCH_CHECK(w_scale.scalar_type() == at::kFloat && w_scale.dim() == 1 && w_scale.is_contiguous() &&
+                    w_scale.size(0) == w8.size(0), "w_dequant: w_scale must be a contiguous fp32 [N] tensor");
+    TORCH_CHECK(out.scalar_type() == at::kBFloat16 && out.is_contiguous() && out.sizes() == w8.sizes(),
+                "w_dequant: out must be a contiguous bf16 [N, K] tensor");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(w8.data_ptr()) % 8 == 0, "w_dequant: w8 must be 8-byte aligned");
+    check_aligned(out, "out");
+    DevGuard g(w8.device());
+    launch_w_dequant(w8.data_ptr(), w8.stride(0), w_scale.data_ptr<float>(), out.data_ptr(), w8.size(0),
+                     (int)w8.size(1), cur_stream());
 }
 
 // ---------------------------------------------------------------- token sampling (sample.hip)
@@ -1448,14 +1481,17 @@ TORCH_LIBRARY(bpe_hip, m) {
     m.def("spec_verify_step(Tensor target_logits, Tensor? draft_logits, float temperature, Tensor rng, "
           "Tensor(a!) win, Tensor(b!) ids, Tensor(c!) out, Tensor(d!) n_out, Tensor base, Tensor(e!) pos_t, "
           "Tensor(f!) pos_d, Tensor(g!) step_t, Tensor(h!) step_d, Tensor(i!) done, int eos) -> ()");
-    m.def("decode_gemv(Tensor x, Tensor? xd, Tensor? ln, float eps, Tensor w, int epi) -> (Tensor, Tensor)");
+    m.def("decode_gemv(Tensor x, Tensor? xd, Tensor? ln, float eps, Tensor w, int epi, Tensor? w_scale=None) -> "
+          "(Tensor, Tensor)");
     m.def("decode_qkv(Tensor x, Tensor? xd, Tensor? ln, float eps, Tensor w, Tensor(a!) k_cache, "
-          "Tensor(b!) v_cache, Tensor cos, Tensor sin, Tensor pos, int H, bool rope) -> (Tensor, Tensor)");
+          "Tensor(b!) v_cache, Tensor cos, Tensor sin, Tensor pos, int H, bool rope, Tensor? w_scale=None) -> "
+          "(Tensor, Tensor)");
     m.def("kv_append(Tensor qkv, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor cos, Tensor sin, Tensor pos, int B, "
           "int T, int H, bool rope) -> Tensor");
     m.def("decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor pos, int H, float scale, "
           "bool combine=True, int T=1) -> Tensor");
-    m.def("decode_attn_proj(Tensor part, Tensor w) -> Tensor");
+    m.def("decode_attn_proj(Tensor part, Tensor w, Tensor? w_scale=None) -> Tensor");
+    m.def("w_dequant(Tensor w8, Tensor w_scale, Tensor(a!) out) -> ()");
     m.def("kv_append_fp8(Tensor qkv, Tensor(a!) k8, Tensor(b!) v8, Tensor(c!) k_scale, Tensor(d!) v_scale, Tensor cos, "
           "Tensor sin, Tensor pos, int B, int T, int H, bool use_rope) -> Tensor");
     m.def("decode_attn_fp8(Tensor q, Tensor k8, Tensor v8, Tensor k_scale, Tensor v_scale, Tensor pos, int H, "
@@ -1575,6 +1611,7 @@ TORCH_LIBRARY_IMPL(bpe_hip, CUDA, m) {
     m.impl("decode_gemv", &decode_gemv);
     m.impl("decode_qkv", &decode_qkv);
     m.impl("decode_attn_proj", &decode_attn_proj);
+    m.impl("w_dequant", &w_dequant);
     m.impl("kv_append_fp8", &kv_append_fp8);
     m.impl("decode_attn_fp8", &decode_attn_fp8);
     m.impl("kv_dequant", &kv_dequant);

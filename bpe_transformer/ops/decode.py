@@ -47,6 +47,15 @@ dequantised values, and that is how its consumers are defined:
   followed by :func:`prefill_attention`, in one launch and with no scratch;
 * :func:`kv_dequant` writes the valid rows of a K / V pair as bf16 into a
   caller's pair -- a utility, and the oracle of that equality.
+
+**fp8 weights**.  The same row format applied to a projection matrix ``w [N,
+K]``, one row per output feature: :func:`weight_quantize` gives ``w8
+float8_e4m3fn [N, K]`` and ``w_scale fp32 [N]``, :func:`weight_dequantize` the
+bf16 matrix they stand for, exactly.  :func:`decode_gemv`, :func:`decode_qkv`
+and :func:`decode_attn_proj` take the pair (``w=w8, w_scale=...``) and stream
+half the weight bytes; each is, bit for bit on the GPU, the same call on
+``weight_dequantize(w8, w_scale)``.  :func:`w_dequant` writes that matrix into
+a caller's bf16 buffer (for a library GEMM).
 """
 
 from __future__ import annotations
@@ -188,11 +197,14 @@ def decode_partials_reference(q, k_cache, v_cache, pos, n_heads, scale=None, chu
     return out
 
 
-def decode_attn_proj(part: Tensor, w: Tensor) -> Tensor:
+def decode_attn_proj(part: Tensor, w: Tensor, w_scale: Tensor | None = None) -> Tensor:
     """Output projection of the decode attention from its partials: ``combine(part) @ w.T`` (bf16 rounding of
-    the combined rows as in the unfused path)."""
+    the combined rows as in the unfused path).  With ``w_scale``, ``w`` is the e4m3 matrix of
+    :func:`weight_quantize`."""
     if part.is_cuda:
-        return ops().decode_attn_proj(part, w)
+        return ops().decode_attn_proj(part, w) if w_scale is None else ops().decode_attn_proj(part, w, w_scale)
+    if w_scale is not None:
+        w = weight_dequantize(w, w_scale)
     B, H, _, D2 = part.shape
     D = D2 - 2
     m = part[..., D]
@@ -206,18 +218,27 @@ def decode_attn_proj(part: Tensor, w: Tensor) -> Tensor:
 
 
 def decode_gemv(x: Tensor, w: Tensor, xd: Tensor | None = None, ln: Tensor | None = None, eps: float = 1e-5,
-                swiglu: bool = False) -> tuple[Tensor, Tensor | None]:
+                swiglu: bool = False, w_scale: Tensor | None = None) -> tuple[Tensor, Tensor | None]:
     """Skinny projection of ``M <= 8`` decode rows (``csrc/decode_gemv.hip``): ``h = RMSNorm(x + xd) * ln``
     (each part optional), then ``y = h W^T`` or, with ``swiglu``, ``silu(h W1^T) * (h W3^T)`` for
-    ``w = [W1; W3]``.  Returns ``(y, x + xd)`` (the second is ``None`` without ``xd``)."""
+    ``w = [W1; W3]``.  Returns ``(y, x + xd)`` (the second is ``None`` without ``xd``).  With ``w_scale``, ``w`` is
+    the e4m3 matrix of :func:`weight_quantize`."""
     if x.is_cuda:
-        y, s = ops().decode_gemv(x, xd, ln, eps, w, 1 if swiglu else 0)
+        y, s = ops().decode_gemv(x, xd, ln, eps, w, 1 if swiglu else 0, *_ws(w_scale))
         return y, (s if xd is not None else None)
-    return decode_gemv_reference(x, w, xd, ln, eps, swiglu)
+    return decode_gemv_reference(x, w, xd, ln, eps, swiglu, w_scale)
 
 
-def decode_gemv_reference(x, w, xd=None, ln=None, eps=1e-5, swiglu=False):
-    """fp32 oracle with the kernel's rounding points (bf16 residual sum, bf16 GEMM outputs before SwiGLU)."""
+def _ws(w_scale: Tensor | None) -> tuple:
+    """The trailing ``w_scale`` argument of a HIP op: absent for bf16 weights (the call is then what it always was)."""
+    return () if w_scale is None else (w_scale,)
+
+
+def decode_gemv_reference(x, w, xd=None, ln=None, eps=1e-5, swiglu=False, w_scale=None):
+    """fp32 oracle with the kernel's rounding points (bf16 residual sum, bf16 GEMM outputs before SwiGLU); fp8
+    weights are dequantised first."""
+    if w_scale is not None:
+        w = weight_dequantize(w, w_scale, x.dtype)
     s = (x.float() + xd.float()).to(x.dtype) if xd is not None else x
     h = s.float()
     if ln is not None:
@@ -231,16 +252,16 @@ def decode_gemv_reference(x, w, xd=None, ln=None, eps=1e-5, swiglu=False):
 
 def decode_qkv(x: Tensor, w: Tensor, k_cache: Tensor, v_cache: Tensor, cos: Tensor | None, sin: Tensor | None,
                pos: Tensor, n_heads: int, xd: Tensor | None = None, ln: Tensor | None = None,
-               eps: float = 1e-5) -> tuple[Tensor, Tensor | None]:
+               eps: float = 1e-5, w_scale: Tensor | None = None) -> tuple[Tensor, Tensor | None]:
     """Fused decode QKV: ``qkv = RMSNorm(x + xd) W^T`` for one new token per sequence, RoPE at the device-side
     position, K / V written into the caches; returns ``(q [M, H*D], x + xd)``.  With ``pos [M]`` row ``m`` is
     sequence ``m`` at ``pos[m]``; a row at ``Lmax`` or past it writes nothing, and its query row is unspecified
-    (as for :func:`kv_append`)."""
+    (as for :func:`kv_append`).  With ``w_scale``, ``w`` is the e4m3 matrix of :func:`weight_quantize`."""
     if x.is_cuda:
         c, sn, use_rope = _rope_args(x, cos, sin)
-        q, s = ops().decode_qkv(x, xd, ln, eps, w, k_cache, v_cache, c, sn, pos, n_heads, use_rope)
+        q, s = ops().decode_qkv(x, xd, ln, eps, w, k_cache, v_cache, c, sn, pos, n_heads, use_rope, *_ws(w_scale))
         return q, (s if xd is not None else None)
-    qkv, s = decode_gemv_reference(x, w, xd, ln, eps)
+    qkv, s = decode_gemv_reference(x, w, xd, ln, eps, w_scale=w_scale)
     return kv_append_reference(qkv, k_cache, v_cache, cos, sin, pos, x.shape[0], 1, n_heads), s
 
 
@@ -347,3 +368,26 @@ def kv_dequant(k8: Tensor, v8: Tensor, k_scale: Tensor, v_scale: Tensor, pos: Te
         n = max(0, min(p0 + n_new, Lmax))
         k_out[b, :, :n] = kv_dequantize_reference(k8[b, :, :n], k_scale[b, :, :n], k_out.dtype)
         v_out[b, :, :n] = kv_dequantize_reference(v8[b, :, :n], v_scale[b, :, :n], v_out.dtype)
+
+
+# ------------------------------------------------------------------ fp8 weights (csrc/decode_gemv.hip)
+def weight_quantize(w: Tensor) -> tuple[Tensor, Tensor]:
+    """``w [N, K]`` -> (``w8 float8_e4m3fn [N, K]``, ``w_scale fp32 [N]``): :func:`kv_quantize_reference` on the rows,
+    one row per output feature -- the same scale rule, corner cases and clamp.  Plain torch on ``w``'s device: it
+    runs once per session."""
+    assert w.dim() == 2, "weight_quantize: a [N, K] matrix"
+    return kv_quantize_reference(w)
+
+
+def weight_dequantize(w8: Tensor, w_scale: Tensor, dtype: torch.dtype = torch.bfloat16) -> Tensor:
+    """The matrix an fp8 weight pair stands for: ``w8 * w_scale`` per row (exact in fp32, representable in bf16)."""
+    return kv_dequantize_reference(w8, w_scale, dtype)
+
+
+def w_dequant(w8: Tensor, w_scale: Tensor, out: Tensor) -> Tensor:
+    """:func:`weight_dequantize` into the caller's contiguous bf16 ``out [N, K]`` (``K % 8 == 0``); returns it."""
+    if w8.is_cuda:
+        ops().w_dequant(w8, w_scale, out)
+    else:
+        out.copy_(weight_dequantize(w8, w_scale, out.dtype))
+    return out

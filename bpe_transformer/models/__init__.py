@@ -12,7 +12,7 @@ from .layers import (
     SwiGLU,
     TransformerBlock,
 )
-from .generation import DecodeSession, KVCache, SpeculativeSession
+from .generation import DecodeSession, KVCache, PromptLookupSession, SpeculativeSession
 from .transformer import TransformerLM
 
 __all__ = [
@@ -24,6 +24,7 @@ __all__ = [
     "Linear",
     "ModelConfig",
     "MultiHeadSelfAttention",
+    "PromptLookupSession",
     "RMSNorm",
     "RotaryPositionalEmbedding",
     "SpeculativeSession",

@@ -97,6 +97,17 @@ sequence (``cache.pos [B]``, stride 1, host mirror ``cache.lengths``).  So
 Cache rows at and past ``pos[b]`` may hold pad-token (or inactive-step) values.
 They are never visible -- every read of sequence ``b`` stops at ``pos[b]`` plus
 its own new tokens -- and are overwritten as the sequence grows.
+
+**Speculative decoding** is one round engine with two proposers, each round
+captured into one graph with no host sync inside: :class:`SpeculativeSession`
+drafts with a second model (its own ragged session and cache), and
+:class:`PromptLookupSession` drafts from the sequence's own history
+(``lookup_draft``: the continuation of the most recent earlier occurrence of
+the last few tokens), which needs no second model, cache or decode step.
+Either way the target scores the ``K + 1`` window in one pass and
+``spec_verify_step`` keeps the drafts that stand; greedy output is the
+target's own, sampled output is distributed as the target's.  Neither
+composes with the fp8 cache or fp8 weights yet.
 """
 
 from __future__ import annotations
@@ -1002,6 +1013,9 @@ class SpeculativeSession:
     first token is the target's own draw at counter ``(0, row, stream 2)``, round ``r`` starts at ``c = 1 + r (K +
     1)`` and draws draft ``j`` at ``(c + j - 1, row, stream 0)``, its accept test at ``(c + j - 1, row, stream 1)``
     and the final token at ``(c, row, stream 2)``.
+
+    The proposer is the two hooks ``_propose`` (step 2 and 3) and ``_prefill_proposer``;
+    :class:`PromptLookupSession` replaces them with the n-gram lookup and shares everything else.
     """
 
     def __init__(self, target, draft, batch: int, num_draft_tokens: int = 4, max_len: int | None = None,
@@ -1022,10 +1036,16 @@ class SpeculativeSession:
                              "runs on the bf16 cache only")
         self.target = DecodeSession(target, batch, self.max_len, use_graph, ragged=True)
         self.draft = DecodeSession(draft, batch, self.max_len, use_graph, ragged=True)
-        self.device = dev = self.target.device
-        self.fast = self.target.fast and self.draft.fast
+        self._setup(use_graph)
+
+    def _setup(self, use_graph: bool) -> None:
+        """The round's state, for either proposer: ``self.draft`` is the draft's session, or ``None`` when the
+        drafts come from the lookup (``pos_d`` / ``step_d`` / ``ids`` are then scratch for ``spec_verify_step``)."""
+        t, d, K, batch = self.target, self.draft, self.K, self.batch
+        self._sessions = [(t, "step_t")] + ([(d, "step_d")] if d is not None else [])
+        self.device = dev = t.device
+        self.fast = all(s.fast for s, _ in self._sessions)
         self.use_graph = use_graph and self.fast
-        t, d = self.target, self.draft
         if self.fast:  # the target's window must be one pass over the layers (no position moves inside the round)
             plan = _append_plan(K + 1, t.H // t.Hkv, True)
             assert len(plan) == 1, plan
@@ -1040,7 +1060,8 @@ class SpeculativeSession:
             "rngs": torch.zeros(K + 1, 2, dtype=torch.long, device=dev),
             # a session off the fast path has no static step: the round's own
             "step_t": t._step if t._step is not None else torch.ones(batch, **i32),
-            "step_d": d._step if d._step is not None else torch.ones(batch, **i32),
+            "step_d": d._step if d is not None and d._step is not None else torch.ones(batch, **i32),
+            "pos_d": d.cache.pos if d is not None else torch.zeros(batch, **i32),
         }
         self._graph, self._key = None, None
 
@@ -1062,11 +1083,11 @@ class SpeculativeSession:
             return t._forward_fast(st["win"], self._win_kind, all_logits=True, advance=False).view(B, K + 1, -1)
         return t._forward_reference(st["win"], [0] * B, list(range(B)), all_logits=True)  # (0: no advance)
 
-    def _round(self, temperature: float, eos: int, out: Tensor) -> None:
+    def _propose(self, temperature: float, out: Tensor) -> list[Tensor]:
+        """Write the K drafts into ``win[:, 1:]``; returns the draft logits of a sampling round (else nothing)."""
         from ..ops import sampling
 
         st, K = self._st, self.K
-        st["base"].copy_(self.target.cache.pos)
         kept = []
         for j in range(1, K + 1):
             logits = self._decode_draft()
@@ -1075,15 +1096,26 @@ class SpeculativeSession:
             if temperature > 0:
                 kept.append(logits)
         self._decode_draft()
+        return kept
+
+    def _prefill_proposer(self, ids: Tensor, n: list[int]) -> None:
+        self.draft.prefill(ids, n)
+
+    def _round(self, temperature: float, eos: int, out: Tensor) -> None:
+        from ..ops import sampling
+
+        st, K = self._st, self.K
+        st["base"].copy_(self.target.cache.pos)
+        kept = self._propose(temperature, out)
         tl = self._score_window()
         sl = torch.stack(kept, 1).to(tl.dtype) if kept else None  # the one gathering launch of a sampling round
         sampling.spec_verify_step(tl, sl, temperature, st["rngs"][0], st["win"], st["ids"], out, st["n_out"],
-                                  st["base"], self.target.cache.pos, self.draft.cache.pos, st["step_t"], st["step_d"],
-                                  st["done"], eos)
+                                  st["base"], self.target.cache.pos, st["pos_d"], st["step_t"], st["step_d"],
+                                  st["done"], eos, point_mass=self.draft is None)
         st["rngs"][:, 1].add_(K + 1)
 
     def _sync_mirrors(self) -> None:
-        for s in (self.target, self.draft):
+        for s, _ in self._sessions:
             s.cache._len[:] = [int(x) for x in s.cache.pos.tolist()]
 
     def _capture(self, key) -> None:
@@ -1105,14 +1137,14 @@ class SpeculativeSession:
 
     def _init_state(self, seed: int) -> None:
         st, K = self._st, self.K
-        self.target.reset()
-        self.draft.reset()
         st["win"].zero_()
         st["ids"].zero_()
         st["out"].fill_(-1)
         for k in ("n_out", "base", "done"):
             st[k].zero_()
-        for k, s in (("step_t", self.target), ("step_d", self.draft)):
+        st["step_d"].fill_(1)
+        for s, k in self._sessions:
+            s.reset()
             st[k].fill_(1)
             s._step_host = [1] * self.batch
         st["rngs"].copy_(torch.tensor([[seed, 1 + j] for j in range(K + 1)], dtype=torch.long))
@@ -1127,7 +1159,7 @@ class SpeculativeSession:
         rounds.  ``prompt + max_new_tokens + num_draft_tokens + 1 <= max_len`` is checked once, up front."""
         from ..ops import sampling
 
-        t, d, st, K, B = self.target, self.draft, self._st, self.K, self.batch
+        t, st, K, B = self.target, self._st, self.K, self.batch
         as_list = isinstance(prompt, (list, tuple))
         if as_list:
             prompts, n, ids = t._pad_prompts(prompt)
@@ -1155,7 +1187,7 @@ class SpeculativeSession:
         out = st["out"][:, :max_new_tokens]
         # the first token is the target's own: prefill both, draw at Philox counter (0, row, stream 2)
         logits = t.prefill(ids, n)
-        d.prefill(ids, n)
+        self._prefill_proposer(ids, n)
         first = sampling.sample_logits(logits, temperature, 0, 1.0, sampling.philox_uniform(seed, 0, B, stream=2))
         first = first.to(self.device)
         out[:, 0] = first
@@ -1166,7 +1198,8 @@ class SpeculativeSession:
         if key[1] >= 0:
             fin |= first == key[1]
         st["done"].copy_(fin)
-        for k, s in (("step_t", t), ("step_d", d)):
+        st["step_d"].copy_(~fin)
+        for s, k in self._sessions:
             st[k].copy_(~fin)
             s._step_host = None  # the device owns the steps until the end
         rounds = 0
@@ -1181,11 +1214,11 @@ class SpeculativeSession:
             rounds += 1
         made = [int(x) for x in st["n_out"].tolist()]
         res = out.cpu()
-        for s, k in ((t, "step_t"), (d, "step_d")):
+        for s, k in self._sessions:
             s._step_host = [int(x) for x in st[k].tolist()]
         if as_list:
             # both caches hold every emitted token but the last; pos[b] already says so on the device
-            for s in (t, d):
+            for s, _ in self._sessions:
                 s.cache._len[:] = [n[b] + made[b] - 1 for b in range(B)]
             return [torch.cat([p, res[b, : made[b]].to(self.device, p.dtype)]) for b, p in enumerate(prompts)]
         # tensor prompt: keep the tokens up to the one at which every row had emitted EOS, as DecodeSession does
@@ -1194,7 +1227,7 @@ class SpeculativeSession:
             hit = res[:, :keep] == eos
             if bool(hit.any(1).all()):
                 keep = min(keep, int(hit.int().argmax(1).max()) + 1)
-        for s in (t, d):
+        for s, _ in self._sessions:
             s.cache.pos.fill_(n[0] + keep - 1)
             s.cache._len[:] = [n[0] + keep - 1] * B
         return torch.cat([ids, res[:, :keep].to(self.device, ids.dtype)], 1)
@@ -1209,3 +1242,64 @@ class SpeculativeSession:
         hit = out.cpu() == eos
         first = [int(h[:m].int().argmax()) if bool(h[:m].any()) else -1 for h, m in zip(hit, made)]
         return min(first) >= 0 and min(made) >= max(first) + 1
+
+
+def _lookup_bounds(prompt_lookup) -> tuple[int, int]:
+    """``prompt_lookup=n_hi`` or ``(n_hi, n_lo)`` -> the checked n-gram bounds ``(n_hi, n_lo)``; an int means
+    ``n_lo = 1``."""
+    n_hi, n_lo = prompt_lookup if isinstance(prompt_lookup, (tuple, list)) else (prompt_lookup, 1)
+    n_hi, n_lo = int(n_hi), int(n_lo)
+    if not 1 <= n_lo <= n_hi:
+        raise ValueError(f"prompt_lookup: n-gram bounds need 1 <= n_lo <= n_hi, got n_hi={n_hi}, n_lo={n_lo}")
+    return n_hi, n_lo
+
+
+class PromptLookupSession(SpeculativeSession):
+    """Speculative decoding without a draft model (prompt lookup / n-gram drafting): every round
+    ``ops.lookup_draft`` finds the most recent earlier occurrence of the last ``n_lo .. n_hi`` tokens in the
+    sequence's own history (prompt + emitted tokens) and proposes what followed it; the target verifies the proposal
+    in one pass, with ``spec_verify_step(point_mass=True)`` (``ops/sampling.py`` states both functions).  Greedy
+    decoding emits exactly the target's tokens, sampling emits tokens distributed as the target's, whatever is
+    proposed.  No second model, no second KV cache, no draft decode steps.
+
+    It is :class:`SpeculativeSession`'s round and ``generate`` with another proposer.  It owns the target's ragged
+    :class:`DecodeSession` only, a static device copy of the padded prompts (``prompt [B, max_len]``, ``n_prompt
+    [B]``, filled per ``generate`` call; columns at and past ``n_prompt[b]`` are never read) and int32 ``[B]``
+    scratch in the place of the draft's ``pos`` / ``step``.  One round, one graph on one stream: ``base = pos``;
+    ``lookup_draft`` writes ``win[:, 1:]``; the target's window pass; ``spec_verify_step``; ``rngs[:, 1] += K + 1``.
+    The Philox counters are the draft-model form's, stream 0 unused.
+    """
+
+    def __init__(self, target, batch: int, num_draft_tokens: int = 4, prompt_lookup=3, max_len: int | None = None,
+                 use_graph: bool = True, kv_dtype: str = "bf16", weight_dtype: str = "bf16"):
+        K = int(num_draft_tokens)
+        if K < 1:
+            raise ValueError("num_draft_tokens must be at least 1")
+        self.n_hi, self.n_lo = _lookup_bounds(prompt_lookup)
+        for name, v in (("kv_dtype", kv_dtype), ("weight_dtype", weight_dtype)):
+            if v != "bf16":  # (left for later, as with a draft model)
+                raise ValueError(f"{name}={v!r} with prompt_lookup is not supported yet: speculative decoding runs "
+                                 "on the bf16 cache and bf16 weights only")
+        self.K = K
+        self.batch = batch
+        self.max_len = max_len or target.context_length
+        if self.max_len > target.context_length:
+            raise ValueError("max_len exceeds the context length of the target")
+        self.target = DecodeSession(target, batch, self.max_len, use_graph, ragged=True)
+        self.draft = None
+        self._setup(use_graph)
+        self._st["prompt"] = torch.zeros(batch, self.max_len, dtype=torch.long, device=self.device)
+        self._st["n_prompt"] = torch.zeros(batch, dtype=torch.int32, device=self.device)
+
+    def _propose(self, temperature: float, out: Tensor) -> list[Tensor]:
+        from ..ops import sampling
+
+        st = self._st
+        sampling.lookup_draft(st["prompt"], st["n_prompt"], out, st["n_out"], st["win"], st["step_t"], st["done"],
+                              self.n_hi, self.n_lo)
+        return []
+
+    def _prefill_proposer(self, ids: Tensor, n: list[int]) -> None:
+        st = self._st
+        st["prompt"][:, : ids.shape[1]] = ids
+        st["n_prompt"].copy_(torch.tensor(n, dtype=torch.int32))

@@ -191,10 +191,13 @@ class TransformerLM(nn.Module):
         return m
 
     def _generate_speculative(self, prompt, max_new_tokens, temperature, top_p, eos_token_id, generator, top_k, seed,
-                              draft_model, num_draft_tokens):
-        from .generation import SpeculativeSession
+                              draft_model, num_draft_tokens, prompt_lookup=None):
+        from .generation import PromptLookupSession, SpeculativeSession
 
         if top_k or (top_p is not None and top_p < 1.0):
+            if draft_model is None:
+                raise ValueError("top_k / top_p cannot be combined with prompt_lookup: speculative verification "
+                                 "needs the unwarped distribution of the target")
             raise ValueError("top_k / top_p cannot be combined with draft_model: speculative verification needs "
                              "the unwarped distributions of both models")
         K = int(num_draft_tokens)
@@ -204,9 +207,12 @@ class TransformerLM(nn.Module):
         ids = list(prompt) if as_list else (prompt.unsqueeze(0) if squeeze else prompt)
         longest = max(int(p.numel()) for p in ids) if as_list else ids.shape[1]
         need = longest + max(max_new_tokens, 0) + K + 1
-        if need > min(self.context_length, draft_model.context_length):
+        if need > min(self.context_length, (self if draft_model is None else draft_model).context_length):
             raise ValueError(f"prompt + max_new_tokens + num_draft_tokens + 1 = {need} exceeds the context length")
-        sess = SpeculativeSession(self, draft_model, len(ids), K, max_len=need)
+        if draft_model is None:
+            sess = PromptLookupSession(self, len(ids), K, prompt_lookup, max_len=need)
+        else:
+            sess = SpeculativeSession(self, draft_model, len(ids), K, max_len=need)
         out = sess.generate(ids, max_new_tokens, temperature, eos_token_id, seed, generator)
         return out[0] if squeeze else out
 
@@ -227,6 +233,7 @@ class TransformerLM(nn.Module):
         num_draft_tokens: int = 4,
         kv_dtype: str = "bf16",
         weight_dtype: str = "bf16",
+        prompt_lookup: "int | tuple[int, int] | None" = None,
     ) -> Tensor:
         """Autoregressive sampling (temperature, top-k, nucleus).  ``prompt``: ``[S]`` or ``[B, S]``.
 
@@ -257,12 +264,31 @@ class TransformerLM(nn.Module):
         (``DecodeSession(..., weight_dtype="fp8")``: about half the weight bytes a decode step streams).  The output
         is that of this call on a model whose projection weights are the dequantised rows.  It needs the KV-cache
         path and is not yet supported together with ``draft_model`` (``ValueError``).
+
+        ``prompt_lookup=n_hi`` (or ``(n_hi, n_lo)``; an int means ``n_lo = 1``) turns on speculative decoding without
+        a draft model (:class:`~bpe_transformer.models.generation.PromptLookupSession`): every round proposes the
+        ``num_draft_tokens`` tokens that followed the most recent earlier occurrence of the last ``n_lo .. n_hi``
+        tokens in the sequence's own prompt and output, and this model verifies them in one pass.  The output
+        guarantees, the implied device sampler and the ``ValueError`` with ``top_k`` / ``top_p``, ``kv_dtype="fp8"``
+        or ``weight_dtype="fp8"`` are those of ``draft_model``; the two cannot be combined (``ValueError``).
         """
         assert sampler in ("host", "device"), "sampler: 'host' or 'device'"
         if kv_dtype not in ("bf16", "fp8"):
             raise ValueError(f"kv_dtype: 'bf16' or 'fp8', got {kv_dtype!r}")
         if weight_dtype not in ("bf16", "fp8"):
             raise ValueError(f"weight_dtype: 'bf16' or 'fp8', got {weight_dtype!r}")
+        if prompt_lookup is not None:
+            from .generation import _lookup_bounds
+
+            if draft_model is not None:
+                raise ValueError("prompt_lookup cannot be combined with draft_model: a round has one proposer")
+            _lookup_bounds(prompt_lookup)
+            for name, v in (("kv_dtype", kv_dtype), ("weight_dtype", weight_dtype)):
+                if v != "bf16":
+                    raise ValueError(f"{name}='fp8' with prompt_lookup is not supported yet: speculative decoding "
+                                     "runs on the bf16 cache and bf16 weights only")
+            return self._generate_speculative(prompt, max_new_tokens, temperature, top_p, eos_token_id, generator,
+                                              top_k, seed, None, num_draft_tokens, prompt_lookup)
         if draft_model is not None:
             if weight_dtype != "bf16":
                 raise ValueError("weight_dtype='fp8' with draft_model is not supported yet: speculative decoding runs "

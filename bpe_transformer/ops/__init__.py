@@ -18,7 +18,7 @@ from .loss import IGNORE_INDEX, cross_entropy, lm_head_cross_entropy
 from .norm import rmsnorm
 from .optim import clip_grad_norm_, fused_adamw_step, grad_norm
 from .rope import apply_rope
-from .sampling import philox_uniform, sample_logits, sample_step, spec_verify, spec_verify_step
+from .sampling import lookup_draft, philox_uniform, sample_logits, sample_step, spec_verify, spec_verify_step
 from .softmax import softmax
 
 __all__ = [
@@ -40,6 +40,7 @@ __all__ = [
     "library_path",
     "lm_head_cross_entropy",
     "load",
+    "lookup_draft",
     "philox_uniform",
     "prefill_attention",
     "rmsnorm",

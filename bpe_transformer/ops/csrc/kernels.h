@@ -236,7 +236,7 @@ void launch_sample(const SampleArgs& a, int dtype, int B, hipStream_t s);
 // a row that emitted `eos` or filled `out` sets done[b] and clears step_t[b], step_d[b].
 struct SpecArgs {
     const void* t;
-    const void* s;  // nullptr: greedy
+    const void* s;  // nullptr: greedy, or point_mass
     int V, K;
     float temperature;  // <= 0: greedy
     const long long* draft;
@@ -260,8 +260,30 @@ struct SpecArgs {
     int* step_d;
     int* done;
     int eos;  // < 0: none
+    int point_mass;  // sampling only: q_i is the point mass at draft i (s is nullptr), as if s were one-hot logits
 };
 void launch_spec_verify(const SpecArgs& a, int dtype, int B, hipStream_t s);
+
+// lookup_draft.hip (prompt-lookup drafts; ops/sampling.py states the function).  One workgroup per sequence.  The
+// history of sequence b is prompt[b][0 .. n_prompt[b]) followed by out[b][0 .. n_out[b]) (int64 token ids that fit
+// int32); the K drafts go to win[b][1 .. K].  A row with done[b] != 0 or step[b] == 0 is left as it is.
+struct LookupArgs {
+    const long long* prompt;
+    long prompt_ld;
+    int prompt_n;  // columns of prompt: n_prompt[b] is clamped to it
+    const int* n_prompt;
+    const long long* out;
+    long out_ld;
+    int out_n;  // columns of out: n_out[b] is clamped to it
+    const int* n_out;
+    long long* win;
+    long win_ld;
+    int K;
+    const int* step;
+    const int* done;
+    int n_hi, n_lo;  // 1 <= n_lo <= n_hi
+};
+void launch_lookup_draft(const LookupArgs& a, int B, hipStream_t s);
 
 size_t fa_fwd_lds_bytes(int D);
 size_t fa_bwd_lds_bytes(int D);

@@ -16,6 +16,11 @@
 // is floor(max(zp_j / Z_p - zq_j / Z_q, 0) * 2^40), a function of integers only; its p row is read in vectors, its
 // q row element by element at the same index (the two rows need not share an alignment).
 //
+// point_mass (prompt-lookup drafts: q_i is the point mass at d[i], there are no draft logits): the q row passes are
+// skipped and zq(d) = Z_q = 2^40, zq elsewhere = 0 stand in the same expressions, which is what one-hot draft logits
+// (0 at d[i], -inf elsewhere) give the code above, bit for bit.  A d outside [0, V) never stands and is never read;
+// the token after it is drawn from p itself.
+//
 // All writes are plain vector stores by thread 0.
 #include "sample_common.h"
 
@@ -37,7 +42,7 @@ __global__ void __launch_bounds__(S_NT) spec_verify_kernel(SpecArgs a) {
     Ctx<T> cp, cq;
     unsigned bk;
     int bi, n = 0, y;
-    if (!(a.temperature > 0.f) || a.s == nullptr) {
+    if (!(a.temperature > 0.f) || (a.s == nullptr && !a.point_mass)) {
         for (n = 0;; ++n) {
             cp.init(a.t, (long)b * (K + 1) + n, V, smem);
             row_argmax(cp, bk, bi);
@@ -54,18 +59,23 @@ __global__ void __launch_bounds__(S_NT) spec_verify_kernel(SpecArgs a) {
             row_argmax(cp, bk, bi);
             cp.xmax = R::key_val(bk);
             Zp = row_total(cp, [&](unsigned raw) -> u64 { return cp.zq(raw); });
-            cq.init(a.s, (long)b * K + n, V, smem);
-            cq.invT = invT;
-            unsigned qk;
-            int qi;
-            row_argmax(cq, qk, qi);
-            cq.xmax = R::key_val(qk);
-            Zq = row_total(cq, [&](unsigned raw) -> u64 { return cq.zq(raw); });
+            if (!a.point_mass) {
+                cq.init(a.s, (long)b * K + n, V, smem);
+                cq.invT = invT;
+                unsigned qk;
+                int qi;
+                row_argmax(cq, qk, qi);
+                cq.xmax = R::key_val(qk);
+                Zq = row_total(cq, [&](unsigned raw) -> u64 { return cq.zq(raw); });
+            } else {
+                Zq = (u64)S_FIX;
+            }
             const long long d = draft[n];
             bool ok = false;
             if (d >= 0 && d < V) {  // (a token outside the vocabulary is never read and never stands)
                 const float ua = a.rng != nullptr ? philox_u(seed, cnt + (u64)n, (unsigned)b, 1u) : a.ua[(long)b * K + n];
-                const double lhs = (double)ua * (double)cq.zq(cq.at((int)d)) * (double)Zp;
+                const u64 zqd = a.point_mass ? (u64)S_FIX : cq.zq(cq.at((int)d));
+                const double lhs = (double)ua * (double)zqd * (double)Zp;
                 const double rhs = (double)cp.zq(cp.at((int)d)) * (double)Zq;
                 ok = lhs < rhs;
             }
@@ -73,7 +83,18 @@ __global__ void __launch_bounds__(S_NT) spec_verify_kernel(SpecArgs a) {
         }
         const float us = a.rng != nullptr ? philox_u(seed, cnt, (unsigned)b, 2u) : a.us[b];
         int i = -1;
-        if (n < K) {  // rejected at position n + 1: the residual of that position (cp, cq, Zp, Zq are its own)
+        if (n < K && a.point_mass) {  // rejected at position n + 1: p with d zeroed (a d outside [0, V): p itself)
+            const long long d = draft[n];
+            const double ip = Zp ? 1.0 / (double)Zp : 0.0, iq = 1.0 / (double)S_FIX;
+            if (d >= 0 && d < V)
+                i = prefix_find(
+                    cp,
+                    [&](unsigned raw, unsigned, int j) -> u64 {
+                        const double r = (double)cp.zq(raw) * ip - (double)(j == (int)d ? (u64)S_FIX : (u64)0) * iq;
+                        return r > 0.0 ? (u64)(r * (double)S_FIX) : 0;
+                    },
+                    [&](u64 M) -> u64 { return draw_target(us, M); });
+        } else if (n < K) {  // rejected at position n + 1: the residual of that position (cp, cq, Zp, Zq are its own)
             const double ip = Zp ? 1.0 / (double)Zp : 0.0, iq = Zq ? 1.0 / (double)Zq : 0.0;
             i = prefix_find(
                 cp,

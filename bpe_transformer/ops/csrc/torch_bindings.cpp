@@ -1378,7 +1378,8 @@ bool spec_i32(const at::Tensor& x, int64_t B) {
     return x.is_cuda() && x.scalar_type() == at::kInt && x.is_contiguous() && x.numel() == B;
 }
 
-SpecArgs spec_setup(const at::Tensor& t, const c10::optional<at::Tensor>& s, double temperature, int64_t K) {
+SpecArgs spec_setup(const at::Tensor& t, const c10::optional<at::Tensor>& s, double temperature, int64_t K,
+                    bool point_mass) {
     check_cuda(t, "target_logits");
     TORCH_CHECK(K >= 1 && spec_dense(t) && t.size(1) == K + 1, "spec_verify: target_logits must be dense [B, K + 1, V]");
     TORCH_CHECK(t.size(2) >= 1 && t.size(2) <= SAMPLE_MAX_V, "spec_verify: 1 <= V <= ", SAMPLE_MAX_V);
@@ -1390,7 +1391,10 @@ SpecArgs spec_setup(const at::Tensor& t, const c10::optional<at::Tensor>& s, dou
     a.K = (int)K;
     a.temperature = (float)temperature;
     a.eos = -1;
-    if (temperature > 0) {
+    if (temperature > 0 && point_mass) {
+        TORCH_CHECK(!s.has_value(), "spec_verify: point-mass drafts have no draft logits");
+        a.point_mass = 1;
+    } else if (temperature > 0) {
         TORCH_CHECK(s.has_value(), "spec_verify: sampling (temperature > 0) needs the draft logits");
         TORCH_CHECK(s->is_cuda() && s->get_device() == t.get_device() && s->scalar_type() == t.scalar_type() &&
                         spec_dense(*s) && s->size(0) == t.size(0) && s->size(1) == K && s->size(2) == t.size(2),
@@ -1404,10 +1408,10 @@ SpecArgs spec_setup(const at::Tensor& t, const c10::optional<at::Tensor>& s, dou
 std::tuple<at::Tensor, at::Tensor> spec_verify(const at::Tensor& t, const at::Tensor& draft,
                                                const c10::optional<at::Tensor>& s, double temperature,
                                                const c10::optional<at::Tensor>& ua,
-                                               const c10::optional<at::Tensor>& us) {
+                                               const c10::optional<at::Tensor>& us, bool point_mass) {
     TORCH_CHECK(draft.dim() == 2, "spec_verify: draft_tokens must be [B, K]");
     const int64_t B = t.size(0), K = draft.size(1);
-    SpecArgs a = spec_setup(t, s, temperature, K);
+    SpecArgs a = spec_setup(t, s, temperature, K, point_mass);
     TORCH_CHECK(draft.is_cuda() && draft.scalar_type() == at::kLong && draft.is_contiguous() && draft.size(0) == B,
                 "spec_verify: draft_tokens must be a contiguous int64 GPU tensor [B, K]");
     if (temperature > 0) {
@@ -1433,10 +1437,10 @@ std::tuple<at::Tensor, at::Tensor> spec_verify(const at::Tensor& t, const at::Te
 void spec_verify_step(const at::Tensor& t, const c10::optional<at::Tensor>& s, double temperature,
                       const at::Tensor& rng, at::Tensor win, at::Tensor ids, at::Tensor out, at::Tensor n_out,
                       const at::Tensor& base, at::Tensor pos_t, at::Tensor pos_d, at::Tensor step_t, at::Tensor step_d,
-                      at::Tensor done, int64_t eos) {
+                      at::Tensor done, int64_t eos, bool point_mass) {
     TORCH_CHECK(win.dim() == 2 && win.size(1) >= 2, "spec_verify_step: win must be [B, K + 1]");
     const int64_t B = t.size(0), K = win.size(1) - 1;
-    SpecArgs a = spec_setup(t, s, temperature, K);
+    SpecArgs a = spec_setup(t, s, temperature, K, point_mass);
     TORCH_CHECK(rng.is_cuda() && rng.scalar_type() == at::kLong && rng.is_contiguous() && rng.numel() == 2,
                 "spec_verify_step: rng must be a contiguous int64 GPU tensor (seed, count)");
     TORCH_CHECK(win.is_cuda() && win.scalar_type() == at::kLong && win.size(0) == B && win.stride(1) == 1,
@@ -1470,6 +1474,42 @@ void spec_verify_step(const at::Tensor& t, const c10::optional<at::Tensor>& s, d
     launch_spec_verify(a, dt_code(t), (int)B, cur_stream());
 }
 
+// ---------------------------------------------------------------- prompt-lookup drafts (lookup_draft.hip)
+void lookup_draft(const at::Tensor& prompt, const at::Tensor& n_prompt, const at::Tensor& out, const at::Tensor& n_out,
+                  at::Tensor win, const at::Tensor& step, const at::Tensor& done, int64_t n_hi, int64_t n_lo) {
+    check_cuda(win, "win");
+    TORCH_CHECK(win.dim() == 2 && win.size(1) >= 2, "lookup_draft: win must be [B, K + 1]");
+    const int64_t B = win.size(0);
+    auto rows = [&](const at::Tensor& x) {
+        return x.is_cuda() && x.get_device() == win.get_device() && x.scalar_type() == at::kLong && x.dim() == 2 &&
+               x.size(0) == B && (x.size(1) <= 1 || x.stride(1) == 1);
+    };
+    TORCH_CHECK(rows(win) && rows(prompt) && rows(out),
+                "lookup_draft: prompt, out and win must be int64 GPU tensors [B, *] on one device, rows dense");
+    TORCH_CHECK(spec_i32(n_prompt, B) && spec_i32(n_out, B) && spec_i32(step, B) && spec_i32(done, B),
+                "lookup_draft: n_prompt, n_out, step and done must be contiguous int32 GPU tensors [B]");
+    TORCH_CHECK(n_lo >= 1 && n_lo <= n_hi && n_hi <= INT32_MAX, "lookup_draft: 1 <= n_lo <= n_hi");
+    TORCH_CHECK(prompt.size(1) + out.size(1) < INT32_MAX, "lookup_draft: history too long");
+    DevGuard g(win.device());
+    LookupArgs a{};
+    a.prompt = (const long long*)prompt.data_ptr<int64_t>();
+    a.prompt_ld = prompt.stride(0);
+    a.prompt_n = (int)prompt.size(1);
+    a.n_prompt = n_prompt.data_ptr<int>();
+    a.out = (const long long*)out.data_ptr<int64_t>();
+    a.out_ld = out.stride(0);
+    a.out_n = (int)out.size(1);
+    a.n_out = n_out.data_ptr<int>();
+    a.win = (long long*)win.data_ptr<int64_t>();
+    a.win_ld = win.stride(0);
+    a.K = (int)(win.size(1) - 1);
+    a.step = step.data_ptr<int>();
+    a.done = done.data_ptr<int>();
+    a.n_hi = (int)n_hi;
+    a.n_lo = (int)n_lo;
+    launch_lookup_draft(a, (int)B, cur_stream());
+}
+
 }  // namespace
 
 TORCH_LIBRARY(bpe_hip, m) {
@@ -1477,10 +1517,13 @@ TORCH_LIBRARY(bpe_hip, m) {
     m.def("sample_step(Tensor logits, float temperature, int top_k, float top_p, Tensor rng, Tensor(a!) ids, "
           "Tensor(b!) out, Tensor(c!)? step, Tensor(d!) done, int eos, int col=-1) -> ()");
     m.def("spec_verify(Tensor target_logits, Tensor draft_tokens, Tensor? draft_logits, float temperature, "
-          "Tensor? ua, Tensor? us) -> (Tensor, Tensor)");
+          "Tensor? ua, Tensor? us, bool point_mass=False) -> (Tensor, Tensor)");
     m.def("spec_verify_step(Tensor target_logits, Tensor? draft_logits, float temperature, Tensor rng, "
           "Tensor(a!) win, Tensor(b!) ids, Tensor(c!) out, Tensor(d!) n_out, Tensor base, Tensor(e!) pos_t, "
-          "Tensor(f!) pos_d, Tensor(g!) step_t, Tensor(h!) step_d, Tensor(i!) done, int eos) -> ()");
+          "Tensor(f!) pos_d, Tensor(g!) step_t, Tensor(h!) step_d, Tensor(i!) done, int eos, "
+          "bool point_mass=False) -> ()");
+    m.def("lookup_draft(Tensor prompt, Tensor n_prompt, Tensor out, Tensor n_out, Tensor(a!) win, Tensor step, "
+          "Tensor done, int n_hi, int n_lo) -> ()");
     m.def("decode_gemv(Tensor x, Tensor? xd, Tensor? ln, float eps, Tensor w, int epi, Tensor? w_scale=None) -> "
           "(Tensor, Tensor)");
     m.def("decode_qkv(Tensor x, Tensor? xd, Tensor? ln, float eps, Tensor w, Tensor(a!) k_cache, "
@@ -1619,4 +1662,5 @@ TORCH_LIBRARY_IMPL(bpe_hip, CUDA, m) {
     m.impl("sample_step", &sample_step);
     m.impl("spec_verify", &spec_verify);
     m.impl("spec_verify_step", &spec_verify_step);
+    m.impl("lookup_draft", &lookup_draft);
 }

@@ -57,6 +57,36 @@ and the draft's ``ids[b, 0]``, and sets ``pos_target[b] = pos_draft[b] = base[b]
 emitted token but the last.  Emission stops, inclusive, at the first ``eos`` or at the last column of ``out``;
 either sets ``done[b]`` and clears the row's ``step`` in both sessions (without them ``m = n + 1``).  A row with
 ``done`` set or ``step == 0`` writes nothing.  ``rng`` is read only.
+
+**Point-mass drafts** (``point_mass=True``): the proposer is deterministic, so ``q_i`` is the point mass at ``d[i]``
+and there are no draft logits (``draft_logits`` is ``None``).  Sampling then reads:
+
+2. draft ``i`` is accepted iff ``ua[i] < p_i(d[i])``;
+4. if ``n < K``, ``y`` is drawn from ``p_{n+1}`` with ``d[n+1]`` zeroed -- the index-order inverse CDF at ``us`` as
+   above -- and from ``p_{n+1}`` itself if that leaves no mass or if ``d[n+1]`` lies outside ``[0, V)`` (such a
+   ``d`` never stands and is never read).
+
+Greedy is unchanged.  It is the function above for one-hot draft logits (``0`` at ``d[i]``, ``-inf`` elsewhere), and
+the kernel computes it in the same fixed-point arithmetic, so the two agree exactly; what is saved is the ``[B, K, V]``
+draft-logits tensor and its row passes.
+
+**Prompt-lookup drafts** (``csrc/lookup_draft.hip``; n-gram drafting from the sequence's own history, as in Saxena,
+"Prompt Lookup Decoding", 2023).  Per sequence ``b`` the history is ``h = prompt[b, :n_prompt[b]] ++ out[b,
+:n_out[b]]`` of length ``L`` (never materialised); its last token ``h[L-1]`` is the last emitted one, ``win[b, 0]``.
+With ``K`` drafts and n-gram bounds ``1 <= n_lo <= n_hi``:
+
+1. A candidate is an end position ``e``, ``0 <= e <= L-2``; its match length ``m(e)`` is the largest ``t <=
+   min(n_hi, e+1)`` with ``h[e-t+1+u] == h[L-t+u]`` for all ``0 <= u < t``.
+2. The chosen ``e`` has the largest ``m(e)`` and, among equal lengths, is the largest (the most recent); it is a
+   match iff that ``m >= n_lo``.  (The same as trying ``n = n_hi`` down to ``n_lo`` and taking the latest earlier
+   occurrence of the last ``n`` tokens that has at least one token after it.)
+3. With a match and ``p = L-1-e >= 1``: ``d[j] = h[e + 1 + (j mod p)]`` for ``j = 0..K-1`` -- the continuation is
+   extended periodically past the end of the history, so a period-``p`` loop yields ``K`` drafts, not ``p``.
+4. With no match, or ``L == 1``: ``d[j] = h[L-1]`` for all ``j``.
+
+Any drafts are valid for the verifier: the proposal is deterministic, so with ``point_mass=True`` the emitted tokens
+remain the target's (greedy) or distributed as the target's (sampling) whatever is proposed.  :func:`lookup_draft`
+writes ``d`` into ``win[b, 1..K]`` inside the captured round; token ids must fit int32.
 """
 
 from __future__ import annotations
@@ -172,32 +202,35 @@ def sample_step_reference(logits, temperature, top_k, top_p, rng, ids, out, step
 
 
 # ---------------------------------------------------------------- speculative verification
-def _check_spec(target_logits: Tensor, draft_tokens: Tensor, draft_logits: Tensor | None, temperature: float) -> None:
+def _check_spec(target_logits: Tensor, draft_tokens: Tensor, draft_logits: Tensor | None, temperature: float,
+                point_mass: bool = False) -> None:
     assert target_logits.dim() == 3 and draft_tokens.dim() == 2, "target_logits [B, K + 1, V], draft_tokens [B, K]"
     B, K1, V = target_logits.shape
     assert K1 >= 2 and V >= 1 and tuple(draft_tokens.shape) == (B, K1 - 1), "target_logits [B, K + 1, V], K >= 1"
     assert target_logits.dtype in (torch.bfloat16, torch.float32), "logits: bf16 or fp32"
-    if temperature > 0:
+    if point_mass:
+        assert draft_logits is None, "point-mass drafts have no draft logits"
+    elif temperature > 0:
         assert draft_logits is not None and tuple(draft_logits.shape) == (B, K1 - 1, V) \
             and draft_logits.dtype == target_logits.dtype, "sampling needs draft_logits [B, K, V] of the target's dtype"
 
 
 def spec_verify(target_logits: Tensor, draft_tokens: Tensor, draft_logits: Tensor | None, temperature: float,
-                ua: Tensor | None = None, us: Tensor | None = None) -> tuple[Tensor, Tensor]:
+                ua: Tensor | None = None, us: Tensor | None = None, point_mass: bool = False) -> tuple[Tensor, Tensor]:
     """``(n [B] int32, y [B] int64)`` of the module docstring for ``target_logits [B, K + 1, V]``, ``draft_tokens
-    [B, K]``, ``draft_logits [B, K, V]`` (``None`` for greedy) and the uniforms ``ua [B, K]``, ``us [B]`` (unused
-    for greedy)."""
-    _check_spec(target_logits, draft_tokens, draft_logits, temperature)
+    [B, K]``, ``draft_logits [B, K, V]`` (``None`` for greedy and for ``point_mass``) and the uniforms ``ua [B, K]``,
+    ``us [B]`` (unused for greedy)."""
+    _check_spec(target_logits, draft_tokens, draft_logits, temperature, point_mass)
     if not target_logits.is_cuda:
-        return spec_verify_reference(target_logits, draft_tokens, draft_logits, temperature, ua, us)
+        return spec_verify_reference(target_logits, draft_tokens, draft_logits, temperature, ua, us, point_mass)
     dev = target_logits.device
     if temperature > 0:
         ua, us = ua.to(dev, torch.float32).contiguous(), us.to(dev, torch.float32).contiguous()
-        draft_logits = draft_logits.contiguous()
+        draft_logits = None if point_mass else draft_logits.contiguous()
     else:
         ua = us = draft_logits = None
     return ops().spec_verify(target_logits.contiguous(), draft_tokens.to(dev, torch.long).contiguous(), draft_logits,
-                             float(temperature), ua, us)
+                             float(temperature), ua, us, bool(point_mass))
 
 
 def _inv_cdf(w: Tensor, u: float) -> int:
@@ -214,7 +247,8 @@ def _argmax_low(x: Tensor) -> int:
     return int((x == x.max()).nonzero()[0])
 
 
-def spec_verify_reference(target_logits, draft_tokens, draft_logits, temperature, ua=None, us=None):
+def spec_verify_reference(target_logits, draft_tokens, draft_logits, temperature, ua=None, us=None,
+                          point_mass: bool = False):
     """The verification function in torch, fp64 masses, one sequence at a time."""
     t = target_logits.double()
     B, K1, V = t.shape
@@ -230,10 +264,20 @@ def spec_verify_reference(target_logits, draft_tokens, draft_logits, temperature
             ys.append(_argmax_low(t[b, n]))
             continue
         soft = lambda x: torch.softmax(x / float(temperature), -1)  # noqa: E731  (exp(-inf) = 0)
-        s = draft_logits[b].double()
+        s = None if point_mass else draft_logits[b].double()
         n, r = 0, None
         while n < K:
-            p, q = soft(t[b, n]), soft(s[n])
+            p = soft(t[b, n])
+            if point_mass:  # q: the point mass at d[n]
+                ok = 0 <= d[n] < V and float(ua[b, n]) < float(p[d[n]])
+                if not ok:
+                    r = p.clone()
+                    if 0 <= d[n] < V:
+                        r[d[n]] = 0
+                    break
+                n += 1
+                continue
+            q = soft(s[n])
             ok = 0 <= d[n] < V and float(ua[b, n]) * float(q[d[n]]) < float(p[d[n]])
             if not ok:
                 r = (p - q).clamp_(min=0)
@@ -251,22 +295,24 @@ def spec_verify_reference(target_logits, draft_tokens, draft_logits, temperature
 
 def spec_verify_step(target_logits: Tensor, draft_logits: Tensor | None, temperature: float, rng: Tensor, win: Tensor,
                      ids: Tensor, out: Tensor, n_out: Tensor, base: Tensor, pos_target: Tensor, pos_draft: Tensor,
-                     step_target: Tensor, step_draft: Tensor, done: Tensor, eos: int) -> None:
+                     step_target: Tensor, step_draft: Tensor, done: Tensor, eos: int, point_mass: bool = False) -> None:
     """Verify one speculative round in place (module docstring): ``win`` int64 ``[B, K + 1]`` holds the last
     emitted token and the K drafts, ``rng`` int64 ``[2]`` = (seed, c) is read only; ``ids`` int64 ``[B, 1]``, ``out``
-    int64 ``[B, N]``, ``n_out`` / ``base`` / ``pos_*`` / ``step_*`` / ``done`` int32 ``[B]``; ``eos < 0``: none."""
-    _check_spec(target_logits, win[:, 1:], draft_logits, temperature)
+    int64 ``[B, N]``, ``n_out`` / ``base`` / ``pos_*`` / ``step_*`` / ``done`` int32 ``[B]``; ``eos < 0``: none.
+    With ``point_mass`` (no draft model) ``ids``, ``pos_draft`` and ``step_draft`` are scratch of those shapes."""
+    _check_spec(target_logits, win[:, 1:], draft_logits, temperature, point_mass)
     if target_logits.is_cuda:
         ops().spec_verify_step(target_logits.contiguous(),
-                               draft_logits.contiguous() if temperature > 0 else None, float(temperature), rng, win,
-                               ids, out, n_out, base, pos_target, pos_draft, step_target, step_draft, done, int(eos))
+                               draft_logits.contiguous() if temperature > 0 and not point_mass else None,
+                               float(temperature), rng, win, ids, out, n_out, base, pos_target, pos_draft, step_target,
+                               step_draft, done, int(eos), bool(point_mass))
         return
     spec_verify_step_reference(target_logits, draft_logits, temperature, rng, win, ids, out, n_out, base, pos_target,
-                               pos_draft, step_target, step_draft, done, eos)
+                               pos_draft, step_target, step_draft, done, eos, point_mass)
 
 
 def spec_verify_step_reference(target_logits, draft_logits, temperature, rng, win, ids, out, n_out, base, pos_target,
-                               pos_draft, step_target, step_draft, done, eos) -> None:
+                               pos_draft, step_target, step_draft, done, eos, point_mass: bool = False) -> None:
     B, K = win.shape[0], win.shape[1] - 1
     seed, c = (int(v) for v in rng.tolist())
     dev = target_logits.device
@@ -274,7 +320,7 @@ def spec_verify_step_reference(target_logits, draft_logits, temperature, rng, wi
     if temperature > 0:
         ua = torch.stack([philox_uniform(seed, c + i, B, dev, stream=1) for i in range(K)], 1)
         us = philox_uniform(seed, c, B, dev, stream=2)
-    ns, ys = spec_verify_reference(target_logits, win[:, 1:], draft_logits, temperature, ua, us)
+    ns, ys = spec_verify_reference(target_logits, win[:, 1:], draft_logits, temperature, ua, us, point_mass)
     N = out.shape[1]
     for b in range(B):
         if int(done[b]) != 0 or int(step_target[b]) == 0:
@@ -297,3 +343,45 @@ def spec_verify_step_reference(target_logits, draft_logits, temperature, rng, wi
             done[b] = 1
             step_target[b] = 0
             step_draft[b] = 0
+
+
+# ---------------------------------------------------------------- prompt-lookup drafts
+def lookup_draft(prompt: Tensor, n_prompt: Tensor, out: Tensor, n_out: Tensor, win: Tensor, step: Tensor, done: Tensor,
+                 n_hi: int, n_lo: int = 1) -> None:
+    """Write the ``K = win.shape[1] - 1`` prompt-lookup drafts of the module docstring into ``win[b, 1..K]``, in
+    place.  ``prompt`` int64 ``[B, P]`` and ``out`` int64 ``[B, N]`` hold the history, of which only ``prompt[b,
+    :n_prompt[b]]`` and ``out[b, :n_out[b]]`` are read; ``n_prompt`` / ``n_out`` / ``step`` / ``done`` int32 ``[B]``.
+    A row with ``done[b] != 0`` or ``step[b] == 0`` keeps its ``win`` row; nothing else is written."""
+    assert win.dim() == 2 and win.shape[1] >= 2, "win: [B, K + 1], K >= 1"
+    assert prompt.dim() == 2 and out.dim() == 2 and prompt.shape[0] == out.shape[0] == win.shape[0], "[B, *] rows"
+    if not 1 <= int(n_lo) <= int(n_hi):
+        raise ValueError(f"lookup_draft: 1 <= n_lo <= n_hi, got n_lo={n_lo}, n_hi={n_hi}")
+    if win.is_cuda:
+        ops().lookup_draft(prompt, n_prompt, out, n_out, win, step, done, int(n_hi), int(n_lo))
+        return
+    lookup_draft_reference(prompt, n_prompt, out, n_out, win, step, done, n_hi, n_lo)
+
+
+def lookup_draft_reference(prompt, n_prompt, out, n_out, win, step, done, n_hi: int, n_lo: int = 1) -> None:
+    """The lookup function in torch, one sequence at a time: every candidate's match length at once."""
+    B, K = win.shape[0], win.shape[1] - 1
+    for b in range(B):
+        if int(done[b]) != 0 or int(step[b]) == 0:
+            continue
+        h = torch.cat([prompt[b, : int(n_prompt[b])], out[b, : int(n_out[b])]])
+        L = h.numel()
+        if L < 1:
+            continue
+        start, p = L - 1, 1  # no match: the last token, K times
+        if L >= 2:
+            e = torch.arange(L - 1, device=h.device)
+            m = torch.zeros_like(e)
+            alive = torch.ones_like(e, dtype=torch.bool)
+            for t in range(min(int(n_hi), L - 1)):  # token t from the end of the suffix against h[e - t]
+                alive = alive & (e >= t) & (h[(e - t).clamp(min=0)] == h[L - 1 - t])
+                m = m + alive
+            best = int(m.max())
+            if best >= int(n_lo):
+                end = int((m == best).nonzero()[-1])  # the most recent of the longest
+                start, p = end + 1, L - 1 - end
+        win[b, 1:] = h[start + torch.arange(K, device=h.device) % p]

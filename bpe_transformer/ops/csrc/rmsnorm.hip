@@ -12,6 +12,8 @@
 #include "common.h"
 #include "kernels.h"
 
+#include <stdexcept>
+
 namespace bpe {
 
 template <typename T>
@@ -498,7 +500,8 @@ static int rms_bwd_dispatch(const T* dy, const T* x, const T* w, const float* rs
     }
     RMS_CASE(1) RMS_CASE(2) RMS_CASE(4) RMS_CASE(8)
 #undef RMS_CASE
-    return grid;
+    // no instance holds more than 8 chunks per lane: nothing was launched, so there is no grid to return
+    throw std::runtime_error("rmsnorm bwd: no kernel for this hidden size (more than 512 vectors per row)");
 }
 
 void launch_add_rmsnorm_fwd(int dtype, const void* x, const void* d, const void* w, void* sum, void* y, float* rstd,

@@ -84,13 +84,21 @@ std::tuple<at::Tensor, at::Tensor> rmsnorm_bwd(const at::Tensor& dy, const at::T
                                                const at::Tensor& rstd, const c10::optional<at::Tensor>& dres,
                                                const c10::optional<at::Tensor>& dw_acc) {
     check_cuda(x, "x");
+    TORCH_CHECK(x.dim() >= 1 && x.numel() > 0 && x.is_contiguous(), "rmsnorm bwd: x must be contiguous and non-empty");
     auto dyc = dy.contiguous();
     const int N = (int)x.size(-1);
     const int M = (int)(x.numel() / N);
+    TORCH_CHECK(N % vec_elems(x) == 0, "rmsnorm bwd: last dim must be a multiple of 8 (bf16) / 4 (fp32)");
     const int nv = N / vec_elems(x);
-    TORCH_CHECK(N <= 8 * 64 * vec_elems(x) || (N % vec_elems(x) == 0 && nv % 256 == 0 && nv <= 1024),
-                "rmsnorm bwd: hidden size too large");
+    TORCH_CHECK(nv <= 8 * 64 || (nv % 256 == 0 && nv <= 1024), "rmsnorm bwd: hidden size too large");
     TORCH_CHECK(dyc.scalar_type() == x.scalar_type(), "rmsnorm bwd: dtype mismatch");
+    TORCH_CHECK(dyc.numel() == x.numel(), "rmsnorm bwd: dy and x sizes differ");
+    TORCH_CHECK(w.scalar_type() == x.scalar_type() && w.numel() == N && w.is_contiguous(),
+                "rmsnorm bwd: weight must be a contiguous [N] tensor of x's dtype");
+    TORCH_CHECK(rstd.scalar_type() == at::kFloat && rstd.numel() == M && rstd.is_contiguous(),
+                "rmsnorm bwd: rstd must be a contiguous fp32 [M] tensor");
+    TORCH_CHECK(dyc.device() == x.device() && w.device() == x.device() && rstd.device() == x.device(),
+                "rmsnorm bwd: tensors on different devices");
     DevGuard g(x.device());
     auto dx = at::empty_like(x);
     const bool acc = dw_acc.has_value() && dw_acc->defined();

@@ -48,7 +48,9 @@ def clip_grad_norm_(parameters: Iterable[torch.nn.Parameter], max_l2_norm: float
             if g.is_contiguous():
                 ops().scale_(g, coef)
             else:
-                g.mul_(coef.to(g.dtype))
+                # what scale_ does, without a host sync: the -1 sentinel leaves g alone, one rounding to g's dtype
+                c = torch.where(coef >= 0, coef, torch.ones_like(coef))
+                g.copy_(g.float() * c)
     elif bool(coef >= 0):  # coef -1 marks a non-finite norm: leave the gradients as they are
         for g in grads:
             g.mul_(coef.to(g.dtype))

@@ -32,7 +32,8 @@ def _ref_grads(fn, inputs, dout):
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 # (64, 768), (4096, 768), (6, 1024) bf16 and (10, 384) fp32: the half-wave-row backward (csrc/rmsnorm.hip), the
-# second with a grid-stride loop over more rows than one round; (7, 512): odd rows, the one-wave-per-row kernel
+# second exactly one round of its 512-block grid (512 * 8 rows; tests/test_rmsnorm_bwd_gpu.py goes beyond one round);
+# (7, 512): odd rows, the one-wave-per-row kernel
 @pytest.mark.parametrize("shape", [(64, 768), (3, 5, 2048), (7, 512), (2048, 2048), (33, 4096), (4096, 768), (6, 1024),
                                    (10, 384)])
 def test_rmsnorm(gpu_device, dtype, shape):

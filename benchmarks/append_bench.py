@@ -16,6 +16,9 @@ filled cache.  Two routes are timed on the same session, alternating, after a wa
 * ``dequant`` -- ``kv_dequant`` of the layer's valid rows into a one-layer bf16 scratch + the bf16 ``cache_attn``, called
   through the ops on the same cache (``KVView.attend`` is swapped for the timed call), two launches per layer.
 
+``--kv-layout paged`` times the paged session (``DecodeSession(kv_layout="paged")``, of ``--kv-dtype``) against the
+slab one on this tree's route, two sessions alternating: the same launches, the cache rows behind a block table.
+
 ``--long-cache`` adds the 4-layer Llama-shaped model with 4030 tokens cached (max_len 4096) and windows of 64 and 512.
 
 Every timed call starts from the same cache state (the position is put back, the rows are overwritten with the same
@@ -23,6 +26,7 @@ values).  Times are medians of ``--reps`` host-synchronised calls; one JSON line
 
     python benchmarks/append_bench.py --filled 512 --tokens 9 16 64 256 512
     python benchmarks/append_bench.py --kv-dtype fp8 --long-cache
+    python benchmarks/append_bench.py --kv-layout paged
 """
 import argparse
 import json
@@ -129,6 +133,38 @@ def run_fp8(a, name, B, model, vocab, filled, tokens):
     torch.cuda.empty_cache()
 
 
+def run_paged(a, name, B, model, vocab, filled, tokens):
+    """Slab against paged sessions of ``--kv-dtype`` on the session's own route, alternating, ``--reps`` rounds."""
+    max_len = 4096 if name == "llama-4l" else filled + max(tokens)
+    kw = dict(max_len=max_len, kv_dtype=a.kv_dtype, prefill_chunk=512)
+    sess = {"slab": DecodeSession(model, B, **kw), "paged": DecodeSession(model, B, kv_layout="paged", **kw)}
+    G = sess["slab"].H // sess["slab"].Hkv
+    ids = torch.randint(0, vocab, (B, filled + max(tokens)), device="cuda")
+    with torch.no_grad():
+        for s in sess.values():
+            s.prefill(ids[:, :filled])
+            s.prefill_chunk = None
+        for T in tokens:
+            new = ids[:, filled : filled + T]
+            for s in sess.values():
+                timed_append(s, new, filled, "cache")
+            t = {k: [] for k in sess}
+            for _ in range(a.reps):
+                for k, s in sess.items():
+                    t[k].append(timed_append(s, new, filled, "cache"))
+            med = {k: statistics.median(v) for k, v in t.items()}
+            print(json.dumps({"config": name, "kv_dtype": a.kv_dtype, "batch": B, "G": G, "filled": filled, "T": T,
+                              "rounds": a.reps,
+                              "slab_ms_median_min_max": [round(x * 1e3, 3) for x in (med["slab"], min(t["slab"]),
+                                                                                     max(t["slab"]))],
+                              "paged_ms_median_min_max": [round(x * 1e3, 3) for x in (med["paged"], min(t["paged"]),
+                                                                                      max(t["paged"]))],
+                              "paged_over_slab": round(med["paged"] / med["slab"], 4),
+                              "pages_in_use": sess["paged"].cache.pages_in_use}), flush=True)
+    del sess
+    torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", nargs="+", default=["gpt2-small:1", "gpt2-small:8", "llama-2l:1"],
@@ -138,6 +174,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: the fp8-cache session, cache_attn_fp8 against kv_dequant + cache_attn")
+    ap.add_argument("--kv-layout", choices=["slab", "paged"], default="slab",
+                    help="paged: the paged session against the slab one (of --kv-dtype), alternating")
     ap.add_argument("--long-cache", action="store_true",
                     help="add llama-4l (max_len 4096) with 4030 tokens cached, windows of 64 and 512")
     ap.add_argument("--long-batch", type=int, nargs="+", default=[1, 16], help="batch sizes of the --long-cache arm")
@@ -153,6 +191,9 @@ def main():
         if name not in models:
             models[name] = build(name)
         model, vocab = models[name]
+        if a.kv_layout == "paged":
+            run_paged(a, name, B, model, vocab, filled, tokens)
+            continue
         if a.kv_dtype == "fp8":
             run_fp8(a, name, B, model, vocab, filled, tokens)
             continue

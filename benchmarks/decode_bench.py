@@ -13,11 +13,15 @@ fills it (``4096 - tokens - 2``), batch 64 by default.
 ``--weight-dtype fp8`` adds, in the same alternating way, the fp8-weight session (``DecodeSession(weight_dtype="fp8")``)
 against the bf16 one: median, min and max of each over the rounds, the ratio of the medians and both sessions'
 projection-weight bytes.
+``--kv-layout paged`` adds, in the same alternating way, the paged session (``DecodeSession(kv_layout="paged")``)
+against the slab one -- with ``--kv-dtype fp8`` both on the fp8 cache: median, min and max of each, the ratio of the
+medians, the pages in use and the paged attention kernel alone through the session's block table.
 Random-init weights, synthetic prompts; one JSON line per configuration.
 
     python benchmarks/decode_bench.py --model gpt2-small --batch 1 8 64 --prompt 128 --tokens 256
     python benchmarks/decode_bench.py --kv-dtype fp8 --long-context --batch 64 --tokens 64
     python benchmarks/decode_bench.py --weight-dtype fp8 --model llama-1.1b --batch 1 8 64
+    python benchmarks/decode_bench.py --kv-layout paged --model gpt2-small --batch 1 8 64
 """
 import argparse
 import json
@@ -102,6 +106,38 @@ def w8_arm(model, sess, ids, prompt, tokens, rounds, graph, chunk):
     }
 
 
+def paged_arm(model, sess, ids, prompt, tokens, rounds, graph, chunk, kv_dtype):
+    """Slab and paged sessions (of ``kv_dtype``) alternating in this process -> the extra fields of the JSON line."""
+    B = ids.shape[0]
+    kw = dict(max_len=sess.max_len, use_graph=graph, prefill_chunk=chunk, kv_dtype=kv_dtype)
+    slab = sess if kv_dtype == "bf16" else DecodeSession(model, B, **kw)
+    pg = DecodeSession(model, B, kv_layout="paged", **kw)
+    t = {"slab": [], "paged": []}
+    for _ in range(rounds):
+        t["slab"].append(time_decode(slab, ids, prompt, tokens))
+        t["paged"].append(time_decode(pg, ids, prompt, tokens))
+    L, c = pg.length, pg.cache
+    q = torch.randn(B, pg.H * pg.D, device="cuda", dtype=torch.bfloat16)
+    pos = torch.tensor([L - 1], dtype=torch.int32, device="cuda")
+    tail = dict(block_table=c.block_table, max_len=c.max_len)
+    if kv_dtype == "fp8":
+        fn = lambda: dec.decode_attention_fp8(q, c.k[0], c.v[0], c.k_scale[0], c.v_scale[0], pos, pg.H, **tail)  # noqa: E731
+    else:
+        fn = lambda: dec.decode_attention(q, c.k[0], c.v[0], pos, pg.H, **tail)  # noqa: E731
+    t_attn = time_attn(fn)
+    med = lambda x: sorted(x)[len(x) // 2]  # noqa: E731
+    mmm = lambda x: [round(med(x) * 1e3, 4), round(min(x) * 1e3, 4), round(max(x) * 1e3, 4)]  # noqa: E731
+    return {
+        "layout_rounds": rounds, "layout_kv_dtype": kv_dtype,
+        "slab_decode_ms_per_step_median_min_max": mmm(t["slab"]),
+        "paged_decode_ms_per_step_median_min_max": mmm(t["paged"]),
+        "paged_over_slab": round(med(t["paged"]) / med(t["slab"]), 4),
+        "pages_in_use": c.pages_in_use, "pages": c.num_pages,
+        "slab_cache_bytes": slab.cache.nbytes(), "paged_pool_bytes": c.nbytes(),
+        "paged_attn_us_per_layer": round(t_attn * 1e6, 2),
+    }
+
+
 def ragged_lengths(batch, prompt):
     """Prompt lengths over [prompt / 4, prompt], fixed seed; the longest is ``prompt`` itself."""
     g = torch.Generator().manual_seed(1234)
@@ -137,8 +173,10 @@ def main():
                     help="fp8: also time the fp8-cache session against the bf16 one, alternating in this process")
     ap.add_argument("--weight-dtype", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: also time the fp8-weight session against the bf16 one, alternating in this process")
+    ap.add_argument("--kv-layout", choices=["slab", "paged"], default="slab",
+                    help="paged: also time the paged session against the slab one, alternating in this process")
     ap.add_argument("--rounds", type=int, default=5,
-                    help="alternating rounds of the --kv-dtype fp8 / --weight-dtype fp8 comparisons")
+                    help="alternating rounds of the --kv-dtype fp8 / --weight-dtype fp8 / --kv-layout paged comparisons")
     ap.add_argument("--long-context", action="store_true",
                     help="Llama-shaped model cut to --layers layers, max_len 4096, a prompt that nearly fills it")
     ap.add_argument("--layers", type=int, default=4)
@@ -199,6 +237,8 @@ def main():
                 out.update(fp8_arm(model, sess, ids, a.prompt, a.tokens, a.rounds, not a.no_graph, chunk))
             if a.weight_dtype == "fp8":
                 out.update(w8_arm(model, sess, ids, a.prompt, a.tokens, a.rounds, not a.no_graph, chunk))
+            if a.kv_layout == "paged":
+                out.update(paged_arm(model, sess, ids, a.prompt, a.tokens, a.rounds, not a.no_graph, chunk, a.kv_dtype))
             if a.ragged:
                 lengths = ragged_lengths(B, a.prompt)
                 rs = DecodeSession(model, B, max_len=max_len, use_graph=not a.no_graph, ragged=True)

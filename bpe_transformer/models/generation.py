@@ -63,6 +63,36 @@ launch and a write per matrix.  Composes with ``kv_dtype="fp8"``, ``ragged``,
 ``prefill_chunk``, the device sampler and the graph (the scratch is static).
 Not available with a draft model yet.
 
+**Paged cache** (``kv_layout="paged"``, opt-in, with ``num_pages``): instead of one ``Lmax``-row slab per slot,
+``k, v: [num_layers, P, Hkv, 256, D]`` are pools of ``P`` pages of 256 rows (either row format; an fp8 pool has
+``k_scale, v_scale: [num_layers, P, Hkv, 256]``), and a device int32 ``block_table [B, NB]``, ``NB = ceil(Lmax /
+256)``, says which page holds positions ``256 j .. 256 j + 255`` of sequence ``b`` (``-1``: none; page ``p`` means
+page ``p`` of every layer's pool; ``ops/decode.py`` states the format).  A sequence costs the pages it uses, not its
+worst-case context.  A page is ``decode_attn``'s key chunk and four of ``cache_attn``'s key tiles, so every cache
+kernel takes the table with one lookup per chunk / per four tiles and runs the slab kernel's arithmetic on the same
+rows: a paged session's tokens and logits are the slab session's, bit for bit.  The allocator lives on the host
+(:class:`KVCache`: a mirror of the table, a free list, one reference count per page):
+
+* pages are allocated from the length mirror *before* the launch that needs them -- prefill, append and chunked
+  prefill reserve up to ``len + n``, a host-sampled decode step ``len + 1`` for the active sequences, and the device
+  sampler ``min(len + sync_every, max_len)`` before each run of replays (it does not know on the host which sequences
+  have finished; at most one page per sequence too many, given back when ``generate`` returns).  The table is a
+  static device tensor updated in stream order, like ``step``: the graph is captured once and nothing new syncs;
+* a pool that runs out raises ``RuntimeError`` (pages needed, pages free) before the call that needed the pages has
+  launched or changed anything, and the session stays usable.  That holds per call: a ``generate`` that runs out
+  part-way raises with the prompt and the tokens so far in the cache.  ``num_pages=None`` means ``batch * NB``, which
+  is never short;
+* ``reset_slot``, ``reset`` and ``truncate`` give back the pages wholly past the new length;
+* ``fork_slot(src, dst)`` (ragged, ``dst`` empty) is prefix sharing: ``dst`` takes ``src``'s length, shares every
+  page wholly below it by reference count and gets a private copy of the partial last page.  Appends only write at
+  or past a sequence's own length, so a shared page is never written; ``truncate`` to a length inside a shared page
+  first gives the slot a private copy.  A page returns to the pool when its last holder lets go.
+
+The kernels do not trust the table any more than ``pos``: readers clamp a page id into the pool, an append without a
+valid entry writes nothing (a ragged prefill's pad tokens past a sequence's reserved pages are dropped that way).
+Composes with ``kv_dtype="fp8"``, ``weight_dtype="fp8"``, ``ragged``, ``prefill_chunk``, both samplers and the
+graph.  Not available with a draft model or prompt lookup yet.
+
 On the CPU, in fp32, or with the reference ablations (post-norm, no RMSNorm,
 non-SwiGLU FFN) the same session runs the oracle math over the same cache
 (with fp8 weights: on a copy of the model that holds the dequantised rows).
@@ -107,7 +137,7 @@ the last few tokens), which needs no second model, cache or decode step.
 Either way the target scores the ``K + 1`` window in one pass and
 ``spec_verify_step`` keeps the drafts that stand; greedy output is the
 target's own, sampled output is distributed as the target's.  Neither
-composes with the fp8 cache or fp8 weights yet.
+composes with the fp8 cache, fp8 weights or the paged cache yet.
 """
 
 from __future__ import annotations
@@ -120,6 +150,7 @@ import torch
 from torch import Tensor
 
 from ..ops import reference as F
+from ..ops.decode import KV_PAGE  # rows of a page of the paged cache (csrc/kv_cache.h)
 
 # decode steps of up to this many sequences run on the fused skinny-GEMM kernels (they take up to 16 -- one MFMA
 # column block -- but every workgroup re-normalises all rows in its prologue, so past ~12 rows the library
@@ -172,19 +203,47 @@ def _gemv_ok(m: int, k: int) -> bool:
     return rows * k * 2 <= 160 * 1024 or mfma
 
 
+
+
 class KVCache:
     """Per-layer K/V caches ``[L, B, Hkv, Lmax, D]`` plus the device-side fill position: one int32 shared by the
     batch, or with ``ragged`` one per sequence (``pos [B]``, host mirror ``lengths``).
 
     ``kv_dtype="fp8"``: ``k`` / ``v`` are ``float8_e4m3fn`` bytes and ``k_scale`` / ``v_scale [L, B, Hkv, Lmax]`` hold
     one power-of-two fp32 scale per row (``ops/decode.py`` states the format); ``dtype`` is then only the dtype in
-    which :meth:`read` hands rows back."""
+    which :meth:`read` hands rows back.
+
+    ``kv_layout="paged"``: ``k`` / ``v`` (and the fp8 scales) are pools ``[L, P, Hkv, 256, D]`` (``[L, P, Hkv, 256]``)
+    of ``num_pages`` pages -- page ``p`` means page ``p`` of every layer's pool -- behind the device ``block_table
+    [B, NB]`` (int32, ``NB = ceil(max_len / 256)``, ``-1`` = unallocated; ``ops/decode.py`` states the format).  The
+    host keeps a mirror of the table, a free list and one reference count per page.  :meth:`reserve` allocates, from
+    the length mirror and before the launch that needs the pages; :meth:`release` gives back the pages wholly past a
+    length; :meth:`fork` lets a second sequence share a prefix by reference.  Table updates go into the static
+    device tensor in stream order, so a captured graph that reads it stays valid.  ``num_pages=None`` means ``batch *
+    NB``, which is never short."""
 
     def __init__(self, num_layers: int, batch: int, num_kv_heads: int, max_len: int, head_dim: int, device=None,
-                 dtype=torch.bfloat16, ragged: bool = False, kv_dtype: str = "bf16"):
+                 dtype=torch.bfloat16, ragged: bool = False, kv_dtype: str = "bf16", kv_layout: str = "slab",
+                 num_pages: int | None = None):
         if kv_dtype not in ("bf16", "fp8"):
             raise ValueError(f"kv_dtype: 'bf16' or 'fp8', got {kv_dtype!r}")
+        if kv_layout not in ("slab", "paged"):
+            raise ValueError(f"kv_layout: 'slab' or 'paged', got {kv_layout!r}")
+        if num_pages is not None and kv_layout != "paged":
+            raise ValueError("num_pages needs kv_layout='paged'")
+        self.kv_layout = kv_layout
+        self.paged = kv_layout == "paged"
         shape = (num_layers, batch, num_kv_heads, max_len, head_dim)
+        if self.paged:
+            self.pages_per_seq = nb = (max_len + KV_PAGE - 1) // KV_PAGE
+            self.num_pages = batch * nb if num_pages is None else int(num_pages)
+            if self.num_pages < 1:
+                raise ValueError(f"num_pages: at least one page, got {num_pages!r}")
+            shape = (num_layers, self.num_pages, num_kv_heads, KV_PAGE, head_dim)
+            self.block_table = torch.full((batch, nb), -1, device=device, dtype=torch.int32)
+            self._table = [[-1] * nb for _ in range(batch)]  # host mirror of block_table
+            self._free = list(range(self.num_pages - 1, -1, -1))  # popped from the end: lowest page first
+            self._ref = [0] * self.num_pages  # table entries that name the page
         self.kv_dtype = kv_dtype
         self.fp8 = kv_dtype == "fp8"
         self.dtype = dtype
@@ -219,6 +278,135 @@ class KVCache:
     def reset(self) -> None:
         self.pos.zero_()
         self._len = [0] * self.batch
+        if self.paged:
+            self.release(range(self.batch), [0] * self.batch)
+
+    # ---- paged layout: the allocator (host side).  On a slab cache reserve / release / cut do nothing and the page
+    # counts are 0; fork is refused.
+    @property
+    def pages_free(self) -> int:
+        return len(self._free) if self.paged else 0
+
+    @property
+    def pages_in_use(self) -> int:
+        return self.num_pages - len(self._free) if self.paged else 0
+
+    @staticmethod
+    def _npages(n: int) -> int:
+        return (n + KV_PAGE - 1) // KV_PAGE
+
+    def _take(self, need: int) -> None:
+        if need > len(self._free):
+            raise RuntimeError(f"KV cache out of pages: {need} needed, {len(self._free)} free "
+                               f"(of {self.num_pages}; a page is {KV_PAGE} tokens of one sequence)")
+
+    def _alloc(self) -> int:
+        p = self._free.pop()
+        self._ref[p] = 1
+        return p
+
+    def _drop(self, p: int) -> None:
+        self._ref[p] -= 1
+        if self._ref[p] == 0:
+            self._free.append(p)
+
+    def _sync_table(self) -> None:
+        """The host mirror -> the static device table, in stream order (like the decode step's ``step``)."""
+        self.block_table.copy_(torch.tensor(self._table, dtype=torch.int32))
+
+    def reserve(self, rows, upto) -> None:
+        """Sequence ``rows[i]`` is about to hold up to ``upto[i]`` tokens (clamped to ``max_len``): allocate the pages
+        it lacks.  Raises ``RuntimeError`` (pages needed, pages free) before anything is changed."""
+        if not self.paged:
+            return
+        want = [(r, j) for r, n in zip(rows, upto) for j in range(self._npages(min(int(n), self.max_len)))
+                if self._table[r][j] < 0]
+        if not want:
+            return
+        self._take(len(want))
+        for r, j in want:
+            self._table[r][j] = self._alloc()
+        self._sync_table()
+
+    def release(self, rows, lengths) -> None:
+        """Give back the pages of sequence ``rows[i]`` that lie wholly past its first ``lengths[i]`` tokens (a page
+        returns to the pool when no table entry names it any more)."""
+        if not self.paged:
+            return
+        changed = False
+        for r, n in zip(rows, lengths):
+            for j in range(self._npages(int(n)), self.pages_per_seq):
+                if self._table[r][j] >= 0:
+                    self._drop(self._table[r][j])
+                    self._table[r][j] = -1
+                    changed = True
+        if changed:
+            self._sync_table()
+
+    def _copy_page(self, src: int, dst: int) -> None:
+        for t in (self.k, self.v) + ((self.k_scale, self.v_scale) if self.fp8 else ()):
+            t[:, dst] = t[:, src]
+
+    def cut(self, rows, lengths) -> None:
+        """Sequence ``rows[i]`` is cut back to ``lengths[i]`` tokens: :meth:`release` what lies wholly past them, and
+        where the new end lies inside a page that another sequence still shares, give this one a private copy of it
+        -- its next tokens will be written there.  The sequences are taken in order, on the reference counts as the
+        cuts before them leave them: of several holders that cut into the same page the last keeps the original, and
+        a page that all its holders let go in this call counts as free for the copies.  Raises ``RuntimeError``
+        before anything is changed."""
+        if not self.paged:
+            return
+        rows, lengths = list(rows), [int(n) for n in lengths]
+        ref, freed, cow = list(self._ref), 0, []  # the call played through on a copy of the counts
+        for r, n in zip(rows, lengths):
+            for j in range(self._npages(n), self.pages_per_seq):
+                p = self._table[r][j]
+                if p >= 0:
+                    ref[p] -= 1
+                    freed += ref[p] == 0
+        for r, n in zip(rows, lengths):
+            p = self._table[r][n // KV_PAGE] if n % KV_PAGE else -1
+            if p >= 0 and ref[p] > 1:
+                ref[p] -= 1
+                cow.append((r, n // KV_PAGE))
+        self._take(max(len(cow) - freed, 0))
+        self.release(rows, lengths)
+        if not cow:
+            return
+        for r, j in cow:
+            old, new = self._table[r][j], self._alloc()
+            self._copy_page(old, new)
+            self._drop(old)
+            self._table[r][j] = new
+        self._sync_table()
+
+    def fork(self, src: int, dst: int) -> None:
+        """Prefix sharing: the empty sequence ``dst`` becomes a copy of ``src``.  It takes ``src``'s length, shares
+        (by reference count) every page wholly below it, and gets a private copy -- all layers, K, V and scales --
+        of the partial last page.  Appends only write at or past a sequence's own length, so a shared page is never
+        written (``truncate`` into one unshares it first)."""
+        assert self.paged and self.ragged, "fork needs a ragged session with kv_layout='paged'"
+        assert src != dst and self._len[dst] == 0, "fork: dst must be another, empty slot"
+        n = self._len[src]
+        full, part = n // KV_PAGE, int(n % KV_PAGE > 0)
+        held = sum(p >= 0 and self._ref[p] == 1 for p in self._table[dst])  # (its own, freed first: none if emptied)
+        self._take(max(part - held, 0))
+        self.release([dst], [0])
+        for j in range(full):
+            p = self._table[dst][j] = self._table[src][j]
+            self._ref[p] += 1
+        if part:
+            p = self._table[dst][full] = self._alloc()
+            self._copy_page(self._table[src][full], p)
+        self._sync_table()
+        self._len[dst] = n
+        self.pos[dst : dst + 1].fill_(n)
+
+    def _pool(self, t: Tensor, rows: list[int], n: int) -> Tensor:
+        """Oracle path: the first ``n`` rows of the sequences ``rows`` of one layer's pool, through the table."""
+        from ..ops.decode import paged_gather
+
+        return paged_gather(t, torch.tensor([self._table[r] for r in rows]), self.max_len)[:, :, :n]
 
     def advance(self, rows, steps) -> None:
         """Host mirror: sequence ``rows[i]`` grew by ``steps[i]`` tokens."""
@@ -227,12 +415,26 @@ class KVCache:
 
     def nbytes(self) -> int:
         """Bytes of K and V, the fp8 cache's scales included: ``(D + 4) / (2 D)`` of the bf16 cache's."""
-        n = 2 * self.k.numel() * self.k.element_size()
+        n = 2 * self.k.numel() * self.k.element_size()  # (paged: of the pool)
         return n + 2 * self.k_scale.numel() * 4 if self.fp8 else n
 
     def write(self, layer: int, row: int, lo: int, hi: int, k: Tensor, v: Tensor) -> None:
         """Oracle path: ``k`` / ``v [Hkv, hi - lo, D]`` become rows ``lo .. hi - 1`` of sequence ``row`` (fp8: rounded
-        to bf16, as the bf16 cache would hold them, then quantised)."""
+        to bf16, as the bf16 cache would hold them, then quantised).  Paged: page by page through the table;
+        rows without a page are dropped, as the kernels drop them."""
+        if self.paged:
+            a = lo
+            while a < hi:
+                b = min(hi, (a // KV_PAGE + 1) * KV_PAGE)
+                page = self._table[row][a // KV_PAGE]
+                if page >= 0:  # (no page: dropped, as the kernels drop it -- an inactive sequence's token, a pad token)
+                    self._write(layer, page, a % KV_PAGE, a % KV_PAGE + b - a, k[:, a - lo : b - lo],
+                                v[:, a - lo : b - lo])
+                a = b
+            return
+        self._write(layer, row, lo, hi, k, v)
+
+    def _write(self, layer: int, row: int, lo: int, hi: int, k: Tensor, v: Tensor) -> None:
         if not self.fp8:
             self.k[layer, row, :, lo:hi] = k.to(self.k.dtype)
             self.v[layer, row, :, lo:hi] = v.to(self.v.dtype)
@@ -244,35 +446,45 @@ class KVCache:
 
     def read(self, layer: int, rows: list[int], n: int, dtype) -> tuple[Tensor, Tensor]:
         """Oracle path: the first ``n`` rows of the sequences ``rows`` as ``dtype`` (fp8: dequantised, exactly)."""
+        if self.paged:
+            get = lambda t: self._pool(t[layer], rows, n)
+        else:
+            get = lambda t: t[layer, rows, :, :n]
         if not self.fp8:
-            return self.k[layer, rows, :, :n].to(dtype), self.v[layer, rows, :, :n].to(dtype)
+            return get(self.k).to(dtype), get(self.v).to(dtype)
         from ..ops.decode import kv_dequantize_reference as deq
 
-        return (deq(self.k[layer, rows, :, :n], self.k_scale[layer, rows, :, :n], dtype),
-                deq(self.v[layer, rows, :, :n], self.v_scale[layer, rows, :, :n], dtype))
+        return deq(get(self.k), get(self.k_scale), dtype), deq(get(self.v), get(self.v_scale), dtype)
 
 
 class KVView:
     """The cache as one pass over the layers sees it -- ``k`` / ``v [L, n, Hkv, Lmax, D]``, ``pos`` and, for fp8, the
     row ``scales`` -- of the whole batch or of one slot (``cache.k[:, b:b+1]`` ...: contiguous slabs at the same
     addresses, so a captured graph stays valid).  Every HIP op call that depends on the cache format is made here:
-    the engine appends and attends, and does not know what a row is stored as.  ``h`` is the HIP ops handle, ``rope``
-    the session's ``(cos, sin, use_rope)``."""
+    the engine appends and attends, and does not know what a row is stored as, nor where.  ``h`` is the HIP ops
+    handle, ``rope`` the session's ``(cos, sin, use_rope)``.  A paged cache's view holds the whole pools, and the slot
+    is a row of the block table (``block_table[b:b+1]``); ``pg`` is then the ``(block_table, max_len)`` tail of every
+    op call, and empty for slabs, whose calls are what they always were."""
 
     def __init__(self, cache: KVCache, b: int | None = None):
-        one = (lambda t: t) if b is None else (lambda t: t[:, b : b + 1])
+        one = (lambda t: t) if b is None or cache.paged else (lambda t: t[:, b : b + 1])
         self.cache = cache
         self.k, self.v = one(cache.k), one(cache.v)
         self.pos = cache.pos if b is None else cache.pos[b : b + 1]
         self.scales = (one(cache.k_scale), one(cache.v_scale)) if cache.fp8 else None
+        self.pg = ()
+        if cache.paged:
+            self.pg = (cache.block_table if b is None else cache.block_table[b : b + 1], cache.max_len)
+        self.n = cache.batch if b is None else 1  # sequences
 
     def append(self, h, qkv: Tensor, li: int, T: int, H: int, rope) -> Tensor:
         """RoPE and cache write of layer ``li``'s fused-QKV rows, ``T`` new tokens per sequence; returns the roped q."""
-        B = self.k.shape[1]
+        B = self.n
         if self.scales is None:
-            return h.kv_append(qkv, self.k[li], self.v[li], rope[0], rope[1], self.pos, B, T, H, rope[2])
+            return h.kv_append(qkv, self.k[li], self.v[li], rope[0], rope[1], self.pos, B, T, H, rope[2], *self.pg)
         ks, vs = self.scales
-        return h.kv_append_fp8(qkv, self.k[li], self.v[li], ks[li], vs[li], rope[0], rope[1], self.pos, B, T, H, rope[2])
+        return h.kv_append_fp8(qkv, self.k[li], self.v[li], ks[li], vs[li], rope[0], rope[1], self.pos, B, T, H, rope[2],
+                               *self.pg)
 
     def attend(self, h, q: Tensor, li: int, T: int, H: int, kind: str, combine: bool = True) -> Tensor:
         """Attention of the appended tokens over the cache as stored: ``kind`` ``"cache"`` (``cache_attn``; fp8:
@@ -281,20 +493,21 @@ class KVView:
         scale = 1.0 / math.sqrt(k.shape[-1])
         if self.scales is None:
             if kind == "cache":
-                return h.cache_attn(q, k, v, pos, H, scale, T)
-            return h.decode_attn(q, k, v, pos, H, scale, combine, T)
+                return h.cache_attn(q, k, v, pos, H, scale, T, *self.pg)
+            return h.decode_attn(q, k, v, pos, H, scale, combine, T, *self.pg)
         ks, vs = self.scales[0][li], self.scales[1][li]
         if kind == "cache":
-            return h.cache_attn_fp8(q, k, v, ks, vs, pos, H, scale, T)
-        return h.decode_attn_fp8(q, k, v, ks, vs, pos, H, scale, combine, T)
+            return h.cache_attn_fp8(q, k, v, ks, vs, pos, H, scale, T, *self.pg)
+        return h.decode_attn_fp8(q, k, v, ks, vs, pos, H, scale, combine, T, *self.pg)
 
     def decode_qkv(self, h, xr: Tensor, xd, ln1: Tensor, eps: float, wqkv: Tensor, li: int, H: int, rope, ws=()):
         """QKV step of the skinny decode route -> ``(q, x + xd)``: the fused ``decode_qkv`` (projection, RoPE, cache
         write), or for fp8 ``decode_gemv`` with the plain epilogue followed by :meth:`append` (a row's amax spans
         several workgroups of the fused epilogue).  ``ws``: ``(w_scale,)`` when ``wqkv`` is an e4m3 matrix."""
         if self.scales is None:
+            tail = ws if not self.pg else (ws[0] if ws else None, *self.pg)  # (w_scale precedes the table)
             return h.decode_qkv(xr, xd, ln1, eps, wqkv, self.k[li], self.v[li], rope[0], rope[1], self.pos, H, rope[2],
-                                *ws)
+                                *tail)
         qkv, s = h.decode_gemv(xr, xd, ln1, eps, wqkv, 0, *ws)
         return self.append(h, qkv, li, 1, H, rope), s
 
@@ -383,10 +596,16 @@ class DecodeSession:
     the skinny GEMMs; prefill, appends, ``score`` and batch > 8 dequantise each matrix into one static bf16 scratch
     (sized for the largest, reused in stream order) just before its GEMM, and pay for that.  Off the fast path the
     session runs the oracle math on a copy of the model that holds the dequantised rows.  No draft model yet.
+
+    ``kv_layout="paged"`` keeps the cache as a pool of ``num_pages`` 256-row pages behind a block table (module
+    docstring: format, allocator rules, ``RuntimeError`` on exhaustion): the same launches with the table as a
+    trailing argument, the same bits.  ``cache.pages_in_use`` / ``cache.pages_free`` report the pool;
+    :meth:`fork_slot` shares a prefix between slots of a ragged session.
     """
 
     def __init__(self, model, batch: int, max_len: int | None = None, use_graph: bool = True, ragged: bool = False,
-                 prefill_chunk: int | None = None, kv_dtype: str = "bf16", weight_dtype: str = "bf16"):
+                 prefill_chunk: int | None = None, kv_dtype: str = "bf16", weight_dtype: str = "bf16",
+                 kv_layout: str = "slab", num_pages: int | None = None):
         assert prefill_chunk is None or prefill_chunk >= 1, "prefill_chunk: a positive number of tokens, or None"
         if weight_dtype not in ("bf16", "fp8"):
             raise ValueError(f"weight_dtype: 'bf16' or 'fp8', got {weight_dtype!r}")
@@ -408,8 +627,9 @@ class DecodeSession:
         p = model.lm_head.weight
         self.device = p.device
         self.cache = KVCache(len(model.layers), batch, self.Hkv, self.max_len, self.D, self.device, p.dtype, ragged,
-                             kv_dtype)
+                             kv_dtype, kv_layout, num_pages)
         self.fp8 = self.cache.fp8
+        self.kv_layout = kv_layout
         self.fast = self._fast_ok()
         self.use_graph = use_graph and self.fast
         # ragged: per-sequence advance of the decode step (1 = active), static so that the captured graph reads it
@@ -510,6 +730,7 @@ class DecodeSession:
         assert len(step) == B, "active: one flag per sequence"
         rows = list(range(B))
         assert all(c + s <= self.max_len for c, s in zip(self.cache._len, step)), "KV cache full"
+        self.cache.reserve(rows, [c + s for c, s in zip(self.cache._len, step)])
         ids = ids.reshape(B, 1).to(self.device)
         if self._step is not None and step != self._step_host:
             # (the mask changes only when a sequence finishes or a slot is refilled)
@@ -540,6 +761,7 @@ class DecodeSession:
         c = self.cache
         rows = list(range(B))
         assert all(p + T <= self.max_len for p in c._len), "KV cache full"
+        c.reserve(rows, [p + T for p in c._len])
         if not self.fast:  # the oracle math reads the host lengths, which therefore move chunk by chunk
             out = []
             for t0, w in _chunks(T, self.prefill_chunk):
@@ -554,21 +776,38 @@ class DecodeSession:
     @torch.no_grad()
     def truncate(self, lengths) -> None:
         """Ragged sessions: cut sequence ``b`` back to its first ``lengths[b]`` tokens (at most what it holds).  The
-        cache rows past the new position become invisible, like everything at and past ``pos[b]``."""
+        cache rows past the new position become invisible, like everything at and past ``pos[b]``.  A paged cache
+        takes back the pages wholly past the new length; where the new end lies inside a page shared with a fork, the
+        sequence first gets a private copy of that page (``RuntimeError`` if the pool has none left)."""
         assert self.ragged, "truncate needs DecodeSession(..., ragged=True)"
         n = [int(x) for x in (lengths.tolist() if isinstance(lengths, Tensor) else lengths)]
         c = self.cache
         assert len(n) == self.batch and all(0 <= x <= p for x, p in zip(n, c._len)), \
             "lengths: one int per sequence, at most its cached length"
+        c.cut(range(self.batch), n)
         c.pos.copy_(torch.tensor(n, dtype=torch.int32))
         c._len[:] = n
 
     @torch.no_grad()
     def reset_slot(self, b: int) -> None:
-        """Ragged sessions: empty slot ``b`` for a new request; the other sequences are untouched."""
+        """Ragged sessions: empty slot ``b`` for a new request; the other sequences are untouched.  A paged cache
+        takes its pages back (a page shared with a fork stays until its last holder lets go)."""
         assert self.ragged, "slots need DecodeSession(..., ragged=True)"
         self.cache.pos[b : b + 1].zero_()
         self.cache.lengths[b] = 0
+        self.cache.release([b], [0])
+
+    @torch.no_grad()
+    def fork_slot(self, src: int, dst: int) -> None:
+        """Prefix sharing (ragged sessions, ``kv_layout="paged"``): the empty slot ``dst`` becomes a copy of sequence
+        ``src`` without prefilling or storing the common prefix again -- it takes ``src``'s length, shares every full
+        page below it by reference and gets a private copy of the partial last page (:meth:`KVCache.fork`).  Decode
+        ``dst`` like any slot afterwards: feed it the token that follows the prefix.  ``RuntimeError`` if the pool has
+        no page for the copy; nothing has changed then."""
+        assert self.ragged, "slots need DecodeSession(..., ragged=True)"
+        if not self.cache.paged:
+            raise ValueError("fork_slot needs kv_layout='paged': slabs cannot share rows")
+        self.cache.fork(src, dst)
 
     @torch.no_grad()
     def prefill_slot(self, b: int, ids: Tensor) -> Tensor:
@@ -585,6 +824,7 @@ class DecodeSession:
         c = self.cache
         cur = [c._len[r] for r in rows]
         assert all(p + x <= self.max_len for p, x in zip(cur, n)), "KV cache full"
+        c.reserve(rows, [p + x for p, x in zip(cur, n)])
         ids = ids[:, : max(n)]
         B, T = ids.shape
         G = self.H // self.Hkv
@@ -798,11 +1038,17 @@ class DecodeSession:
                              st["params"][3])
         st["rng"][1:].add_(1)
         made = 1  # tokens sampled per row
+        upto = 0  # a paged cache has pages for the first `upto` fed tokens of every row
         while made < max_new_tokens:
             if eos >= 0 and made % sync_every == 0:  # the only host sync of the loop
                 done = st["done"] != 0 if as_list else (st["out"][:, :made] == eos).any(1)
                 if bool(done.all()):
                     break
+            if made > upto:
+                # the host does not know which rows have finished: every row gets the pages of the next sync_every
+                # tokens (at most one page too many each), before the replays that write them
+                upto = made - 1 + sync_every
+                self.cache.reserve(range(B), [x + upto for x in n])
             self._device_step(st)
             made += 1
         out = st["out"][:, :made].cpu()
@@ -816,6 +1062,7 @@ class DecodeSession:
                 c._len[b] = n[b] + min(first[b], made - 1)
             if self._step is not None:
                 self._step_host = [int(f >= made) for f in first]
+            c.release(range(B), c._len)  # (pages reserved ahead for rows that finished early)
             return [torch.cat([p, out[b, : min(first[b] + 1, made)].to(self.device, p.dtype)])
                     for b, p in enumerate(prompts)]
         # tensor prompt: keep the steps up to the one at which every row had emitted EOS; the replays past it (up to
@@ -823,6 +1070,7 @@ class DecodeSession:
         keep = min(max(first) + 1, made)
         c.pos.fill_(n[0] + keep - 1)
         c._len[:] = [n[0] + keep - 1] * B
+        c.release(range(B), c._len)
         return torch.cat([ids, out[:, :keep].to(self.device, ids.dtype)], 1)
 
     # ------------------------------------------------------------------ HIP path

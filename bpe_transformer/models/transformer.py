@@ -234,6 +234,8 @@ class TransformerLM(nn.Module):
         kv_dtype: str = "bf16",
         weight_dtype: str = "bf16",
         prompt_lookup: "int | tuple[int, int] | None" = None,
+        kv_layout: str = "slab",
+        num_pages: int | None = None,
     ) -> Tensor:
         """Autoregressive sampling (temperature, top-k, nucleus).  ``prompt``: ``[S]`` or ``[B, S]``.
 
@@ -265,6 +267,12 @@ class TransformerLM(nn.Module):
         is that of this call on a model whose projection weights are the dequantised rows.  It needs the KV-cache
         path and is not yet supported together with ``draft_model`` (``ValueError``).
 
+        ``kv_layout="paged"`` keeps the KV cache as a pool of 256-token pages behind a block table
+        (``DecodeSession(..., kv_layout="paged", num_pages=...)``): a sequence holds the pages it uses, not its
+        worst-case context, and the output is that of the slab cache, bit for bit.  ``num_pages`` sizes the pool
+        (default: enough for every sequence at full length; a pool that runs out raises ``RuntimeError``).  It needs the
+        KV-cache path and is not yet supported together with ``draft_model`` or ``prompt_lookup`` (``ValueError``).
+
         ``prompt_lookup=n_hi`` (or ``(n_hi, n_lo)``; an int means ``n_lo = 1``) turns on speculative decoding without
         a draft model (:class:`~bpe_transformer.models.generation.PromptLookupSession`): every round proposes the
         ``num_draft_tokens`` tokens that followed the most recent earlier occurrence of the last ``n_lo .. n_hi``
@@ -275,6 +283,13 @@ class TransformerLM(nn.Module):
         assert sampler in ("host", "device"), "sampler: 'host' or 'device'"
         if kv_dtype not in ("bf16", "fp8"):
             raise ValueError(f"kv_dtype: 'bf16' or 'fp8', got {kv_dtype!r}")
+        if kv_layout not in ("slab", "paged"):
+            raise ValueError(f"kv_layout: 'slab' or 'paged', got {kv_layout!r}")
+        if num_pages is not None and kv_layout != "paged":
+            raise ValueError("num_pages needs kv_layout='paged'")
+        if kv_layout != "slab" and (draft_model is not None or prompt_lookup is not None):
+            raise ValueError(f"kv_layout={kv_layout!r} with {'draft_model' if draft_model is not None else 'prompt_lookup'}"
+                             " is not supported yet: speculative decoding runs on the slab cache only")
         if weight_dtype not in ("bf16", "fp8"):
             raise ValueError(f"weight_dtype: 'bf16' or 'fp8', got {weight_dtype!r}")
         if prompt_lookup is not None:
@@ -306,11 +321,13 @@ class TransformerLM(nn.Module):
                 from .generation import DecodeSession
 
                 sess = DecodeSession(self, len(prompt), max_len=longest + max_new_tokens, ragged=True,
-                                     kv_dtype=kv_dtype, weight_dtype=weight_dtype)
+                                     kv_dtype=kv_dtype, weight_dtype=weight_dtype, kv_layout=kv_layout,
+                                     num_pages=num_pages)
                 return sess.generate(list(prompt), max_new_tokens, temperature, top_p, eos_token_id, generator, **kw)
             # without the cache: one sequence at a time through the loop below (which stops at its EOS)
             return [self.generate(p.reshape(-1), max_new_tokens, temperature, top_p, eos_token_id, generator, use_cache,
-                                  kv_dtype=kv_dtype, weight_dtype=weight_dtype, **kw) for p in prompt]
+                                  kv_dtype=kv_dtype, weight_dtype=weight_dtype, kv_layout=kv_layout,
+                                  num_pages=num_pages, **kw) for p in prompt]
         squeeze = prompt.dim() == 1
         ids = prompt.unsqueeze(0) if squeeze else prompt
         self._fence(self)  # the decode session packs / reads every weight up front
@@ -318,7 +335,7 @@ class TransformerLM(nn.Module):
             from .generation import DecodeSession
 
             sess = DecodeSession(self, ids.shape[0], max_len=ids.shape[1] + max_new_tokens, kv_dtype=kv_dtype,
-                                 weight_dtype=weight_dtype)
+                                 weight_dtype=weight_dtype, kv_layout=kv_layout, num_pages=num_pages)
             out = sess.generate(ids, max_new_tokens, temperature, top_p, eos_token_id, generator, **kw)
             return out[0] if squeeze else out
         assert sampler == "host" or max_new_tokens <= 0, "sampler='device' needs the KV-cache path (use_cache, and " \
@@ -327,6 +344,8 @@ class TransformerLM(nn.Module):
             "prompt + max_new_tokens within context_length)"
         assert weight_dtype == "bf16" or max_new_tokens <= 0, "weight_dtype='fp8' needs the KV-cache path (use_cache, " \
             "and prompt + max_new_tokens within context_length)"
+        assert kv_layout == "slab" or max_new_tokens <= 0, "kv_layout='paged' needs the KV-cache path (use_cache, and " \
+            "prompt + max_new_tokens within context_length)"
         for _ in range(max_new_tokens):
             ctx = ids[:, -self.context_length :]
             # (sampling is not document-masked: hidden_states takes explicit bounds only, never doc_mask_token)

@@ -47,6 +47,15 @@
 //   cache_attn_kernel<64 / 128, Fp8Cache>   VGPRs 122 / 184   SGPRs 52 / 54   LDS 25104 / 49680   waves/SIMD 4 / 2
 //     (flash_attn_cache.hip)
 // The format's scale loads and multiplies exist only in the Fp8Cache instantiations (`if constexpr`).
+// Paged layout (kv_cache.h PagedLayout; the rows above are the SlabLayout instantiations, unchanged by it).  LDS and
+// scratch as the slab twin; no paged instantiation loses a wave per SIMD against its twin:
+//   decode_attn_kernel<64, MR, Bf16Cache, PagedLayout>   VGPRs 90 / 107 / 122 / 180   SGPRs 48 / 51 / 51 / 56   waves/SIMD 5 / 4 / 4 / 2
+//   decode_attn_kernel<128, MR, Bf16Cache, PagedLayout>  VGPRs 154 / 168 / 200 / 242  SGPRs 64 / 67 / 72 / 67   waves/SIMD 3 / 3 / 2 / 2
+//   decode_attn_kernel<64, MR, Fp8Cache, PagedLayout>    VGPRs 60 / 80 / 96 / 180     SGPRs 48 / 51 / 51 / 56   waves/SIMD 8 / 6 / 5 / 2
+//   decode_attn_kernel<128, MR, Fp8Cache, PagedLayout>   VGPRs 92 / 110 / 118 / 180   SGPRs 64 / 67 / 72 / 67   waves/SIMD 5 / 4 / 4 / 2
+//   kv_append_kernel<PagedLayout> VGPRs 42, SGPRs 72   kv_append_fp8_kernel<PagedLayout> VGPRs 42, SGPRs 83   (8 waves)
+//   cache_attn_kernel<64 / 128, Bf16Cache, PagedLayout>  VGPRs 118 / 176   SGPRs 48 / 47   waves/SIMD 4 / 2
+//   cache_attn_kernel<64 / 128, Fp8Cache, PagedLayout>   VGPRs 122 / 184   SGPRs 60 / 62   waves/SIMD 4 / 2
 #include "kv_cache.h"
 #include "kernels.h"
 
@@ -64,12 +73,15 @@ constexpr int CH = 256;  // keys per chunk (= threads per workgroup)
 // Fmt (kv_cache.h) is the cache format; Ks / Vs are read only where it has scales (null otherwise).  Both formats
 // run the same floating-point operations in the same order on the unpacked values; a key's scale multiplies its
 // finished score, a value's scale its probability, and no bf16 instruction sees either.
-template <int D, int MR, class Fmt>
+// Lay (kv_cache.h) is the cache layout.  Paged: Kc / Vc (Ks / Vs) are the pools, chunk `split` of sequence b is the
+// page table[b, split] (clamped into the pool), and everything after `rowbase` is the slab kernel's code.
+template <int D, int MR, class Fmt, class Lay = SlabLayout>
 __global__ void __launch_bounds__(256) decode_attn_kernel(const __bf16* __restrict__ q, const void* __restrict__ Kc,
                                                           const void* __restrict__ Vc, const float* __restrict__ Ks,
                                                           const float* __restrict__ Vs, float* __restrict__ part,
                                                           const int* __restrict__ pos, int pstride, int H, int Hkv,
-                                                          int Lmax, int nsplit, float scale, int T) {
+                                                          int Lmax, int nsplit, float scale, int T, Lay lay) {
+    static_assert(CH == KV_PAGE, "a chunk is one page");
     typedef typename Fmt::elem elem;
     typedef typename Fmt::KVec KVec;
     typedef typename Fmt::VVec VVec;
@@ -100,7 +112,9 @@ __global__ void __launch_bounds__(256) decode_attn_kernel(const __bf16* __restri
         return;
     }
     const int n = min(CH, L - s0);
-    const long rowbase = (long)bk * Lmax + s0;  // first cache row of the chunk (its scale is at rowbase)
+    long rowbase;  // first cache row of the chunk (its scale is at rowbase)
+    if constexpr (Lay::paged) rowbase = ((long)lay.page_clamped(b, split) * Hkv + hk) * KV_PAGE;
+    else rowbase = (long)bk * Lmax + s0;
     const long kvbase = rowbase * D;            // and its first element
     // every K and V load of the chunk is issued up front (latency-bound at small batch: the q staging, the
     // score reductions and the softmax run while they are in flight): the key's row (and scale), the value scale of
@@ -243,17 +257,18 @@ __global__ void __launch_bounds__(D) decode_combine_kernel(const float* __restri
 }
 
 // KV-cache append into the bf16 cache: append_vec's (kv_cache.h) vector goes to q [B*T, H*D] or, roped K / plain V,
-// into the caches [B, Hkv, Lmax, D].
+// into the caches [B, Hkv, Lmax, D] (paged: the pools, through the block table).
+template <class Lay>
 __global__ void __launch_bounds__(256) kv_append_kernel(const __bf16* __restrict__ qkv, long ld,
                                                         __bf16* __restrict__ qo, __bf16* __restrict__ Kc,
                                                         __bf16* __restrict__ Vc, const float* __restrict__ cosT,
                                                         const float* __restrict__ sinT, const int* __restrict__ pos,
                                                         int pstride, int T, int H, int Hkv, int D, int Lmax,
-                                                        long total) {
+                                                        long total, Lay lay) {
     const int pshared = pos[0];
     for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
         AppendVec a;
-        if (!append_vec(a, idx, total, qkv, ld, cosT, sinT, pos, pstride, pshared, T, H, Hkv, D, Lmax)) continue;
+        if (!append_vec(a, idx, total, qkv, ld, cosT, sinT, pos, pstride, pshared, T, H, Hkv, D, Lmax, lay)) continue;
         __bf16* dst;
         if (a.hh < H) dst = qo + a.r * (long)H * D + (long)a.hh * D + a.d0;
         else dst = (a.hh < H + Hkv ? Kc : Vc) + a.row * D + a.d0;
@@ -266,6 +281,8 @@ __global__ void __launch_bounds__(256) kv_append_kernel(const __bf16* __restrict
 
 using namespace bpe::dec;
 
+int kv_page_rows() { return KV_PAGE; }
+
 int decode_attn_splits(int Lmax) { return (Lmax + CH - 1) / CH; }
 
 // T new tokens per sequence: the G * T query rows of a kv head share one workgroup (at most 8)
@@ -274,16 +291,16 @@ bool decode_attn_ok(int H, int Hkv, int D, int T) {
     return (D == 64 || D == 128) && Hkv > 0 && H % Hkv == 0 && T >= 1 && G >= 1 && G * T <= 8;
 }
 
-template <int D, class Fmt>
+template <int D, class Fmt, class Lay>
 static void launch_d(const void* q, const void* k, const void* v, const float* ks, const float* vs, float* part,
                      void* out, const int* pos, int pstride, int B, int T, int H, int Hkv, int Lmax, float scale,
-                     hipStream_t s) {
+                     Lay lay, hipStream_t s) {
     const int ns = decode_attn_splits(Lmax);
     const int grid = B * Hkv * ns;
     const int R = (H / Hkv) * T;
 #define DEC(MR)                                                                                                   \
-    decode_attn_kernel<D, MR, Fmt><<<grid, 256, 0, s>>>((const __bf16*)q, k, v, ks, vs, part, pos, pstride, H, Hkv, \
-                                                        Lmax, ns, scale, T)
+    decode_attn_kernel<D, MR, Fmt, Lay><<<grid, 256, 0, s>>>((const __bf16*)q, k, v, ks, vs, part, pos, pstride, H, \
+                                                             Hkv, Lmax, ns, scale, T, lay)
     if (R <= 1) DEC(1);
     else if (R <= 2) DEC(2);
     else if (R <= 4) DEC(4);
@@ -292,19 +309,35 @@ static void launch_d(const void* q, const void* k, const void* v, const float* k
     if (out != nullptr) decode_combine_kernel<D><<<B * T * H, D, 0, s>>>(part, (__bf16*)out, ns);
 }
 
+template <class Lay>
+static void launch_lay(const void* q, const void* k, const void* v, const float* ks, const float* vs, float* part,
+                       void* out, const int* pos, int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax,
+                       float scale, Lay lay, hipStream_t s) {
+    const auto launch = ks != nullptr ? (D == 64 ? launch_d<64, Fp8Cache, Lay> : launch_d<128, Fp8Cache, Lay>)
+                                      : (D == 64 ? launch_d<64, Bf16Cache, Lay> : launch_d<128, Bf16Cache, Lay>);
+    launch(q, k, v, ks, vs, part, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, lay, s);
+}
+
 void launch_decode_attn(const void* q, const void* k, const void* v, const float* ks, const float* vs, float* part,
                         void* out, const int* pos, int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax,
-                        float scale, hipStream_t s) {
-    const auto launch = ks != nullptr ? (D == 64 ? launch_d<64, Fp8Cache> : launch_d<128, Fp8Cache>)
-                                      : (D == 64 ? launch_d<64, Bf16Cache> : launch_d<128, Bf16Cache>);
-    launch(q, k, v, ks, vs, part, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, s);
+                        float scale, hipStream_t s, const KvPages& pg) {
+    if (pg.table != nullptr)
+        launch_lay(q, k, v, ks, vs, part, out, pos, pos_stride, B, T, H, Hkv, D, Lmax, scale,
+                   PagedLayout{pg.table, pg.NB, pg.P}, s);
+    else launch_lay(q, k, v, ks, vs, part, out, pos, pos_stride, B, T, H, Hkv, D, Lmax, scale, SlabLayout{}, s);
 }
 
 void launch_kv_append(const void* qkv, long ld, void* qo, void* Kc, void* Vc, const float* cosT, const float* sinT,
-                      const int* pos, int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax, hipStream_t s) {
+                      const int* pos, int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax, hipStream_t s,
+                      const KvPages& pg) {
     const long total = (long)B * T * (H + 2 * Hkv) * (D / 8);
     const long want = (total + 255) / 256;
     const int grid = (int)(want < 8192 ? want : 8192);
-    kv_append_kernel<<<grid, 256, 0, s>>>((const __bf16*)qkv, ld, (__bf16*)qo, (__bf16*)Kc, (__bf16*)Vc, cosT, sinT,
-                                          pos, pos_stride, T, H, Hkv, D, Lmax, total);
+    if (pg.table != nullptr)
+        kv_append_kernel<<<grid, 256, 0, s>>>((const __bf16*)qkv, ld, (__bf16*)qo, (__bf16*)Kc, (__bf16*)Vc, cosT,
+                                              sinT, pos, pos_stride, T, H, Hkv, D, Lmax, total,
+                                              PagedLayout{pg.table, pg.NB, pg.P});
+    else
+        kv_append_kernel<<<grid, 256, 0, s>>>((const __bf16*)qkv, ld, (__bf16*)qo, (__bf16*)Kc, (__bf16*)Vc, cosT,
+                                              sinT, pos, pos_stride, T, H, Hkv, D, Lmax, total, SlabLayout{});
 }

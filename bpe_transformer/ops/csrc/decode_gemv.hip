@@ -9,7 +9,8 @@
 //             1: y[:, j] = silu(g_j) * u_j over [W1; W3]    (SwiGLU; rows j and F + j in one wave)
 //             2: fused-QKV with RoPE at the device-side position and the K / V cache write (rows n, n + 1 of
 //                a rotation pair in one wave) -- replaces the separate kv_append launch.  The position is shared
-//                by the batch or one per row (GemvArgs::pos_stride; row m = sequence m).
+//                by the batch or one per row (GemvArgs::pos_stride; row m = sequence m).  The cache is the slabs
+//                or a paged pool behind a block table (GemvArgs::pages, kv_cache.h; cache_elem below).
 // Rounding matches the training kernels exactly (bf16 residual sum, (s * rstd) * g, bf16 GEMM outputs before
 // SwiGLU / RoPE), so decode logits agree with the model's forward pass.
 //
@@ -140,7 +141,22 @@ __device__ __forceinline__ void gemv_prologue_rows(const GemvArgs& a, u16* hs, i
 // RAG (epilogue 2 only): one position per row (GemvArgs::pos_stride == 1).  A template switch, so that the
 // shared-position instantiation is the code it was before positions could differ.  W8: e4m3 weight rows with a
 // scale each (the header states the scheme); likewise a switch, and the bf16 instantiations are the code they were.
-template <int MM, int EPI, bool RAG = false, bool W8 = false>
+// The cache element (m, hk, p, d) of epilogue 2, p < Lmax: the slab's, or (PG, GemvArgs::pages) the pool's through the
+// block table -- -1 where nothing may be written: a negative position, or a table entry that is no page of the pool.
+template <bool PG>
+__device__ __forceinline__ long cache_elem(const GemvArgs& a, int m, int hk, int p, int d) {
+    if constexpr (PG) {
+        if (p < 0) return -1;
+        const kvc::PagedLayout lay{a.pages.table, a.pages.NB, a.pages.P};
+        const long row = lay.row(m, hk, a.Hkv, p);
+        return row < 0 ? -1 : row * a.D + d;
+    } else {
+        return (((long)m * a.Hkv + hk) * a.Lmax + p) * a.D + d;
+    }
+}
+
+// PG (epilogue 2 only): the caches are the pools of a paged cache; a switch like RAG and W8.
+template <int MM, int EPI, bool RAG = false, bool W8 = false, bool PG = false>
 __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
     typedef Wt<W8> WT;
     extern __shared__ __attribute__((aligned(16))) u16 hs[];  // [MM][K] normalized input rows (bf16)
@@ -249,7 +265,7 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
                     const int pm = a.pos[m];
                     const float me = bf2f(f2bf(acc[m])), pa = bf2f(f2bf(other[m]));
                     float v = me;
-                    if (rot && pm < a.Lmax) {  // a dropped row (pm >= Lmax) may be past the table: q unspecified
+                    if (rot && pm < a.Lmax && (!PG || pm >= 0)) {  // a dropped row (pm >= Lmax) may be past the table: q unspecified
                         const float cm = a.cosT[(long)pm * (D / 2) + d / 2], sm = a.sinT[(long)pm * (D / 2) + d / 2];
                         v = (d & 1) ? pa * sm + me * cm : me * cm - pa * sm;
                     }
@@ -259,7 +275,8 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
                         const bool isk = hh < H + Hkv;
                         const int hk = isk ? hh - H : hh - H - Hkv;
                         u16* cache = reinterpret_cast<u16*>(isk ? a.kc : a.vc);
-                        cache[(((long)m * Hkv + hk) * a.Lmax + pm) * D + d] = o;
+                        const long e = cache_elem<PG>(a, m, hk, pm, d);
+                        if (!PG || e >= 0) cache[e] = o;
                     }
                 }
             }
@@ -267,7 +284,7 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
         }
         const int p = a.pos[0];
         float c = 1.f, s = 0.f;
-        if (rot && valid) {
+        if (rot && valid && (!PG || (p >= 0 && p < a.Lmax))) {
             c = a.cosT[(long)p * (D / 2) + d / 2];
             s = a.sinT[(long)p * (D / 2) + d / 2];
         }
@@ -282,7 +299,8 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
                     const bool isk = hh < H + Hkv;
                     const int hk = isk ? hh - H : hh - H - Hkv;
                     u16* cache = reinterpret_cast<u16*>(isk ? a.kc : a.vc);
-                    cache[(((long)m * Hkv + hk) * a.Lmax + p) * D + d] = o;
+                    const long e = cache_elem<PG>(a, m, hk, p, d);
+                    if (!PG || e >= 0) cache[e] = o;
                 }
             }
     }
@@ -299,7 +317,7 @@ __global__ void __launch_bounds__(256) gemv_kernel(const GemvArgs a) {
 // tokens at one k would otherwise hit the same banks).
 constexpr int MF_PF = 8;  // k-steps (32 each) of W in flight per wave
 
-template <int EPI, bool RAG = false, bool W8 = false>
+template <int EPI, bool RAG = false, bool W8 = false, bool PG = false>
 __global__ void __launch_bounds__(256) gemv_mfma_kernel(const GemvArgs a) {
     typedef Wt<W8> WT;
     extern __shared__ __attribute__((aligned(16))) u16 hs[];  // [M][K + 8] input rows, then float red[4][16][17]
@@ -406,7 +424,7 @@ __global__ void __launch_bounds__(256) gemv_mfma_kernel(const GemvArgs a) {
         const float me = bf2f(f2bf(c)), pa = bf2f(f2bf(cp));
         float v = me;
         // (with one position per sequence a row at p >= Lmax is dropped and may be past the table: q unspecified)
-        if (a.cosT != nullptr && hh < H + Hkv && (!RAG || p < a.Lmax)) {
+        if (a.cosT != nullptr && hh < H + Hkv && (!RAG || p < a.Lmax) && (!PG || (p >= 0 && p < a.Lmax))) {
             const float cs = a.cosT[(long)p * (D / 2) + d / 2], sn = a.sinT[(long)p * (D / 2) + d / 2];
             v = (d & 1) ? pa * sn + me * cs : me * cs - pa * sn;
         }
@@ -416,7 +434,8 @@ __global__ void __launch_bounds__(256) gemv_mfma_kernel(const GemvArgs a) {
             const bool isk = hh < H + Hkv;
             const int hk = isk ? hh - H : hh - H - Hkv;
             u16* cache = reinterpret_cast<u16*>(isk ? a.kc : a.vc);
-            cache[(((long)m * Hkv + hk) * a.Lmax + p) * D + d] = o;
+            const long e = cache_elem<PG>(a, m, hk, p, d);
+            if (!PG || e >= 0) cache[e] = o;
         }
     }
 }
@@ -459,20 +478,20 @@ bool gemv_ok(int M, int K) {
     return gemv_lds_bytes(M, K) <= 160 * 1024 || mfma_fits(M, K);
 }
 
-template <int MM, int EPI, bool RAG, bool W8>
+template <int MM, int EPI, bool RAG, bool W8, bool PG>
 static void launch_mm(const GemvArgs& a, int grid, size_t lds, hipStream_t s) {
     if (lds > 64 * 1024)
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_kernel<MM, EPI, RAG, W8>),
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_kernel<MM, EPI, RAG, W8, PG>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    gemv_kernel<MM, EPI, RAG, W8><<<grid, 256, lds, s>>>(a);
+    gemv_kernel<MM, EPI, RAG, W8, PG><<<grid, 256, lds, s>>>(a);
 }
 
-template <int EPI, bool RAG, bool W8>
+template <int EPI, bool RAG, bool W8, bool PG = false>
 static void launch_epi(const GemvArgs& a, int grid, size_t lds, hipStream_t s) {
-    if (a.M <= 1) launch_mm<1, EPI, RAG, W8>(a, grid, lds, s);
-    else if (a.M <= 2) launch_mm<2, EPI, RAG, W8>(a, grid, lds, s);
-    else if (a.M <= 4) launch_mm<4, EPI, RAG, W8>(a, grid, lds, s);
-    else launch_mm<8, EPI, RAG, W8>(a, grid, lds, s);
+    if (a.M <= 1) launch_mm<1, EPI, RAG, W8, PG>(a, grid, lds, s);
+    else if (a.M <= 2) launch_mm<2, EPI, RAG, W8, PG>(a, grid, lds, s);
+    else if (a.M <= 4) launch_mm<4, EPI, RAG, W8, PG>(a, grid, lds, s);
+    else launch_mm<8, EPI, RAG, W8, PG>(a, grid, lds, s);
 }
 
 // decode rows from which the MFMA variant runs (BPE_GEMV_MFMA_MIN_M, default 2)
@@ -484,26 +503,32 @@ static int mfma_min_m() {
     return v;
 }
 
-template <int EPI, bool RAG, bool W8>
+template <int EPI, bool RAG, bool W8, bool PG = false>
 static void launch_mfma(const GemvArgs& a, int grid, hipStream_t s) {
     const size_t lds = gemv_mfma_lds_bytes(a.M, a.K);
     if (lds > 64 * 1024)
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_mfma_kernel<EPI, RAG, W8>),
+        hipFuncSetAttribute(reinterpret_cast<const void*>(&gemv_mfma_kernel<EPI, RAG, W8, PG>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    gemv_mfma_kernel<EPI, RAG, W8><<<grid, 256, lds, s>>>(a);
+    gemv_mfma_kernel<EPI, RAG, W8, PG><<<grid, 256, lds, s>>>(a);
 }
 
 template <bool W8>
 static void launch_w(const GemvArgs& a, int epi, hipStream_t s) {
     if ((a.M >= mfma_min_m() || a.M > 8 || gemv_lds_bytes(a.M, a.K) > 160 * 1024) && mfma_fits(a.M, a.K)) {
+        const bool pg = a.pages.table != nullptr;
         if (epi == 1) launch_mfma<1, false, W8>(a, (a.N / 2 + 7) / 8, s);
+        else if (epi == 2 && pg && a.pos_stride != 0) launch_mfma<2, true, W8, true>(a, (a.N + 15) / 16, s);
+        else if (epi == 2 && pg) launch_mfma<2, false, W8, true>(a, (a.N + 15) / 16, s);
         else if (epi == 2 && a.pos_stride != 0) launch_mfma<2, true, W8>(a, (a.N + 15) / 16, s);
         else if (epi == 2) launch_mfma<2, false, W8>(a, (a.N + 15) / 16, s);
         else launch_mfma<0, false, W8>(a, (a.N + 15) / 16, s);
         return;
     }
     const size_t lds = gemv_lds_bytes(a.M, a.K);
+    const bool pg = a.pages.table != nullptr;
     if (epi == 1) launch_epi<1, false, W8>(a, (a.N / 2 + 7) / 8, lds, s);
+    else if (epi == 2 && pg && a.pos_stride != 0) launch_epi<2, true, W8, true>(a, (a.N + 15) / 16, lds, s);
+    else if (epi == 2 && pg) launch_epi<2, false, W8, true>(a, (a.N + 15) / 16, lds, s);
     else if (epi == 2 && a.pos_stride != 0) launch_epi<2, true, W8>(a, (a.N + 15) / 16, lds, s);
     else if (epi == 2) launch_epi<2, false, W8>(a, (a.N + 15) / 16, lds, s);
     else launch_epi<0, false, W8>(a, (a.N + 15) / 16, lds, s);

@@ -150,11 +150,55 @@ template <int D> struct Request<D, kvc::Fp8Cache> {
     }
 };
 
-template <int D, class C>
+// The same requests over the paged cache (kv_cache.h PagedLayout; Kc / Vc / scales are the pools).  Tile t lies in
+// page t / 4 of the sequence: the resources start at that page's (page, hk) block of KV_PAGE rows, the tile's offset
+// inside it is (t % 4) * 64 rows, and the extent is min(KV_PAGE, L - KV_PAGE (t / 4)) rows, so rows from L on still
+// read as zeros, bytes and scales.  `pg` is the page id, read by the kernel once per page (wave-uniform, clamped).
+template <int D, class C> struct PagedRequest;
+
+template <int D> struct PagedRequest<D, kvc::Bf16Cache> {
+    static constexpr int RB = 2 * D, TILE = 64 * RB;
+    const __bf16 *k, *v;
+    int hk, Hkv, L, wu;
+    char* smem;
+    DmaVoff<4, RB> vo;
+    __device__ __forceinline__ PagedRequest(const u16* kp, const u16* vp, int hk_, int Hkv_, int L_, char* lds,
+                                            Scales<kvc::Bf16Cache>, int w, int l)
+        : k((const __bf16*)kp), v((const __bf16*)vp), hk(hk_), Hkv(Hkv_), L(L_), wu(w), smem(lds),
+          vo(dma_voff<4, RB>(D, w, l)) {}
+    __device__ __forceinline__ void operator()(int n0, int buf, int pg) const {
+        const long off = ((long)pg * Hkv + hk) * kvc::KV_PAGE * D;
+        const int nbytes = min(kvc::KV_PAGE, L - n0 / kvc::KV_PAGE * kvc::KV_PAGE) * RB;
+        dma_tile64_buf<4, RB>(k + off, nbytes, vo, n0 % kvc::KV_PAGE, D, smem + buf * TILE, wu);
+        dma_tile64_buf<4, RB>(v + off, nbytes, vo, n0 % kvc::KV_PAGE, D, smem + (2 + buf) * TILE, wu);
+    }
+};
+
+template <int D> struct PagedRequest<D, kvc::Fp8Cache> {
+    static constexpr int TILE = 64 * 2 * D;
+    const unsigned char *k, *v;
+    const float *ks, *vs;  // the pools' scales
+    int hk, Hkv, L, wu, l;
+    char* st;
+    __device__ __forceinline__ PagedRequest(const unsigned char* kp, const unsigned char* vp, int hk_, int Hkv_, int L_,
+                                            char* lds, Scales<kvc::Fp8Cache> sc, int w, int lane)
+        : k(kp), v(vp), ks(sc.k), vs(sc.v), hk(hk_), Hkv(Hkv_), L(L_), wu(w), l(lane), st(lds + 2 * TILE) {}
+    __device__ __forceinline__ void operator()(int n0, int, int pg) const {
+        const long row0 = ((long)pg * Hkv + hk) * kvc::KV_PAGE;
+        const int rows = min(kvc::KV_PAGE, L - n0 / kvc::KV_PAGE * kvc::KV_PAGE), r0 = n0 % kvc::KV_PAGE;
+        dma_bytes64_buf<4, D>(k + row0 * D, rows * D, r0, st, wu, l);
+        dma_bytes64_buf<4, D>(v + row0 * D, rows * D, r0, st + TILE / 2, wu, l);
+        if (wu == 0) dma_scales64_buf(ks + row0, rows * 4, r0, st + TILE, l);
+        if (wu == 1) dma_scales64_buf(vs + row0, rows * 4, r0, st + TILE + 256, l);
+    }
+};
+
+// Lay (kv_cache.h): the cache layout.  The slab instantiations take an empty `lay` and are the code they were.
+template <int D, class C, class Lay = kvc::SlabLayout>
 __global__ void __launch_bounds__(256, 2)
 cache_attn_kernel(const __bf16* __restrict__ Q, const typename C::elem* __restrict__ Kc,
                   const typename C::elem* __restrict__ Vc, __bf16* __restrict__ O, const int* __restrict__ pos,
-                  int pstride, int H, int Hkv, int Lmax, int T, float scale_log2, int nqb, Scales<C> sc) {
+                  int pstride, int H, int Hkv, int Lmax, int T, float scale_log2, int nqb, Scales<C> sc, Lay lay) {
     constexpr int RB = D * 2;      // bytes per LDS row
     constexpr int TILE = 64 * RB;  // bytes per 64-key tile
     constexpr int KS = D / 16;     // k-steps over the head dim
@@ -203,7 +247,22 @@ cache_attn_kernel(const __bf16* __restrict__ Q, const typename C::elem* __restri
     if constexpr (C::scaled) {
         if (tid == 0) *vbad = 0x7fffffff;
     }
-    const Request<D, C> request{kbase, vbase, sbytes, smem, sc, (long)bk * Lmax, L * 4, wu, l};
+    // paged: the page id of the tile being requested, read from the table when a request enters a new page (n0 <= L - 1
+    // < Lmax <= NB * KV_PAGE, so the entry exists; wave-uniform: b and n0 are)
+    [[maybe_unused]] int pg = 0;
+    const auto make_request = [&] {
+        if constexpr (Lay::paged) return PagedRequest<D, C>{Kc, Vc, hk, Hkv, L, smem, sc, wu, l};
+        else return Request<D, C>{kbase, vbase, sbytes, smem, sc, (long)bk * Lmax, L * 4, wu, l};
+    };
+    const auto req = make_request();
+    const auto request = [&](int n0, int buf) {
+        if constexpr (Lay::paged) {
+            if (n0 % kvc::KV_PAGE == 0) pg = __builtin_amdgcn_readfirstlane(lay.page_clamped(b, n0 / kvc::KV_PAGE));
+            req(n0, buf, pg);
+        } else {
+            req(n0, buf);
+        }
+    };
     request(0, 0);
 
     // Q fragments (B operand of S^T = K.Q^T), softmax scale * log2(e) folded in
@@ -354,31 +413,44 @@ bool cache_attn_ok(int H, int Hkv, int D, int T, int Lmax) {
     return cache_shape_ok(H, Hkv, D, T, Lmax) && (long)Lmax * D * 2 < (1L << 31);
 }
 
+// (A paged cache's extents are those of one page, 256 rows: the slab bounds, which a pool always meets, still apply
+// to Lmax as the range of the row indices.)
 // The e4m3 cache: the 32-bit extents are Lmax * D bytes of a slab and Lmax * 4 bytes of its scales.
 bool cache_attn_fp8_ok(int H, int Hkv, int D, int T, int Lmax) {
     return cache_shape_ok(H, Hkv, D, T, Lmax) && (long)Lmax * D < (1L << 31) && (long)Lmax * 4 < (1L << 31);
 }
 
-template <int D, class C>
-static void cache_launch(const void* q, const void* k, const void* v, cache::Scales<C> sc, void* out, const int* pos,
-                         int pstride, int B, int T, int H, int Hkv, int Lmax, float scale, hipStream_t s) {
+template <int D, class C, class Lay>
+static void cache_launch_lay(const void* q, const void* k, const void* v, cache::Scales<C> sc, void* out,
+                             const int* pos, int pstride, int B, int T, int H, int Hkv, int Lmax, float scale, Lay lay,
+                             hipStream_t s) {
     typedef const typename C::elem* cptr;
     const int nqb = ((H / Hkv) * T + 127) / 128;
-    cache::cache_attn_kernel<D, C><<<nqb * B * Hkv, 256, cache::lds_bytes<D, C>(), s>>>(
-        (const __bf16*)q, (cptr)k, (cptr)v, (__bf16*)out, pos, pstride, H, Hkv, Lmax, T, scale * LOG2E, nqb, sc);
+    cache::cache_attn_kernel<D, C, Lay><<<nqb * B * Hkv, 256, cache::lds_bytes<D, C>(), s>>>(
+        (const __bf16*)q, (cptr)k, (cptr)v, (__bf16*)out, pos, pstride, H, Hkv, Lmax, T, scale * LOG2E, nqb, sc, lay);
+}
+
+template <int D, class C>
+static void cache_launch(const void* q, const void* k, const void* v, cache::Scales<C> sc, void* out, const int* pos,
+                         int pstride, int B, int T, int H, int Hkv, int Lmax, float scale, const KvPages& pg,
+                         hipStream_t s) {
+    if (pg.table != nullptr)
+        cache_launch_lay<D, C>(q, k, v, sc, out, pos, pstride, B, T, H, Hkv, Lmax, scale,
+                               kvc::PagedLayout{pg.table, pg.NB, pg.P}, s);
+    else cache_launch_lay<D, C>(q, k, v, sc, out, pos, pstride, B, T, H, Hkv, Lmax, scale, kvc::SlabLayout{}, s);
 }
 
 void launch_cache_attn(const void* q, const void* k, const void* v, void* out, const int* pos, int pos_stride, int B,
-                       int T, int H, int Hkv, int D, int Lmax, float scale, hipStream_t s) {
+                       int T, int H, int Hkv, int D, int Lmax, float scale, hipStream_t s, const KvPages& pg) {
     const cache::Scales<kvc::Bf16Cache> none{};
-    if (D == 64) cache_launch<64, kvc::Bf16Cache>(q, k, v, none, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, s);
-    else cache_launch<128, kvc::Bf16Cache>(q, k, v, none, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, s);
+    if (D == 64) cache_launch<64, kvc::Bf16Cache>(q, k, v, none, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, pg, s);
+    else cache_launch<128, kvc::Bf16Cache>(q, k, v, none, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, pg, s);
 }
 
 void launch_cache_attn_fp8(const void* q, const void* k8, const void* v8, const float* ks, const float* vs, void* out,
                            const int* pos, int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax, float scale,
-                           hipStream_t s) {
+                           hipStream_t s, const KvPages& pg) {
     const cache::Scales<kvc::Fp8Cache> sc{ks, vs};
-    if (D == 64) cache_launch<64, kvc::Fp8Cache>(q, k8, v8, sc, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, s);
-    else cache_launch<128, kvc::Fp8Cache>(q, k8, v8, sc, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, s);
+    if (D == 64) cache_launch<64, kvc::Fp8Cache>(q, k8, v8, sc, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, pg, s);
+    else cache_launch<128, kvc::Fp8Cache>(q, k8, v8, sc, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, pg, s);
 }

@@ -144,30 +144,39 @@ struct FaArgs {
 // pos[b * pos_stride], i.e. pos_stride 0 = one position shared by the batch, 1 = one per sequence).
 // launch_decode_attn serves both cache formats: ks / vs null = bf16 K / V [B, Hkv, Lmax, D]; otherwise k / v are
 // e4m3 bytes of that shape with one power-of-two fp32 scale per row, ks / vs [B, Hkv, Lmax] (kv_fp8.hip).
+// Paged cache (kv_cache.h): with `table` set, k / v (ks / vs) are the pools [P, Hkv, 256, D] ([P, Hkv, 256]) and
+// table is the device int32 block table [B, NB], NB * 256 >= Lmax; null = the slabs above.
+struct KvPages {
+    const int* table = nullptr;
+    int NB = 0, P = 0;
+};
+int kv_page_rows();  // kvc::KV_PAGE (kv_cache.h, the one definition), for the bindings' shape checks
 int decode_attn_splits(int Lmax);
 bool decode_attn_ok(int H, int Hkv, int D, int T);
 void launch_decode_attn(const void* q, const void* k, const void* v, const float* ks, const float* vs, float* part,
                         void* out, const int* pos, int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax,
-                        float scale, hipStream_t s);
+                        float scale, hipStream_t s, const KvPages& pg = KvPages{});
 void launch_kv_append(const void* qkv, long ld, void* qo, void* Kc, void* Vc, const float* cosT, const float* sinT,
-                      const int* pos, int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax, hipStream_t s);
+                      const int* pos, int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax, hipStream_t s,
+                      const KvPages& pg = KvPages{});
 // kv_fp8.hip (the fp8 KV cache; the contract of launch_kv_append otherwise).  launch_kv_dequant writes rows
 // [0, min(pos + T, Lmax)) of every K and V slab as bf16 into ko / vo [B, Hkv, Lmax, D].
 void launch_kv_append_fp8(const void* qkv, long ld, void* qo, void* k8, void* v8, float* ks, float* vs,
                           const float* cosT, const float* sinT, const int* pos, int pos_stride, int B, int T, int H,
-                          int Hkv, int D, int Lmax, hipStream_t s);
+                          int Hkv, int D, int Lmax, hipStream_t s, const KvPages& pg = KvPages{});
 void launch_kv_dequant(const void* k8, const void* v8, const float* ks, const float* vs, void* ko, void* vo,
                        const int* pos, int pos_stride, int B, int T, int Hkv, int D, int Lmax, hipStream_t s);
 // flash_attn_cache.hip (flash prefill over the cache: T new tokens per sequence, any T; `pos` as above)
 bool cache_attn_ok(int H, int Hkv, int D, int T, int Lmax);
 void launch_cache_attn(const void* q, const void* k, const void* v, void* out, const int* pos, int pos_stride, int B,
-                       int T, int H, int Hkv, int D, int Lmax, float scale, hipStream_t s);
+                       int T, int H, int Hkv, int D, int Lmax, float scale, hipStream_t s,
+                       const KvPages& pg = KvPages{});
 // the same kernel over the fp8 cache (k8 / v8 e4m3 bytes, ks / vs their row scales): bit for bit launch_cache_attn on
 // what launch_kv_dequant writes
 bool cache_attn_fp8_ok(int H, int Hkv, int D, int T, int Lmax);
 void launch_cache_attn_fp8(const void* q, const void* k8, const void* v8, const float* ks, const float* vs, void* out,
                            const int* pos, int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax, float scale,
-                           hipStream_t s);
+                           hipStream_t s, const KvPages& pg = KvPages{});
 
 // decode_gemv.hip (M <= 16 token rows; epi 0 plain, 1 SwiGLU over [W1; W3], 2 fused QKV + RoPE + KV-cache write)
 struct GemvArgs {
@@ -192,6 +201,7 @@ struct GemvArgs {
     __bf16* vc;
     const float* part;  // optional prologue: x = merged decode-attention partials [M][H][nsplit][D + 2] (H, D)
     int nsplit;
+    KvPages pages;  // epi 2 only: kc / vc are the pools of a paged cache (table null: slabs)
 };
 size_t gemv_lds_bytes(int M, int K);
 bool gemv_ok(int M, int K);

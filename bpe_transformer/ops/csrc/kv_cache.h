@@ -8,6 +8,17 @@
 // register types of a key row and of a V slot, where a row starts, element d of either as fp32, and whether a row
 // carries a scale.  The two append kernels (kv_append_kernel in decode_attn.hip, kv_append_fp8_kernel in kv_fp8.hip)
 // share append_vec: which 8 values a thread handles, RoPE'd, and where they go.
+//
+// Beside the format there is the LAYOUT -- where cache row (b, kv head, position) lies -- as a second policy, SlabLayout
+// / PagedLayout below.  The slab is the [B, Hkv, Lmax, D] tensor above.  The paged cache is a pool of pages
+//   K / V [P, Hkv, KV_PAGE, D] (either format; fp8 scales [P, Hkv, KV_PAGE])
+// and an int32 block table [B, NB], NB * KV_PAGE >= Lmax: entry [b, j] is the pool page that holds positions
+// KV_PAGE * j .. KV_PAGE * j + KV_PAGE - 1 of sequence b, -1 where none is allocated.  KV_PAGE is decode_attn's chunk
+// and four of cache_attn's 64-key tiles, so a chunk is one page and a tile never straddles one: the indirection is
+// one table entry per chunk / per four tiles, and the arithmetic on the rows, and its order, is the slab kernels'.
+// The table is device data like pos, and no content of either may address outside the pool: a reader clamps the page
+// id into [0, P - 1] (page_clamped), a writer whose entry is outside [0, P) writes nothing (paged_row).  The layout
+// is a compile-time property: the slab instantiations take an empty argument and are the code they were.
 #pragma once
 #include "common.h"
 
@@ -16,6 +27,29 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 namespace bpe {
 namespace kvc {
+
+constexpr int KV_PAGE = 256;  // rows of a page (= dec::CH, a multiple of cache_attn's 64-key tile)
+
+struct SlabLayout {
+    static constexpr bool paged = false;
+};
+
+struct PagedLayout {
+    static constexpr bool paged = true;
+    const int* table;  // [B, NB]
+    int NB, P;         // table columns (NB * KV_PAGE >= Lmax), pages in the pool
+    // the page of positions KV_PAGE * j .. of sequence b for a reader, clamped into the pool (0 <= j < NB)
+    __device__ __forceinline__ int page_clamped(int b, int j) const {
+        return min(max(table[(long)b * NB + j], 0), P - 1);
+    }
+    // the pool row of position p (0 <= p < NB * KV_PAGE) of (sequence b, kv head hk) for a writer, or -1 where the
+    // table has no page in [0, P) for it
+    __device__ __forceinline__ long row(int b, int hk, int Hkv, int p) const {
+        const int pg = table[(long)b * NB + p / KV_PAGE];
+        if ((unsigned)pg >= (unsigned)P) return -1;
+        return ((long)pg * Hkv + hk) * KV_PAGE + p % KV_PAGE;
+    }
+};
 
 // two e4m3 bytes of `w` (the low or the high half) -> fp32 (v_cvt_pk_f32_fp8, exact)
 __device__ __forceinline__ f32x2 fp8x2(unsigned w, bool hi) {
@@ -66,7 +100,7 @@ struct Fp8Cache {
 // per sequence at positions *pos .. *pos+T-1; one thread per 16-byte vector (8 bf16) of a row; the rotation pairs
 // (2i, 2i+1) never straddle a vector.  Vector `idx` of `total` is head hh (q heads, then K heads, then V heads) of
 // token row r, elements d0 .. d0 + 7, roped where q or K (cosT null: no RoPE), and, where K or V, belongs to cache
-// row `row` = (b * Hkv + kv head) * Lmax + position.
+// row `row` = (b * Hkv + kv head) * Lmax + position (slab), or the pool row PagedLayout::row gives for it.
 struct AppendVec {
     u16x8 x;
     long r, row;
@@ -75,10 +109,13 @@ struct AppendVec {
 
 // -> false (a.x zero) when the thread has nothing to write: idx past the end, or the token's position at or past Lmax
 // (cache full: nothing is written past the end; per sequence, like the position itself).  `pshared` = pos[0].
+// Paged: also a negative position (pos is device data), and a K or V vector whose table entry is no page of the pool
+// (the D / 8 vectors of a row share the entry, so a row is written or dropped as a whole).
+template <class Lay = SlabLayout>
 __device__ __forceinline__ bool append_vec(AppendVec& a, long idx, long total, const __bf16* __restrict__ qkv, long ld,
                                            const float* __restrict__ cosT, const float* __restrict__ sinT,
                                            const int* __restrict__ pos, int pstride, int pshared, int T, int H, int Hkv,
-                                           int D, int Lmax) {
+                                           int D, int Lmax, const Lay& lay = Lay{}) {
     a.x = u16x8{};
     if (idx >= total) return false;
     const int dv = D / 8, W = (H + 2 * Hkv) * dv;
@@ -89,7 +126,16 @@ __device__ __forceinline__ bool append_vec(AppendVec& a, long idx, long total, c
     const int b = (int)(a.r / T);
     const int p = (pstride ? pos[b] : pshared) + (int)(a.r % T);
     if (p >= Lmax) return false;
-    a.row = ((long)b * Hkv + (a.hh < H + Hkv ? a.hh - H : a.hh - H - Hkv)) * Lmax + p;
+    if constexpr (Lay::paged) {
+        if (p < 0) return false;
+        a.row = 0;
+        if (a.hh >= H) {  // (a q vector has no cache row)
+            a.row = lay.row(b, a.hh < H + Hkv ? a.hh - H : a.hh - H - Hkv, Hkv, p);
+            if (a.row < 0) return false;
+        }
+    } else {
+        a.row = ((long)b * Hkv + (a.hh < H + Hkv ? a.hh - H : a.hh - H - Hkv)) * Lmax + p;
+    }
     a.x = *reinterpret_cast<const u16x8*>(qkv + a.r * ld + (long)a.hh * D + a.d0);
     if (a.hh < H + Hkv && cosT != nullptr) {
         const float* cs = cosT + (long)p * (D / 2) + a.d0 / 2;

@@ -1012,20 +1012,63 @@ void check_kv(const at::Tensor& k, const at::Tensor& v, const at::Tensor* ks, co
     TORCH_CHECK(v.sizes() == k.sizes(), op, ": k / v cache shapes differ");
 }
 
+// The geometry of the K cache of an op named `op`.  Without a block table it is the slab [B, Hkv, Lmax, D].  With one
+// (kv_cache.h: the paged cache) the tensor is the pool [P, Hkv, 256, D] -- and so are V and, for fp8, the scales [P,
+// Hkv, 256] -- the table is a contiguous device int32 [B, NB], and Lmax is `max_len` (0: NB * 256) with NB * 256 >=
+// Lmax.  dim0(B) is what dim 0 of the cache tensors must be (check_cache / check_cache8): the pool's P with a table,
+// and without one the batch `B` the caller runs -- a slab smaller than the batch is refused, never launched on.
+struct KvGeom {
+    int64_t B, Hkv, Lmax, D, P;
+    KvPages pg;
+    int64_t dim0(int64_t batch) const { return pg.table != nullptr ? P : batch; }
+};
+
+KvGeom kv_geom(const char* op, const at::Tensor& kc, const c10::optional<at::Tensor>& table, int64_t max_len) {
+    TORCH_CHECK(kc.dim() == 4, op, ": the k cache must be [B, Hkv, Lmax, D] (paged: the pool [P, Hkv, 256, D])");
+    KvGeom g{kc.size(0), kc.size(1), kc.size(2), kc.size(3), kc.size(0), KvPages{}};
+    if (!(table.has_value() && table->defined())) {
+        TORCH_CHECK(max_len == 0 || max_len == g.Lmax, op, ": max_len is the Lmax of a paged cache; a slab has its own");
+        return g;
+    }
+    const at::Tensor& t = *table;
+    check_cuda(t, "block_table");
+    TORCH_CHECK(t.scalar_type() == at::kInt && t.dim() == 2 && t.is_contiguous() && t.size(0) >= 1 && t.size(1) >= 1,
+                op, ": block_table must be a contiguous device int32 [B, NB] tensor");
+    const int64_t PAGE = kv_page_rows();
+    TORCH_CHECK(kc.size(2) == PAGE && kc.size(0) >= 1, op, ": with a block_table the caches are pools [P, Hkv, ", PAGE,
+                ", D]");
+    const int64_t P = kc.size(0), NB = t.size(1);
+    g.B = t.size(0);
+    g.Lmax = max_len > 0 ? max_len : NB * PAGE;
+    TORCH_CHECK(max_len >= 0 && NB * PAGE >= g.Lmax, op, ": block_table has ", NB, " pages per sequence, fewer than "
+                "max_len ", g.Lmax, " needs");
+    // 32-bit extents: page ids and table indices are ints, the page count of a row index times Hkv * 256 fits 2^62
+    TORCH_CHECK(P < (1LL << 31) && NB < (1LL << 23) && g.B * NB < (1LL << 31) && g.Hkv < (1LL << 16), op,
+                ": pool or block_table too large (P < 2^31, NB < 2^23, B * NB < 2^31)");
+    g.pg.table = t.data_ptr<int>();
+    g.pg.NB = (int)NB;
+    g.pg.P = (int)P;
+    return g;
+}
+
 // qkv [B*T, (H + 2*Hkv)*D] rows of T new tokens at positions *pos.. -> roped q [B*T, H*D]; K (roped) and V are
 // written into the caches at those positions -- as they are, or (ks / vs given) quantised row by row.
 at::Tensor kv_append_impl(const char* op, const at::Tensor& qkv, at::Tensor& kc, at::Tensor& vc, at::Tensor* ks,
                           at::Tensor* vs, const at::Tensor& cos, const at::Tensor& sin, const at::Tensor& pos,
-                          int64_t B, int64_t T, int64_t H, bool use_rope) {
-    TORCH_CHECK(kc.dim() == 4, op, ": the k cache must be [B, Hkv, Lmax, D]");
-    const int64_t Hkv = kc.size(1), Lmax = kc.size(2), D = kc.size(3);
+                          int64_t B, int64_t T, int64_t H, bool use_rope, const c10::optional<at::Tensor>& table,
+                          int64_t max_len) {
+    const KvGeom kg = kv_geom(op, kc, table, max_len);
+    TORCH_CHECK(kg.pg.table == nullptr || kg.B == B, op, ": block_table must have B (", B, ") rows");
+    TORCH_CHECK(kg.pg.table == nullptr || (B >= 1 && T >= 1 && kg.Lmax < (1LL << 30) && T < (1LL << 30)), op,
+                ": a paged cache needs B, T >= 1 and Lmax, T below 2^30");
+    const int64_t Hkv = kg.Hkv, Lmax = kg.Lmax, D = kg.D;
     if (ks != nullptr) {  // (a row's amax is reduced over the D / 8 lanes of one wave)
         TORCH_CHECK((D == 64 || D == 128) && Hkv > 0 && H % Hkv == 0, op, ": head dim 64/128, H multiple of Hkv");
     } else {
         TORCH_CHECK(D % 8 == 0 && Hkv > 0 && H % Hkv == 0, op, ": head dim multiple of 8, H multiple of Hkv");
     }
     check_qkv(qkv, B * T, (H + 2 * Hkv) * D, "qkv");
-    check_kv(kc, vc, ks, vs, B, Hkv, op);
+    check_kv(kc, vc, ks, vs, kg.dim0(B), Hkv, op);
     const int pstride = check_pos(pos, B);
     if (use_rope)
         TORCH_CHECK(cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
@@ -1038,23 +1081,26 @@ at::Tensor kv_append_impl(const char* op, const at::Tensor& qkv, at::Tensor& kc,
     if (ks != nullptr)
         launch_kv_append_fp8(qkv.data_ptr(), qkv.stride(0), q.data_ptr(), kc.data_ptr(), vc.data_ptr(),
                              ks->data_ptr<float>(), vs->data_ptr<float>(), c, sn, pos.data_ptr<int>(), pstride, (int)B,
-                             (int)T, (int)H, (int)Hkv, (int)D, (int)Lmax, cur_stream());
+                             (int)T, (int)H, (int)Hkv, (int)D, (int)Lmax, cur_stream(), kg.pg);
     else
         launch_kv_append(qkv.data_ptr(), qkv.stride(0), q.data_ptr(), kc.data_ptr(), vc.data_ptr(), c, sn,
                          pos.data_ptr<int>(), pstride, (int)B, (int)T, (int)H, (int)Hkv, (int)D, (int)Lmax,
-                         cur_stream());
+                         cur_stream(), kg.pg);
     return q;
 }
 
 at::Tensor kv_append(const at::Tensor& qkv, at::Tensor kc, at::Tensor vc, const at::Tensor& cos, const at::Tensor& sin,
-                     const at::Tensor& pos, int64_t B, int64_t T, int64_t H, bool use_rope) {
-    return kv_append_impl("kv_append", qkv, kc, vc, nullptr, nullptr, cos, sin, pos, B, T, H, use_rope);
+                     const at::Tensor& pos, int64_t B, int64_t T, int64_t H, bool use_rope,
+                     const c10::optional<at::Tensor>& block_table, int64_t max_len) {
+    return kv_append_impl("kv_append", qkv, kc, vc, nullptr, nullptr, cos, sin, pos, B, T, H, use_rope, block_table,
+                          max_len);
 }
 
 at::Tensor kv_append_fp8(const at::Tensor& qkv, at::Tensor k8, at::Tensor v8, at::Tensor ks, at::Tensor vs,
                          const at::Tensor& cos, const at::Tensor& sin, const at::Tensor& pos, int64_t B, int64_t T,
-                         int64_t H, bool use_rope) {
-    return kv_append_impl("kv_append_fp8", qkv, k8, v8, &ks, &vs, cos, sin, pos, B, T, H, use_rope);
+                         int64_t H, bool use_rope, const c10::optional<at::Tensor>& block_table, int64_t max_len) {
+    return kv_append_impl("kv_append_fp8", qkv, k8, v8, &ks, &vs, cos, sin, pos, B, T, H, use_rope, block_table,
+                          max_len);
 }
 
 // q [B, H*D] (roped) attends to the first *pos + 1 cache rows -> [B, H*D]
@@ -1063,15 +1109,16 @@ at::Tensor kv_append_fp8(const at::Tensor& qkv, at::Tensor k8, at::Tensor v8, at
 // ks / vs given: an fp8 cache; the same contract, outputs and partials layout.
 at::Tensor decode_attn_impl(const char* op, const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc,
                             const at::Tensor* ks, const at::Tensor* vs, const at::Tensor& pos, int64_t H, double scale,
-                            bool combine, int64_t T) {
-    TORCH_CHECK(kc.dim() == 4, op, ": the k cache must be [B, Hkv, Lmax, D]");
-    const int64_t B = kc.size(0), Hkv = kc.size(1), Lmax = kc.size(2), D = kc.size(3);
+                            bool combine, int64_t T, const c10::optional<at::Tensor>& table, int64_t max_len) {
+    const KvGeom kg = kv_geom(op, kc, table, max_len);
+    const int64_t B = kg.B, Hkv = kg.Hkv, Lmax = kg.Lmax, D = kg.D;
+    TORCH_CHECK(kg.pg.table == nullptr || Lmax < (1LL << 30), op, ": a paged cache needs Lmax below 2^30");
     TORCH_CHECK(decode_attn_ok((int)H, (int)Hkv, (int)D, (int)T), op,
                 ": head dim 64/128, H a multiple of Hkv and (H / Hkv) * T <= 8 required");
     check_cuda(q, "q");
     TORCH_CHECK(q.scalar_type() == at::kBFloat16 && q.is_contiguous() && q.numel() == B * T * H * D, op,
                 ": q must be contiguous bf16 [B*T, H*D]");
-    check_kv(kc, vc, ks, vs, B, Hkv, op);
+    check_kv(kc, vc, ks, vs, kg.dim0(B), Hkv, op);
     const int pstride = check_pos(pos, B);
     DevGuard g(q.device());
     const int ns = decode_attn_splits((int)Lmax);
@@ -1080,27 +1127,30 @@ at::Tensor decode_attn_impl(const char* op, const at::Tensor& q, const at::Tenso
     launch_decode_attn(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), ks ? ks->data_ptr<float>() : nullptr,
                        vs ? vs->data_ptr<float>() : nullptr, part.data_ptr<float>(), combine ? out.data_ptr() : nullptr,
                        pos.data_ptr<int>(), pstride, (int)B, (int)T, (int)H, (int)Hkv, (int)D, (int)Lmax, (float)scale,
-                       cur_stream());
+                       cur_stream(), kg.pg);
     return combine ? out : part;
 }
 
 at::Tensor decode_attn(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc, const at::Tensor& pos,
-                       int64_t H, double scale, bool combine, int64_t T) {
-    return decode_attn_impl("decode_attn", q, kc, vc, nullptr, nullptr, pos, H, scale, combine, T);
+                       int64_t H, double scale, bool combine, int64_t T, const c10::optional<at::Tensor>& block_table,
+                       int64_t max_len) {
+    return decode_attn_impl("decode_attn", q, kc, vc, nullptr, nullptr, pos, H, scale, combine, T, block_table,
+                            max_len);
 }
 
 at::Tensor decode_attn_fp8(const at::Tensor& q, const at::Tensor& k8, const at::Tensor& v8, const at::Tensor& ks,
                            const at::Tensor& vs, const at::Tensor& pos, int64_t H, double scale, bool combine,
-                           int64_t T) {
-    return decode_attn_impl("decode_attn_fp8", q, k8, v8, &ks, &vs, pos, H, scale, combine, T);
+                           int64_t T, const c10::optional<at::Tensor>& block_table, int64_t max_len) {
+    return decode_attn_impl("decode_attn_fp8", q, k8, v8, &ks, &vs, pos, H, scale, combine, T, block_table, max_len);
 }
 
 // Flash prefill over the cache (flash_attn_cache.hip): q [B*T, H*D] (roped, rows b * T + t, already appended at
 // positions *pos .. *pos + T - 1) -> [B*T, H*D]; token t sees keys 0 .. min(*pos + t, Lmax - 1).  Any T.
 at::Tensor cache_attn(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc, const at::Tensor& pos,
-                      int64_t H, double scale, int64_t T) {
-    TORCH_CHECK(kc.dim() == 4, "cache_attn: k_cache must be [B, Hkv, Lmax, D]");
-    const int64_t B = kc.size(0), Hkv = kc.size(1), Lmax = kc.size(2), D = kc.size(3);
+                      int64_t H, double scale, int64_t T, const c10::optional<at::Tensor>& block_table,
+                      int64_t max_len) {
+    const KvGeom kg = kv_geom("cache_attn", kc, block_table, max_len);
+    const int64_t B = kg.B, Hkv = kg.Hkv, Lmax = kg.Lmax, D = kg.D;
     TORCH_CHECK(H > 0 && T > 0 && H < (1 << 16) && T < (1 << 24) && Lmax < (1LL << 31) &&
                     cache_attn_ok((int)H, (int)Hkv, (int)D, (int)T, (int)Lmax),
                 "cache_attn: head dim 64/128, H a multiple of Hkv with H / Hkv <= 8, T >= 1 and a cache slab below "
@@ -1108,23 +1158,24 @@ at::Tensor cache_attn(const at::Tensor& q, const at::Tensor& kc, const at::Tenso
     check_cuda(q, "q");
     TORCH_CHECK(q.scalar_type() == at::kBFloat16 && q.is_contiguous() && q.numel() == B * T * H * D,
                 "cache_attn: q must be contiguous bf16 [B*T, H*D]");
-    check_cache(kc, B, Hkv, "k_cache");
-    check_cache(vc, B, Hkv, "v_cache");
+    check_cache(kc, kg.dim0(B), Hkv, "k_cache");
+    check_cache(vc, kg.dim0(B), Hkv, "v_cache");
     TORCH_CHECK(vc.sizes() == kc.sizes(), "cache_attn: k / v cache shapes differ");
     const int pstride = check_pos(pos, B);
     DevGuard g(q.device());
     auto out = at::empty({B * T, H * D}, q.options());
     launch_cache_attn(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(), pos.data_ptr<int>(), pstride, (int)B,
-                      (int)T, (int)H, (int)Hkv, (int)D, (int)Lmax, (float)scale, cur_stream());
+                      (int)T, (int)H, (int)Hkv, (int)D, (int)Lmax, (float)scale, cur_stream(), kg.pg);
     return out;
 }
 
 // cache_attn over the fp8 cache as stored (k8 / v8 e4m3 bytes [B, Hkv, Lmax, D], k_scale / v_scale [B, Hkv, Lmax]):
 // bit for bit kv_dequant into a zeroed bf16 pair followed by cache_attn, in one launch and with no scratch.
 at::Tensor cache_attn_fp8(const at::Tensor& q, const at::Tensor& k8, const at::Tensor& v8, const at::Tensor& ks,
-                          const at::Tensor& vs, const at::Tensor& pos, int64_t H, double scale, int64_t T) {
-    TORCH_CHECK(k8.dim() == 4, "cache_attn_fp8: k8 must be [B, Hkv, Lmax, D]");
-    const int64_t B = k8.size(0), Hkv = k8.size(1), Lmax = k8.size(2), D = k8.size(3);
+                          const at::Tensor& vs, const at::Tensor& pos, int64_t H, double scale, int64_t T,
+                          const c10::optional<at::Tensor>& block_table, int64_t max_len) {
+    const KvGeom kg = kv_geom("cache_attn_fp8", k8, block_table, max_len);
+    const int64_t B = kg.B, Hkv = kg.Hkv, Lmax = kg.Lmax, D = kg.D;
     TORCH_CHECK(H > 0 && T > 0 && H < (1 << 16) && T < (1 << 24) && Lmax < (1LL << 31) &&
                     cache_attn_fp8_ok((int)H, (int)Hkv, (int)D, (int)T, (int)Lmax),
                 "cache_attn_fp8: head dim 64/128, H a multiple of Hkv with H / Hkv <= 8, T >= 1 and a cache slab "
@@ -1132,15 +1183,15 @@ at::Tensor cache_attn_fp8(const at::Tensor& q, const at::Tensor& k8, const at::T
     check_cuda(q, "q");
     TORCH_CHECK(q.scalar_type() == at::kBFloat16 && q.is_contiguous() && q.numel() == B * T * H * D,
                 "cache_attn_fp8: q must be contiguous bf16 [B*T, H*D]");
-    check_cache8(k8, ks, B, Hkv, "k8");
-    check_cache8(v8, vs, B, Hkv, "v8");
+    check_cache8(k8, ks, kg.dim0(B), Hkv, "k8");
+    check_cache8(v8, vs, kg.dim0(B), Hkv, "v8");
     TORCH_CHECK(v8.sizes() == k8.sizes(), "cache_attn_fp8: k / v cache shapes differ");
     const int pstride = check_pos(pos, B);
     DevGuard g(q.device());
     auto out = at::empty({B * T, H * D}, q.options());
     launch_cache_attn_fp8(q.data_ptr(), k8.data_ptr(), v8.data_ptr(), ks.data_ptr<float>(), vs.data_ptr<float>(),
                           out.data_ptr(), pos.data_ptr<int>(), pstride, (int)B, (int)T, (int)H, (int)Hkv, (int)D,
-                          (int)Lmax, (float)scale, cur_stream());
+                          (int)Lmax, (float)scale, cur_stream(), kg.pg);
     return out;
 }
 
@@ -1262,12 +1313,16 @@ std::tuple<at::Tensor, at::Tensor> decode_qkv(const at::Tensor& x, const c10::op
                                               const c10::optional<at::Tensor>& ln, double eps, const at::Tensor& w,
                                               at::Tensor kc, at::Tensor vc, const at::Tensor& cos,
                                               const at::Tensor& sin, const at::Tensor& pos, int64_t H, bool use_rope,
-                                              const c10::optional<at::Tensor>& w_scale) {
+                                              const c10::optional<at::Tensor>& w_scale,
+                                              const c10::optional<at::Tensor>& block_table, int64_t max_len) {
     GemvArgs a;
     auto xsum = gemv_setup(a, x, xd, ln, eps, w, w_scale);
-    const int64_t B = a.M, Hkv = kc.size(1), Lmax = kc.size(2), D = kc.size(3);
-    check_cache(kc, B, Hkv, "k_cache");
-    check_cache(vc, B, Hkv, "v_cache");
+    const KvGeom kg = kv_geom("decode_qkv", kc, block_table, max_len);
+    const int64_t B = a.M, Hkv = kg.Hkv, Lmax = kg.Lmax, D = kg.D;
+    TORCH_CHECK(kg.pg.table == nullptr || kg.B == B, "decode_qkv: block_table must have one row per row of x");
+    TORCH_CHECK(Lmax < (1LL << 30), "decode_qkv: Lmax below 2^30");
+    check_cache(kc, kg.dim0(B), Hkv, "k_cache");
+    check_cache(vc, kg.dim0(B), Hkv, "v_cache");
     TORCH_CHECK(vc.sizes() == kc.sizes(), "decode_qkv: k / v cache shapes differ");
     TORCH_CHECK(a.N == (H + 2 * Hkv) * D && D % 2 == 0, "decode_qkv: weight rows must be (H + 2*Hkv) * D");
     const int pstride = check_pos(pos, B);
@@ -1289,6 +1344,7 @@ std::tuple<at::Tensor, at::Tensor> decode_qkv(const at::Tensor& x, const c10::op
     a.pos_stride = pstride;
     a.kc = (__bf16*)kc.data_ptr();
     a.vc = (__bf16*)vc.data_ptr();
+    a.pages = kg.pg;
     launch_gemv(a, 2, cur_stream());
     return {q, xsum};
 }
@@ -1535,23 +1591,26 @@ TORCH_LIBRARY(bpe_hip, m) {
     m.def("decode_gemv(Tensor x, Tensor? xd, Tensor? ln, float eps, Tensor w, int epi, Tensor? w_scale=None) -> "
           "(Tensor, Tensor)");
     m.def("decode_qkv(Tensor x, Tensor? xd, Tensor? ln, float eps, Tensor w, Tensor(a!) k_cache, "
-          "Tensor(b!) v_cache, Tensor cos, Tensor sin, Tensor pos, int H, bool rope, Tensor? w_scale=None) -> "
+          "Tensor(b!) v_cache, Tensor cos, Tensor sin, Tensor pos, int H, bool rope, Tensor? w_scale=None, "
+          "Tensor? block_table=None, int max_len=0) -> "
           "(Tensor, Tensor)");
     m.def("kv_append(Tensor qkv, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor cos, Tensor sin, Tensor pos, int B, "
-          "int T, int H, bool rope) -> Tensor");
+          "int T, int H, bool rope, Tensor? block_table=None, int max_len=0) -> Tensor");
     m.def("decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor pos, int H, float scale, "
-          "bool combine=True, int T=1) -> Tensor");
+          "bool combine=True, int T=1, Tensor? block_table=None, int max_len=0) -> Tensor");
     m.def("decode_attn_proj(Tensor part, Tensor w, Tensor? w_scale=None) -> Tensor");
     m.def("w_dequant(Tensor w8, Tensor w_scale, Tensor(a!) out) -> ()");
     m.def("kv_append_fp8(Tensor qkv, Tensor(a!) k8, Tensor(b!) v8, Tensor(c!) k_scale, Tensor(d!) v_scale, Tensor cos, "
-          "Tensor sin, Tensor pos, int B, int T, int H, bool use_rope) -> Tensor");
+          "Tensor sin, Tensor pos, int B, int T, int H, bool use_rope, Tensor? block_table=None, int max_len=0) -> "
+          "Tensor");
     m.def("decode_attn_fp8(Tensor q, Tensor k8, Tensor v8, Tensor k_scale, Tensor v_scale, Tensor pos, int H, "
-          "float scale, bool combine=True, int T=1) -> Tensor");
+          "float scale, bool combine=True, int T=1, Tensor? block_table=None, int max_len=0) -> Tensor");
     m.def("kv_dequant(Tensor k8, Tensor v8, Tensor k_scale, Tensor v_scale, Tensor pos, int T, Tensor(a!) k_out, "
           "Tensor(b!) v_out) -> ()");
-    m.def("cache_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor pos, int H, float scale, int T) -> Tensor");
+    m.def("cache_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor pos, int H, float scale, int T, "
+          "Tensor? block_table=None, int max_len=0) -> Tensor");
     m.def("cache_attn_fp8(Tensor q, Tensor k8, Tensor v8, Tensor k_scale, Tensor v_scale, Tensor pos, int H, "
-          "float scale, int T) -> Tensor");
+          "float scale, int T, Tensor? block_table=None, int max_len=0) -> Tensor");
     m.def("rmsnorm_fwd(Tensor x, Tensor w, float eps) -> (Tensor, Tensor)");
     m.def("add_rmsnorm_fwd(Tensor x, Tensor d, Tensor w, float eps) -> (Tensor, Tensor, Tensor)");
     m.def("rmsnorm_bwd(Tensor dy, Tensor x, Tensor w, Tensor rstd, Tensor? dres=None, Tensor(a!)? dw_acc=None) -> "

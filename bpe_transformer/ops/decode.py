@@ -56,6 +56,20 @@ and :func:`decode_attn_proj` take the pair (``w=w8, w_scale=...``) and stream
 half the weight bytes; each is, bit for bit on the GPU, the same call on
 ``weight_dequantize(w8, w_scale)``.  :func:`w_dequant` writes that matrix into
 a caller's bf16 buffer (for a library GEMM).
+
+**Paged cache** (``csrc/kv_cache.h``: ``PagedLayout``).  Every function above that takes a cache also takes
+``block_table=None`` and ``max_len=None``.  With a table, ``k_cache`` / ``v_cache`` / ``k8`` / ``v8`` are *pools*
+``[P, Hkv, KV_PAGE, D]`` (bf16 or ``float8_e4m3fn``; an fp8 pool has ``k_scale`` / ``v_scale [P, Hkv, KV_PAGE]``) of
+pages of ``KV_PAGE = 256`` rows in the unchanged row format, and ``block_table`` is a device int32 ``[B, NB]`` with
+``NB * KV_PAGE >= Lmax``: entry ``[b, j]`` is the pool page that holds positions ``256 j .. 256 j + 255`` of sequence
+``b``, ``-1`` where none is allocated.  ``Lmax`` is ``max_len`` (default ``NB * KV_PAGE``) and keeps its meaning: a
+token at or past it is dropped; it need not be a multiple of the page.  The caller guarantees a valid entry for every
+``j < ceil(min(pos[b] + T, Lmax) / 256)`` before a call that reads or writes there.  The kernels do not trust the
+table any more than ``pos``: a reader clamps a page id into ``[0, P - 1]``, and an append whose entry is outside ``[0,
+P)`` writes nothing to the pool.  A paged call gives, bit for bit, what the slab call gives on
+:func:`paged_gather` of the pool -- a page is ``decode_attn``'s 256-key chunk and four of ``cache_attn``'s 64-key
+tiles, so only the row addresses differ -- and the CPU oracles are defined that way: the slab reference on the
+gathered slab, appends scattered back (:func:`paged_scatter`).  :func:`kv_dequant` stays slab-only.
 """
 
 from __future__ import annotations
@@ -82,12 +96,66 @@ def _scale(cache: Tensor, scale: float | None) -> float:
     return 1.0 / math.sqrt(cache.shape[-1]) if scale is None else scale
 
 
+# ------------------------------------------------------------------ paged cache (csrc/kv_cache.h)
+KV_PAGE = 256  # rows of a page: kvc::KV_PAGE, decode_attn's chunk and four of cache_attn's key tiles
+
+
+def _pg(block_table: Tensor | None, max_len: int | None) -> tuple:
+    """The trailing ``block_table, max_len`` arguments of a HIP op: absent for a slab (the call is then what it
+    always was)."""
+    return () if block_table is None else (block_table, 0 if max_len is None else int(max_len))
+
+
+def _paged_len(block_table: Tensor, max_len: int | None) -> int:
+    n = block_table.shape[1] * KV_PAGE
+    assert max_len is None or 1 <= max_len <= n, "max_len: at most NB * KV_PAGE"
+    return n if max_len is None else int(max_len)
+
+
+def paged_gather(pool: Tensor, block_table: Tensor, max_len: int | None = None) -> Tensor:
+    """The slab a block table stands for: ``pool [P, Hkv, KV_PAGE, ...]`` (cache rows, or an fp8 pool's scales) and
+    ``block_table [B, NB]`` -> ``[B, Hkv, Lmax, ...]`` with positions ``256 j ..`` of sequence ``b`` taken from page
+    ``block_table[b, j]``; positions of an unallocated entry (``-1``) are zeros."""
+    Lmax = _paged_len(block_table, max_len)
+    B, NB = block_table.shape
+    t = block_table.to(pool.device).long()
+    pages = pool[t.clamp(min=0)]  # [B, NB, Hkv, KV_PAGE, ...]
+    hole = (t < 0).view(B, NB, *[1] * (pool.dim() - 1))
+    pages = torch.where(hole, torch.zeros((), dtype=pool.dtype, device=pool.device), pages)
+    return pages.transpose(1, 2).reshape(B, pool.shape[1], NB * KV_PAGE, *pool.shape[3:])[:, :, :Lmax].contiguous()
+
+
+def paged_scatter(slab: Tensor, pool: Tensor, block_table: Tensor) -> Tensor:
+    """The inverse of :func:`paged_gather`: the rows of ``slab [B, Hkv, Lmax, ...]`` are written into the pages the
+    table names (in place; entries ``-1`` are skipped, pool rows past ``Lmax`` in a last page and pages in no table
+    row are left as they are).  Returns ``pool``."""
+    Lmax = slab.shape[2]
+    for b, row in enumerate(block_table.tolist()):
+        for j, pg in enumerate(row):
+            n = min(KV_PAGE, Lmax - KV_PAGE * j)
+            if pg >= 0 and n > 0:
+                pool[pg, :, :n] = slab[b, :, KV_PAGE * j : KV_PAGE * j + n]
+    return pool
+
+
+def _on_slab(fn, pools: tuple, block_table: Tensor, max_len: int | None, write: bool = False):
+    """A paged reference: ``fn(*slabs)`` on the gathered slabs of ``pools``; ``write``: the slabs are scattered back."""
+    slabs = [paged_gather(p, block_table, max_len) for p in pools]
+    out = fn(*slabs)
+    if write:
+        for sl, p in zip(slabs, pools):
+            paged_scatter(sl, p, block_table)
+    return out
+
+
 def kv_append(qkv: Tensor, k_cache: Tensor, v_cache: Tensor, cos: Tensor | None, sin: Tensor | None, pos: Tensor,
-              batch: int, n_new: int, n_heads: int) -> Tensor:
+              batch: int, n_new: int, n_heads: int, block_table: Tensor | None = None,
+              max_len: int | None = None) -> Tensor:
     if qkv.is_cuda:
         c, s, use_rope = _rope_args(qkv, cos, sin)
-        return ops().kv_append(qkv, k_cache, v_cache, c, s, pos, batch, n_new, n_heads, use_rope)
-    return kv_append_reference(qkv, k_cache, v_cache, cos, sin, pos, batch, n_new, n_heads)
+        return ops().kv_append(qkv, k_cache, v_cache, c, s, pos, batch, n_new, n_heads, use_rope,
+                               *_pg(block_table, max_len))
+    return kv_append_reference(qkv, k_cache, v_cache, cos, sin, pos, batch, n_new, n_heads, block_table, max_len)
 
 
 def _per_sequence(pos: Tensor) -> bool:
@@ -95,7 +163,11 @@ def _per_sequence(pos: Tensor) -> bool:
     return pos.numel() > 1
 
 
-def kv_append_reference(qkv, k_cache, v_cache, cos, sin, pos, batch, n_new, n_heads) -> Tensor:
+def kv_append_reference(qkv, k_cache, v_cache, cos, sin, pos, batch, n_new, n_heads, block_table=None,
+                        max_len=None) -> Tensor:
+    if block_table is not None:
+        return _on_slab(lambda k, v: kv_append_reference(qkv, k, v, cos, sin, pos, batch, n_new, n_heads),
+                        (k_cache, v_cache), block_table, max_len, write=True)
     if _per_sequence(pos):  # one sequence at a time on its slab of the caches (views: written in place)
         assert pos.numel() == batch
         rows = qkv.view(batch, n_new, -1)
@@ -117,16 +189,22 @@ def kv_append_reference(qkv, k_cache, v_cache, cos, sin, pos, batch, n_new, n_he
 
 
 def decode_attention(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, n_heads: int,
-                     scale: float | None = None, n_new: int = 1) -> Tensor:
+                     scale: float | None = None, n_new: int = 1, block_table: Tensor | None = None,
+                     max_len: int | None = None) -> Tensor:
     """Attention of ``n_new`` new tokens per sequence (``q [B*n_new, H*D]``, already appended to the caches at
     positions ``pos .. pos + n_new - 1``) over the cache; token t sees keys ``0 .. pos + t``."""
     scale = _scale(k_cache, scale)
     if q.is_cuda:
-        return ops().decode_attn(q.contiguous(), k_cache, v_cache, pos, n_heads, scale, True, n_new)
-    return decode_attention_reference(q, k_cache, v_cache, pos, n_heads, scale, n_new)
+        return ops().decode_attn(q.contiguous(), k_cache, v_cache, pos, n_heads, scale, True, n_new,
+                                 *_pg(block_table, max_len))
+    return decode_attention_reference(q, k_cache, v_cache, pos, n_heads, scale, n_new, block_table, max_len)
 
 
-def decode_attention_reference(q, k_cache, v_cache, pos, n_heads, scale=None, n_new: int = 1) -> Tensor:
+def decode_attention_reference(q, k_cache, v_cache, pos, n_heads, scale=None, n_new: int = 1, block_table=None,
+                               max_len=None) -> Tensor:
+    if block_table is not None:
+        return _on_slab(lambda k, v: decode_attention_reference(q, k, v, pos, n_heads, scale, n_new),
+                        (k_cache, v_cache), block_table, max_len)
     B, Hkv, Lmax, D = k_cache.shape
     H, T = n_heads, n_new
     if _per_sequence(pos):
@@ -148,29 +226,38 @@ def decode_attention_reference(q, k_cache, v_cache, pos, n_heads, scale=None, n_
 
 
 def prefill_attention(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, n_heads: int,
-                      scale: float | None = None, n_new: int = 1) -> Tensor:
+                      scale: float | None = None, n_new: int = 1, block_table: Tensor | None = None,
+                      max_len: int | None = None) -> Tensor:
     """Flash prefill over the cache (``csrc/flash_attn_cache.hip``): the contract of :func:`decode_attention` --
     ``q [B*n_new, H*D]`` already appended at ``pos .. pos + n_new - 1``, token t sees keys ``0 .. pos + t`` -- for
     any ``n_new`` (MFMA flash attention whose keys are the cache slabs), where ``decode_attention`` takes at most
     ``8 / G`` tokens.  The row of a token at or past ``Lmax`` is unspecified."""
     scale = _scale(k_cache, scale)
     if q.is_cuda:
-        return ops().cache_attn(q.contiguous(), k_cache, v_cache, pos, n_heads, scale, n_new)
-    return decode_attention_reference(q, k_cache, v_cache, pos, n_heads, scale, n_new)
+        return ops().cache_attn(q.contiguous(), k_cache, v_cache, pos, n_heads, scale, n_new,
+                                *_pg(block_table, max_len))
+    return decode_attention_reference(q, k_cache, v_cache, pos, n_heads, scale, n_new, block_table, max_len)
 
 
 def decode_attention_partials(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, n_heads: int,
-                              scale: float | None = None) -> Tensor:
+                              scale: float | None = None, block_table: Tensor | None = None,
+                              max_len: int | None = None) -> Tensor:
     """Split-K decode attention without the combine: fp32 ``[B, H, nsplit, D + 2]`` = (o, m, l) per 256-key chunk
     (natural-log units), consumed by :func:`decode_attn_proj`.  A chunk past the valid length has ``m = -inf`` and
     ``l = 0``; its ``o`` part is unspecified (the GPU kernel leaves it unwritten) and every consumer skips it."""
     scale = _scale(k_cache, scale)
     if q.is_cuda:
-        return ops().decode_attn(q.contiguous(), k_cache, v_cache, pos, n_heads, scale, False)
-    return decode_partials_reference(q, k_cache, v_cache, pos, n_heads, scale)
+        return ops().decode_attn(q.contiguous(), k_cache, v_cache, pos, n_heads, scale, False, 1,
+                                 *_pg(block_table, max_len))
+    return decode_partials_reference(q, k_cache, v_cache, pos, n_heads, scale, block_table=block_table,
+                                     max_len=max_len)
 
 
-def decode_partials_reference(q, k_cache, v_cache, pos, n_heads, scale=None, chunk: int = 256) -> Tensor:
+def decode_partials_reference(q, k_cache, v_cache, pos, n_heads, scale=None, chunk: int = 256, block_table=None,
+                              max_len=None) -> Tensor:
+    if block_table is not None:
+        return _on_slab(lambda k, v: decode_partials_reference(q, k, v, pos, n_heads, scale, chunk),
+                        (k_cache, v_cache), block_table, max_len)
     B, Hkv, Lmax, D = k_cache.shape
     H = n_heads
     if _per_sequence(pos):
@@ -252,17 +339,19 @@ def decode_gemv_reference(x, w, xd=None, ln=None, eps=1e-5, swiglu=False, w_scal
 
 def decode_qkv(x: Tensor, w: Tensor, k_cache: Tensor, v_cache: Tensor, cos: Tensor | None, sin: Tensor | None,
                pos: Tensor, n_heads: int, xd: Tensor | None = None, ln: Tensor | None = None,
-               eps: float = 1e-5, w_scale: Tensor | None = None) -> tuple[Tensor, Tensor | None]:
+               eps: float = 1e-5, w_scale: Tensor | None = None, block_table: Tensor | None = None,
+               max_len: int | None = None) -> tuple[Tensor, Tensor | None]:
     """Fused decode QKV: ``qkv = RMSNorm(x + xd) W^T`` for one new token per sequence, RoPE at the device-side
     position, K / V written into the caches; returns ``(q [M, H*D], x + xd)``.  With ``pos [M]`` row ``m`` is
     sequence ``m`` at ``pos[m]``; a row at ``Lmax`` or past it writes nothing, and its query row is unspecified
     (as for :func:`kv_append`).  With ``w_scale``, ``w`` is the e4m3 matrix of :func:`weight_quantize`."""
     if x.is_cuda:
         c, sn, use_rope = _rope_args(x, cos, sin)
-        q, s = ops().decode_qkv(x, xd, ln, eps, w, k_cache, v_cache, c, sn, pos, n_heads, use_rope, *_ws(w_scale))
+        tail = _ws(w_scale) if block_table is None else (w_scale, *_pg(block_table, max_len))
+        q, s = ops().decode_qkv(x, xd, ln, eps, w, k_cache, v_cache, c, sn, pos, n_heads, use_rope, *tail)
         return q, (s if xd is not None else None)
     qkv, s = decode_gemv_reference(x, w, xd, ln, eps, w_scale=w_scale)
-    return kv_append_reference(qkv, k_cache, v_cache, cos, sin, pos, x.shape[0], 1, n_heads), s
+    return kv_append_reference(qkv, k_cache, v_cache, cos, sin, pos, x.shape[0], 1, n_heads, block_table, max_len), s
 
 
 # ------------------------------------------------------------------ fp8 cache (csrc/kv_fp8.hip)
@@ -293,18 +382,26 @@ def kv_dequantize_reference(q: Tensor, s: Tensor, dtype: torch.dtype = torch.bfl
 
 
 def kv_append_fp8(qkv: Tensor, k8: Tensor, v8: Tensor, k_scale: Tensor, v_scale: Tensor, cos: Tensor | None,
-                  sin: Tensor | None, pos: Tensor, batch: int, n_new: int, n_heads: int) -> Tensor:
+                  sin: Tensor | None, pos: Tensor, batch: int, n_new: int, n_heads: int,
+                  block_table: Tensor | None = None, max_len: int | None = None) -> Tensor:
     """:func:`kv_append` into an fp8 cache: the rows it would have written to bf16 caches are quantised into ``k8`` /
     ``v8 [B, Hkv, Lmax, D]`` with their scales in ``k_scale`` / ``v_scale [B, Hkv, Lmax]``; returns the same ``q``."""
     if qkv.is_cuda:
         c, s, use_rope = _rope_args(qkv, cos, sin)
-        return ops().kv_append_fp8(qkv, k8, v8, k_scale, v_scale, c, s, pos, batch, n_new, n_heads, use_rope)
-    return kv_append_fp8_reference(qkv, k8, v8, k_scale, v_scale, cos, sin, pos, batch, n_new, n_heads)
+        return ops().kv_append_fp8(qkv, k8, v8, k_scale, v_scale, c, s, pos, batch, n_new, n_heads, use_rope,
+                                   *_pg(block_table, max_len))
+    return kv_append_fp8_reference(qkv, k8, v8, k_scale, v_scale, cos, sin, pos, batch, n_new, n_heads, block_table,
+                                   max_len)
 
 
-def kv_append_fp8_reference(qkv, k8, v8, k_scale, v_scale, cos, sin, pos, batch, n_new, n_heads) -> Tensor:
+def kv_append_fp8_reference(qkv, k8, v8, k_scale, v_scale, cos, sin, pos, batch, n_new, n_heads, block_table=None,
+                            max_len=None) -> Tensor:
     """:func:`kv_append_reference` into bf16-valued staging rows (``qkv``'s dtype rounded to bf16), which are then
     quantised row by row; only the rows ``kv_append`` writes change."""
+    if block_table is not None:
+        return _on_slab(lambda k, v, ks, vs: kv_append_fp8_reference(qkv, k, v, ks, vs, cos, sin, pos, batch, n_new,
+                                                                     n_heads),
+                        (k8, v8, k_scale, v_scale), block_table, max_len, write=True)
     B, Hkv, Lmax, D = k8.shape
     P = pos.reshape(-1).tolist()
     P = P if _per_sequence(pos) else P * batch
@@ -319,37 +416,53 @@ def kv_append_fp8_reference(qkv, k8, v8, k_scale, v_scale, cos, sin, pos, batch,
 
 
 def decode_attention_fp8(q: Tensor, k8: Tensor, v8: Tensor, k_scale: Tensor, v_scale: Tensor, pos: Tensor,
-                         n_heads: int, scale: float | None = None, n_new: int = 1) -> Tensor:
+                         n_heads: int, scale: float | None = None, n_new: int = 1, block_table: Tensor | None = None,
+                         max_len: int | None = None) -> Tensor:
     """:func:`decode_attention` over an fp8 cache."""
     scale = _scale(k8, scale)
     if q.is_cuda:
-        return ops().decode_attn_fp8(q.contiguous(), k8, v8, k_scale, v_scale, pos, n_heads, scale, True, n_new)
-    return decode_attention_fp8_reference(q, k8, v8, k_scale, v_scale, pos, n_heads, scale, n_new)
+        return ops().decode_attn_fp8(q.contiguous(), k8, v8, k_scale, v_scale, pos, n_heads, scale, True, n_new,
+                                     *_pg(block_table, max_len))
+    return decode_attention_fp8_reference(q, k8, v8, k_scale, v_scale, pos, n_heads, scale, n_new, block_table,
+                                          max_len)
 
 
-def decode_attention_fp8_reference(q, k8, v8, k_scale, v_scale, pos, n_heads, scale=None, n_new: int = 1) -> Tensor:
+def decode_attention_fp8_reference(q, k8, v8, k_scale, v_scale, pos, n_heads, scale=None, n_new: int = 1,
+                                   block_table=None, max_len=None) -> Tensor:
     """:func:`decode_attention_reference` on the dequantised caches (fp32 values, so nothing is rounded twice)."""
+    if block_table is not None:
+        return _on_slab(lambda k, v, ks, vs: decode_attention_fp8_reference(q, k, v, ks, vs, pos, n_heads, scale,
+                                                                            n_new),
+                        (k8, v8, k_scale, v_scale), block_table, max_len)
     return decode_attention_reference(q, kv_dequantize_reference(k8, k_scale, torch.float32),
                                       kv_dequantize_reference(v8, v_scale, torch.float32), pos, n_heads, scale, n_new)
 
 
 def prefill_attention_fp8(q: Tensor, k8: Tensor, v8: Tensor, k_scale: Tensor, v_scale: Tensor, pos: Tensor,
-                          n_heads: int, scale: float | None = None, n_new: int = 1) -> Tensor:
+                          n_heads: int, scale: float | None = None, n_new: int = 1,
+                          block_table: Tensor | None = None, max_len: int | None = None) -> Tensor:
     """:func:`prefill_attention` over an fp8 cache (``csrc/flash_attn_cache.hip``, the ``Fp8Cache`` instantiation):
     any ``n_new``, the e4m3 rows and their scales read as stored."""
     scale = _scale(k8, scale)
     if q.is_cuda:
-        return ops().cache_attn_fp8(q.contiguous(), k8, v8, k_scale, v_scale, pos, n_heads, scale, n_new)
-    return decode_attention_fp8_reference(q, k8, v8, k_scale, v_scale, pos, n_heads, scale, n_new)
+        return ops().cache_attn_fp8(q.contiguous(), k8, v8, k_scale, v_scale, pos, n_heads, scale, n_new,
+                                    *_pg(block_table, max_len))
+    return decode_attention_fp8_reference(q, k8, v8, k_scale, v_scale, pos, n_heads, scale, n_new, block_table,
+                                          max_len)
 
 
 def decode_attention_partials_fp8(q: Tensor, k8: Tensor, v8: Tensor, k_scale: Tensor, v_scale: Tensor, pos: Tensor,
-                                  n_heads: int, scale: float | None = None, n_new: int = 1) -> Tensor:
+                                  n_heads: int, scale: float | None = None, n_new: int = 1,
+                                  block_table: Tensor | None = None, max_len: int | None = None) -> Tensor:
     """:func:`decode_attention_partials` over an fp8 cache: the same layout, for :func:`decode_attn_proj`."""
     scale = _scale(k8, scale)
     if q.is_cuda:
-        return ops().decode_attn_fp8(q.contiguous(), k8, v8, k_scale, v_scale, pos, n_heads, scale, False, n_new)
+        return ops().decode_attn_fp8(q.contiguous(), k8, v8, k_scale, v_scale, pos, n_heads, scale, False, n_new,
+                                     *_pg(block_table, max_len))
     assert n_new == 1
+    if block_table is not None:
+        return _on_slab(lambda k, v, ks, vs: decode_attention_partials_fp8(q, k, v, ks, vs, pos, n_heads, scale),
+                        (k8, v8, k_scale, v_scale), block_table, max_len)
     return decode_partials_reference(q, kv_dequantize_reference(k8, k_scale, torch.float32),
                                      kv_dequantize_reference(v8, v_scale, torch.float32), pos, n_heads, scale)
 

@@ -564,6 +564,78 @@ def _sample(logits: Tensor, temperature: float, top_p: float | None, generator, 
     return torch.multinomial(probs, 1, generator=generator).squeeze(-1)
 
 
+class _Controls:
+    """The sampling controls of one ``generate`` call that are not at their defaults (``ops/sampling.py``, "Sampling
+    controls"): ``penal`` -- a penalty is on, so the token history is kept; ``proc`` -- the sampler reads processed
+    logits; ``logprobs`` -- the log-sum-exp and the emitted tokens' log-probs are wanted.  ``key`` is what a captured
+    graph bakes in: the penalty values and the two booleans (the bias values live in a static buffer)."""
+
+    def __init__(self, rp: float, pp: float, fp: float, bias: Tensor | None, logprobs: bool):
+        self.rp, self.pp, self.fp, self.bias, self.logprobs = float(rp), float(pp), float(fp), bias, bool(logprobs)
+        self.penal = self.rp != 1.0 or self.pp != 0.0 or self.fp != 0.0
+        self.proc = self.penal or bias is not None
+        self.key = (self.rp, self.pp, self.fp, bias is not None, self.logprobs)
+
+
+def _controls(V: int, device, repetition_penalty, presence_penalty, frequency_penalty, logit_bias,
+              return_logprobs) -> _Controls | None:
+    """``None`` when every control is at its default (then nothing new runs), else the :class:`_Controls`, with
+    ``logit_bias`` -- a ``{token: value}`` dict or a ``[V]`` tensor -- as an fp32 ``[V]`` tensor on ``device``."""
+    if not float(repetition_penalty) > 0:
+        raise ValueError(f"repetition_penalty must be > 0, got {repetition_penalty}")
+    bias = None
+    if isinstance(logit_bias, dict):
+        if logit_bias:
+            bad = [t for t in logit_bias if not 0 <= int(t) < V]
+            if bad:
+                raise ValueError(f"logit_bias: token {bad[0]} outside the vocabulary of {V}")
+            bias = torch.zeros(V, dtype=torch.float32)
+            for t, v in logit_bias.items():
+                bias[int(t)] = float(v)
+            bias = bias.to(device)
+    elif logit_bias is not None:
+        if tuple(logit_bias.shape) != (V,):
+            raise ValueError(f"logit_bias: a {{token: value}} dict or a [{V}] tensor, got {tuple(logit_bias.shape)}")
+        bias = logit_bias.detach().to(device, torch.float32).contiguous()
+    c = _Controls(repetition_penalty, presence_penalty, frequency_penalty, bias, return_logprobs)
+    return c if c.proc or c.logprobs else None
+
+
+class _HostControls:
+    """The controls around the host sampler: the history, the emitted tokens and their log-probs on the logits'
+    device, ``logit_process`` before ``_sample`` and ``token_commit`` after it."""
+
+    def __init__(self, ctl: _Controls, ids: Tensor, lengths, V: int, max_new_tokens: int):
+        from ..ops import sampling
+
+        B, dev = ids.shape[0], ids.device
+        self.ctl, self.ops = ctl, sampling
+        self.hist = sampling.prompt_hist(ids, lengths, V) if ctl.penal else None
+        self.toks = torch.full((B, max(max_new_tokens, 1)), -1, dtype=torch.long, device=dev)
+        self.rng = torch.zeros(2, dtype=torch.long, device=dev)  # (unused seed, the column)
+        self.lse = torch.empty(B, dtype=torch.float32, device=dev) if ctl.logprobs else None
+        self.logprob = torch.full(self.toks.shape, math.nan, dtype=torch.float32, device=dev) if ctl.logprobs else None
+        self.raw = None
+
+    def process(self, logits: Tensor) -> Tensor:
+        """The logits the sampler reads (the processed copy, or ``logits`` itself with log-probs alone)."""
+        c = self.ctl
+        if logits.dtype not in (torch.bfloat16, torch.float32):
+            logits = logits.float()
+        self.raw = logits = logits.contiguous()
+        out = torch.empty_like(logits) if c.proc else None
+        self.ops.logit_process(logits, self.hist, c.bias, c.rp, c.pp, c.fp, out, self.lse)
+        return out if c.proc else logits
+
+    def commit(self, i: int, nxt: Tensor, idle=None) -> None:
+        """Token ``i`` of every row (``idle [B]`` bool: rows that emit nothing) into the history and the log-probs."""
+        c = self.ctl
+        self.toks[:, i] = nxt if idle is None else torch.where(idle.to(nxt.device), torch.full_like(nxt, -1), nxt)
+        if c.penal or c.logprobs:
+            self.rng[1] = i
+            self.ops.token_commit(self.toks, self.rng, self.hist, self.raw, self.lse, self.logprob)
+
+
 class DecodeSession:
     """Incremental decoding of ``batch`` sequences with a KV cache.
 
@@ -864,7 +936,9 @@ class DecodeSession:
     @torch.no_grad()
     def generate(self, prompt, max_new_tokens: int, temperature: float = 1.0, top_p: float | None = None,
                  eos_token_id: int | None = None, generator: torch.Generator | None = None,
-                 top_k: int | None = None, sampler: str = "host", seed: int | None = None, sync_every: int = 16):
+                 top_k: int | None = None, sampler: str = "host", seed: int | None = None, sync_every: int = 16,
+                 repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
+                 logit_bias=None, return_logprobs: bool = False):
         """``prompt [B, S]`` -> ``[B, S + n]`` (stops early once every row emitted ``eos_token_id``).
 
         Ragged sessions also take a list of ``B`` 1-D prompts of different lengths and return a list of 1-D tensors:
@@ -880,19 +954,35 @@ class DecodeSession:
         host only reads the ``done`` flags every ``sync_every`` tokens (never, without ``eos_token_id``).  Its random
         stream is Philox keyed by ``seed`` at counter (token index, row); ``seed=None`` draws one from ``generator``
         (else from torch's default generator), which is all ``generator`` is used for in this mode.  The results have
-        the shapes of the host sampler's; ``prompt + max_new_tokens <= max_len`` is checked once, up front."""
+        the shapes of the host sampler's; ``prompt + max_new_tokens <= max_len`` is checked once, up front.
+
+        Sampling controls (``ops/sampling.py`` states the function; all default to off, and then nothing new runs):
+        ``repetition_penalty`` (> 0; over prompt and output), ``presence_penalty`` / ``frequency_penalty`` (over the
+        output) and ``logit_bias`` (a ``{token: value}`` dict or a ``[V]`` tensor; ``-inf`` bans a token) change the
+        logits the sampler reads -- ``ops.logit_process`` before every sample, ``ops.token_commit`` after it, with the
+        per-sequence token history on the device; with ``sampler="device"`` both run inside the captured step: decode
+        -> ``logit_process`` -> ``sample_step`` -> ``token_commit`` -> ``rng[1] += 1``.  ``return_logprobs`` makes
+        the result ``(tokens, logprobs)``: fp32 ``[B, n]`` (a list of 1-D tensors for list prompts), aligned with the
+        emitted tokens and trimmed as they are, each the token's log-probability under the model's own
+        distribution (unprocessed logits, T = 1, no filters), not under the warped one it was sampled from."""
         assert sampler in ("host", "device"), "sampler: 'host' or 'device'"
+        ctl = _controls(self.model.lm_head.weight.shape[0], self.device, repetition_penalty, presence_penalty,
+                        frequency_penalty, logit_bias, return_logprobs)
         if sampler == "device":
             return self._generate_device(prompt, max_new_tokens, temperature, top_k, top_p, eos_token_id, generator,
-                                         seed, sync_every)
+                                         seed, sync_every, ctl)
         if isinstance(prompt, (list, tuple)):
-            return self._generate_ragged(prompt, max_new_tokens, temperature, top_p, eos_token_id, generator, top_k)
+            return self._generate_ragged(prompt, max_new_tokens, temperature, top_p, eos_token_id, generator, top_k,
+                                         ctl)
         self.reset()
         logits = self.prefill(prompt)
         outs = [prompt.to(self.device)]
         done = None
+        hc = None if ctl is None else _HostControls(ctl, outs[0], None, logits.shape[-1], max_new_tokens)
         for i in range(max_new_tokens):
-            nxt = _sample(logits, temperature, top_p, generator, top_k)
+            nxt = _sample(logits if hc is None else hc.process(logits), temperature, top_p, generator, top_k)
+            if hc is not None:
+                hc.commit(i, nxt)
             outs.append(nxt[:, None])
             if eos_token_id is not None:
                 hit = nxt == eos_token_id
@@ -901,6 +991,8 @@ class DecodeSession:
                     break
             if i + 1 < max_new_tokens:
                 logits = self.decode(nxt)
+        if ctl is not None and ctl.logprobs:
+            return torch.cat(outs, 1), hc.logprob[:, : len(outs) - 1]
         return torch.cat(outs, 1)
 
     def _pad_prompts(self, prompts):
@@ -917,15 +1009,18 @@ class DecodeSession:
         return prompts, n, ids
 
     def _generate_ragged(self, prompts, max_new_tokens, temperature, top_p, eos_token_id, generator,
-                         top_k=None) -> list[Tensor]:
+                         top_k=None, ctl=None):
         B = self.batch
         prompts, n, ids = self._pad_prompts(prompts)
         self.reset()
         logits = self.prefill(ids, n)
         new: list[list[int]] = [[] for _ in range(B)]
         done = [False] * B
+        hc = None if ctl is None else _HostControls(ctl, ids, n, logits.shape[-1], max_new_tokens)
         for i in range(max_new_tokens):
-            nxt = _sample(logits, temperature, top_p, generator, top_k)
+            nxt = _sample(logits if hc is None else hc.process(logits), temperature, top_p, generator, top_k)
+            if hc is not None:
+                hc.commit(i, nxt, torch.tensor(done))
             for b, tok in enumerate(nxt.tolist()):
                 if not done[b]:
                     new[b].append(tok)
@@ -936,14 +1031,20 @@ class DecodeSession:
                 logits = self.decode(nxt, active=[not d for d in done])
                 if any(done):  # an inactive row's logits are unspecified: keep the sampler's input finite
                     logits[[b for b in range(B) if done[b]]] = 0.0
-        return [torch.cat([p, torch.tensor(t, dtype=p.dtype, device=self.device)]) for p, t in zip(prompts, new)]
+        out = [torch.cat([p, torch.tensor(t, dtype=p.dtype, device=self.device)]) for p, t in zip(prompts, new)]
+        if ctl is not None and ctl.logprobs:
+            return out, [hc.logprob[b, : len(t)].clone() for b, t in enumerate(new)]
+        return out
 
     # ------------------------------------------------------------------ device sampler
-    def _sampler_state(self, temperature: float, top_k: int, top_p: float, eos: int):
+    def _sampler_state(self, temperature: float, top_k: int, top_p: float, eos: int, ctl: "_Controls | None" = None):
         """The device sampler's static buffers -- ``ids [B, 1]`` (the next token: the step's input), ``out
         [B, max_len]`` (token ``i`` of the continuation in column ``i``), ``done [B]``, ``rng = (seed, count)`` --
         and, with ``use_graph``, the graph of one decode step + ``sample_step`` + ``rng[1] += 1`` for these sampling
-        parameters (they are baked into the graph: other parameters capture it again).  Captured like ``_capture``:
+        parameters (they are baked into the graph: other parameters capture it again).  With sampling controls
+        (``ctl``) the state gains static ``hist [B, V]``, ``bias [V]``, ``lse [B]``, ``proc [B, V]`` and ``logprob
+        [B, max_len]``, and the captured step is decode -> ``logit_process`` -> ``sample_step`` on ``proc`` ->
+        ``token_commit`` -> ``rng[1] += 1`` (:meth:`_sample_controlled`).  Captured like ``_capture``:
         one stream, so no parallel branches; the warm-up run's writes are all re-initialised by the caller."""
         from ..ops import sampling
 
@@ -962,10 +1063,29 @@ class DecodeSession:
             }
         key = (float(temperature), top_k, top_p, eos)
         st["params"] = key
+        st["ctl"] = ctl
+        if ctl is not None:
+            # the controls' static buffers (module ops/sampling.py, "Sampling controls"); their contents are the
+            # caller's to initialise.  The penalty values and the two booleans join the graph key; with every
+            # control at its default the key is the old one and selects the graph that exists without them.
+            key = key + ctl.key
+            if "hist" not in st:
+                B, dev, V = self.batch, self.device, self.model.lm_head.weight.shape[0]
+                st["hist"] = torch.zeros(B, V, dtype=torch.int32, device=dev)
+                st["bias"] = torch.zeros(V, dtype=torch.float32, device=dev)
+                st["lse"] = torch.zeros(B, dtype=torch.float32, device=dev)
+                st["logprob"] = torch.full((B, self.max_len), math.nan, dtype=torch.float32, device=dev)
+                # the processed logits, [B, V] of the logits' dtype (off the fast path: made by the first step)
+                st["proc"] = torch.empty(B, V, dtype=self.model.lm_head.weight.dtype, device=dev) if self.fast else None
+            if ctl.bias is not None:
+                st["bias"].copy_(ctl.bias)
         if self.use_graph and st["key"] != key:
             def run():
                 logits = self._forward_fast(st["ids"], "decode", step=self._step)
-                sampling.sample_step(logits, *key[:3], st["rng"], st["ids"], st["out"], st["step"], st["done"], eos)
+                if ctl is None:
+                    sampling.sample_step(logits, *key[:3], st["rng"], st["ids"], st["out"], st["step"], st["done"], eos)
+                else:
+                    self._sample_controlled(st, logits)
                 st["rng"][1:].add_(1)
 
             pos0 = self.cache.pos.clone()
@@ -981,6 +1101,30 @@ class DecodeSession:
             self.cache.pos.copy_(pos0)
             st["graph"], st["key"] = g, key
         return st
+
+    def _sample_controlled(self, st, logits: Tensor) -> None:
+        """``sample_step`` with the call's sampling controls around it, all on the sampler's static buffers:
+        ``logit_process`` (``logits`` -> ``proc``, the raw rows' ``lse``) -> ``sample_step`` on ``proc`` ->
+        ``token_commit`` (history, log-probs).  Three launches on one stream; the caller advances ``rng[1]``."""
+        from ..ops import sampling
+
+        temperature, top_k, top_p, eos = st["params"]
+        ctl = st["ctl"]
+        if logits.dtype not in (torch.bfloat16, torch.float32):  # (an fp64 model off the fast path)
+            logits = logits.float()
+        logits = logits.contiguous()
+        src = logits
+        if ctl.proc:
+            if st["proc"] is None or st["proc"].dtype != logits.dtype:
+                st["proc"] = torch.empty_like(logits)
+            src = st["proc"]
+        hist = st["hist"] if ctl.penal else None
+        lse = st["lse"] if ctl.logprobs else None
+        sampling.logit_process(logits, hist, st["bias"] if ctl.bias is not None else None, ctl.rp, ctl.pp, ctl.fp,
+                               src if ctl.proc else None, lse)
+        sampling.sample_step(src, temperature, top_k, top_p, st["rng"], st["ids"], st["out"], st["step"], st["done"], eos)
+        if ctl.penal or ctl.logprobs:
+            sampling.token_commit(st["out"], st["rng"], hist, logits, lse, st["logprob"] if ctl.logprobs else None)
 
     def _device_step(self, st) -> None:
         """Decode the token in ``st["ids"]`` and sample the next one into it: one replay on the fast path."""
@@ -998,11 +1142,15 @@ class DecodeSession:
             logits = self._forward_reference(st["ids"], n, rows)
             self.cache.advance(rows, n)
         temperature, top_k, top_p, eos = st["params"]
-        sampling.sample_step(logits, temperature, top_k, top_p, st["rng"], st["ids"], st["out"], step, st["done"], eos)
+        if st["ctl"] is None:
+            sampling.sample_step(logits, temperature, top_k, top_p, st["rng"], st["ids"], st["out"], step, st["done"],
+                                 eos)
+        else:
+            self._sample_controlled(st, logits)
         st["rng"][1:].add_(1)
 
     def _generate_device(self, prompt, max_new_tokens, temperature, top_k, top_p, eos_token_id, generator, seed,
-                         sync_every):
+                         sync_every, ctl=None):
         from ..ops import sampling
 
         B = self.batch
@@ -1014,8 +1162,11 @@ class DecodeSession:
             n = [ids.shape[1]] * B
         assert sync_every >= 1, "sync_every: a positive number of tokens"
         assert max(n) + max_new_tokens <= self.max_len, "KV cache full: prompt + max_new_tokens exceeds max_len"
+        lp = ctl is not None and ctl.logprobs
         if max_new_tokens <= 0:
-            return prompts if as_list else ids
+            res = prompts if as_list else ids
+            none = torch.empty(B, 0, dtype=torch.float32, device=self.device)
+            return (res, list(none) if as_list else none) if lp else res
         if seed is None:
             gdev = generator.device if generator is not None else "cpu"
             seed = int(torch.randint(0, 2**62, (1,), generator=generator, device=gdev))
@@ -1025,17 +1176,24 @@ class DecodeSession:
         # A tensor prompt's finished rows keep generating until every row has finished, as with the host sampler, so
         # their tokens are needed: no EOS for the kernel there, and `done` is read off `out` at each sync instead.
         self.reset()
-        st = self._sampler_state(temperature, top_k, top_p, eos if as_list else -1)
+        st = self._sampler_state(temperature, top_k, top_p, eos if as_list else -1, ctl)
         st["rng"].copy_(torch.tensor([seed, 0], dtype=torch.long))
         st["out"].fill_(-1)
         st["done"].zero_()
+        if ctl is not None:  # (after _sampler_state: a capture's warm-up run has written all of them)
+            if ctl.penal:
+                st["hist"].copy_(sampling.prompt_hist(ids, n if as_list else None, st["hist"].shape[1]))
+            st["logprob"].fill_(math.nan)
         step = st["step"]
         if step is not None:
             step.fill_(1)
             self._step_host = [1] * B
         logits = self.prefill(ids, n if as_list else None)
-        sampling.sample_step(logits, temperature, top_k, top_p, st["rng"], st["ids"], st["out"], step, st["done"],
-                             st["params"][3])
+        if ctl is None:
+            sampling.sample_step(logits, temperature, top_k, top_p, st["rng"], st["ids"], st["out"], step, st["done"],
+                                 st["params"][3])
+        else:
+            self._sample_controlled(st, logits)
         st["rng"][1:].add_(1)
         made = 1  # tokens sampled per row
         upto = 0  # a paged cache has pages for the first `upto` fed tokens of every row
@@ -1063,15 +1221,17 @@ class DecodeSession:
             if self._step is not None:
                 self._step_host = [int(f >= made) for f in first]
             c.release(range(B), c._len)  # (pages reserved ahead for rows that finished early)
-            return [torch.cat([p, out[b, : min(first[b] + 1, made)].to(self.device, p.dtype)])
-                    for b, p in enumerate(prompts)]
+            res = [torch.cat([p, out[b, : min(first[b] + 1, made)].to(self.device, p.dtype)])
+                   for b, p in enumerate(prompts)]
+            return (res, [st["logprob"][b, : min(first[b] + 1, made)].clone() for b in range(B)]) if lp else res
         # tensor prompt: keep the steps up to the one at which every row had emitted EOS; the replays past it (up to
         # sync_every - 1) are dropped, from the cache too
         keep = min(max(first) + 1, made)
         c.pos.fill_(n[0] + keep - 1)
         c._len[:] = [n[0] + keep - 1] * B
         c.release(range(B), c._len)
-        return torch.cat([ids, out[:, :keep].to(self.device, ids.dtype)], 1)
+        res = torch.cat([ids, out[:, :keep].to(self.device, ids.dtype)], 1)
+        return (res, st["logprob"][:, :keep].clone()) if lp else res
 
     # ------------------------------------------------------------------ HIP path
     def _capture(self) -> None:

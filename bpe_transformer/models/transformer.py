@@ -236,6 +236,11 @@ class TransformerLM(nn.Module):
         prompt_lookup: "int | tuple[int, int] | None" = None,
         kv_layout: str = "slab",
         num_pages: int | None = None,
+        repetition_penalty: float = 1.0,
+        presence_penalty: float = 0.0,
+        frequency_penalty: float = 0.0,
+        logit_bias=None,
+        return_logprobs: bool = False,
     ) -> Tensor:
         """Autoregressive sampling (temperature, top-k, nucleus).  ``prompt``: ``[S]`` or ``[B, S]``.
 
@@ -279,8 +284,24 @@ class TransformerLM(nn.Module):
         tokens in the sequence's own prompt and output, and this model verifies them in one pass.  The output
         guarantees, the implied device sampler and the ``ValueError`` with ``top_k`` / ``top_p``, ``kv_dtype="fp8"``
         or ``weight_dtype="fp8"`` are those of ``draft_model``; the two cannot be combined (``ValueError``).
+
+        Sampling controls, all off by default (:meth:`DecodeSession.generate`; ``ops/sampling.py`` states the
+        function): ``repetition_penalty`` (> 0, over prompt and output), ``presence_penalty`` and
+        ``frequency_penalty`` (over the output), ``logit_bias`` (a ``{token: value}`` dict or a ``[V]`` tensor; ``-inf``
+        bans a token) and ``return_logprobs``, which makes the result ``(tokens, logprobs)`` with the log-probability
+        of every emitted token under the model's own distribution (not the warped one it was sampled from).  They
+        need the KV-cache path, work with either sampler -- with ``sampler="device"`` inside the captured step -- and
+        are not yet supported together with ``draft_model`` or ``prompt_lookup`` (``ValueError``).
         """
         assert sampler in ("host", "device"), "sampler: 'host' or 'device'"
+        controls = dict(repetition_penalty=repetition_penalty, presence_penalty=presence_penalty,
+                        frequency_penalty=frequency_penalty, logit_bias=logit_bias, return_logprobs=return_logprobs)
+        controlled = (repetition_penalty != 1.0 or presence_penalty != 0.0 or frequency_penalty != 0.0
+                      or logit_bias is not None or return_logprobs)
+        if controlled and (draft_model is not None or prompt_lookup is not None):
+            raise ValueError("repetition_penalty / presence_penalty / frequency_penalty / logit_bias / return_logprobs "
+                             f"with {'draft_model' if draft_model is not None else 'prompt_lookup'} are not supported "
+                             "yet: the verifier's p and q would both need the processing")
         if kv_dtype not in ("bf16", "fp8"):
             raise ValueError(f"kv_dtype: 'bf16' or 'fp8', got {kv_dtype!r}")
         if kv_layout not in ("slab", "paged"):
@@ -314,6 +335,8 @@ class TransformerLM(nn.Module):
             return self._generate_speculative(prompt, max_new_tokens, temperature, top_p, eos_token_id, generator,
                                               top_k, seed, draft_model, num_draft_tokens)
         kw = dict(top_k=top_k, sampler=sampler, seed=seed)
+        if controlled:
+            kw.update(controls)
         if isinstance(prompt, (list, tuple)):
             self._fence(self)
             longest = max(int(p.numel()) for p in prompt)
@@ -337,7 +360,11 @@ class TransformerLM(nn.Module):
             sess = DecodeSession(self, ids.shape[0], max_len=ids.shape[1] + max_new_tokens, kv_dtype=kv_dtype,
                                  weight_dtype=weight_dtype, kv_layout=kv_layout, num_pages=num_pages)
             out = sess.generate(ids, max_new_tokens, temperature, top_p, eos_token_id, generator, **kw)
+            if return_logprobs:
+                return (out[0][0], out[1][0]) if squeeze else out
             return out[0] if squeeze else out
+        assert not controlled or max_new_tokens <= 0, "the sampling controls need the KV-cache path (use_cache, and " \
+            "prompt + max_new_tokens within context_length)"
         assert sampler == "host" or max_new_tokens <= 0, "sampler='device' needs the KV-cache path (use_cache, and " \
             "prompt + max_new_tokens within context_length)"
         assert kv_dtype == "bf16" or max_new_tokens <= 0, "kv_dtype='fp8' needs the KV-cache path (use_cache, and " \

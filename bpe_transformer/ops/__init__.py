@@ -18,7 +18,8 @@ from .loss import IGNORE_INDEX, cross_entropy, lm_head_cross_entropy
 from .norm import rmsnorm
 from .optim import clip_grad_norm_, fused_adamw_step, grad_norm
 from .rope import apply_rope
-from .sampling import lookup_draft, philox_uniform, sample_logits, sample_step, spec_verify, spec_verify_step
+from .sampling import (logit_process, logit_process_reference, lookup_draft, philox_uniform, prompt_hist, sample_logits,
+                       sample_step, spec_verify, spec_verify_step, token_commit, token_commit_reference)
 from .softmax import softmax
 
 __all__ = [
@@ -40,9 +41,12 @@ __all__ = [
     "library_path",
     "lm_head_cross_entropy",
     "load",
+    "logit_process",
+    "logit_process_reference",
     "lookup_draft",
     "philox_uniform",
     "prefill_attention",
+    "prompt_hist",
     "rmsnorm",
     "sample_logits",
     "sample_step",
@@ -52,4 +56,6 @@ __all__ = [
     "silu",
     "softmax",
     "swiglu_gate",
+    "token_commit",
+    "token_commit_reference",
 ]

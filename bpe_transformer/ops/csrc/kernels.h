@@ -235,6 +235,41 @@ struct SampleArgs {
 };
 void launch_sample(const SampleArgs& a, int dtype, int B, hipStream_t s);
 
+// logit_process.hip (sampling controls; ops/sampling.py states the function).  logit_process: one workgroup per
+// logits row x [B][V] (row stride V, any element offset): out [B][V] of x's dtype (may be x; nullptr: none) takes
+// x + bias[v], the repetition penalty where hist[b][v] != 0 and the frequency / presence penalties on hist >> 1;
+// lse [B] (nullptr: none) takes the log-sum-exp of the unprocessed row.  hist int32 [B][V] and bias fp32 [V] are
+// optional.  An element with hist == 0 and bias == 0 keeps its bits.
+struct LogitArgs {
+    const void* x;
+    void* out;
+    const int* hist;
+    const float* bias;
+    float* lse;
+    int V;
+    float rp, inv_rp;  // the repetition penalty and 1 / rp, rounded on the host
+    float pp, fp;      // presence, frequency
+};
+void launch_logit_process(const LogitArgs& a, int dtype, int B, hipStream_t s);
+// token_commit: one thread per row.  count = rng[1]; tok = tokens[b][count] (count inside [0, tok_n), 0 <= tok < V,
+// else nothing: -1 marks an idle row) -> hist[b][tok] += 2 and, with count < lp_n, logprob[b][count] =
+// float(raw[b][tok]) - lse[b].  hist, or logprob (with raw and lse), may be nullptr.
+struct CommitArgs {
+    const long long* tokens;
+    long tok_ld;
+    int tok_n;
+    const long long* rng;
+    int* hist;
+    int V;
+    const void* raw;  // [B][V], DT_F32 / DT_BF16
+    int dtype;
+    const float* lse;
+    float* logprob;
+    long lp_ld;
+    int lp_n;
+};
+void launch_token_commit(const CommitArgs& a, int B, hipStream_t s);
+
 // spec_verify.hip (speculative decoding: which draft tokens stand, and the token after them; ops/sampling.py states
 // the function).  One workgroup per sequence.  t [B][K + 1][V] target logits, s [B][K][V] draft logits (sampling
 // only), both dense rows of one dtype; draft[b * draft_ld + i] = draft token i + 1.  Uniforms: `ua` [B][K] and `us`

@@ -1432,6 +1432,98 @@ void sample_step(const at::Tensor& logits, double temperature, int64_t top_k, do
     launch_sample(a, dt_code(logits), (int)B, cur_stream());
 }
 
+// ---------------------------------------------------------------- sampling controls (logit_process.hip)
+// bias + repetition / presence / frequency penalties into `out`, the raw row's log-sum-exp into `lse`
+void logit_process(const at::Tensor& logits, const c10::optional<at::Tensor>& hist,
+                   const c10::optional<at::Tensor>& bias, double rp, double inv_rp, double pp, double fp,
+                   const c10::optional<at::Tensor>& out, const c10::optional<at::Tensor>& lse) {
+    check_cuda(logits, "logits");
+    TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(), "logit_process: logits must be contiguous [B, V]");
+    const int64_t B = logits.size(0), V = logits.size(1);
+    TORCH_CHECK(V >= 1 && V <= SAMPLE_MAX_V, "logit_process: 1 <= V <= ", SAMPLE_MAX_V);
+    TORCH_CHECK(rp > 0 && inv_rp > 0, "logit_process: repetition_penalty must be > 0");
+    LogitArgs a{};
+    a.x = logits.data_ptr();
+    a.V = (int)V;
+    a.rp = (float)rp;
+    a.inv_rp = (float)inv_rp;
+    a.pp = (float)pp;
+    a.fp = (float)fp;
+    const int dt = dt_code(logits);
+    if (hist.has_value()) {
+        TORCH_CHECK(hist->is_cuda() && hist->scalar_type() == at::kInt && hist->is_contiguous() && hist->dim() == 2 &&
+                        hist->size(0) == B && hist->size(1) == V,
+                    "logit_process: hist must be a contiguous int32 GPU tensor [B, V]");
+        a.hist = hist->data_ptr<int>();
+    }
+    if (bias.has_value()) {
+        TORCH_CHECK(bias->is_cuda() && bias->scalar_type() == at::kFloat && bias->is_contiguous() &&
+                        bias->dim() == 1 && bias->size(0) == V,
+                    "logit_process: bias must be a contiguous fp32 GPU tensor [V]");
+        a.bias = bias->data_ptr<float>();
+    }
+    if (out.has_value()) {
+        TORCH_CHECK(out->is_cuda() && out->scalar_type() == logits.scalar_type() && out->is_contiguous() &&
+                        out->dim() == 2 && out->size(0) == B && out->size(1) == V,
+                    "logit_process: out must be a contiguous GPU tensor [B, V] of the logits' dtype");
+        a.out = out->data_ptr();
+    }
+    if (lse.has_value()) {
+        TORCH_CHECK(lse->is_cuda() && lse->scalar_type() == at::kFloat && lse->is_contiguous() && lse->numel() == B,
+                    "logit_process: lse must be a contiguous fp32 GPU tensor [B]");
+        a.lse = lse->data_ptr<float>();
+    }
+    DevGuard g(logits.device());
+    launch_logit_process(a, dt, (int)B, cur_stream());
+}
+
+// after sample_step: the token of column rng[1] into the history and its log-probability into `logprob`
+void token_commit(const at::Tensor& tokens, const at::Tensor& rng, const c10::optional<at::Tensor>& hist,
+                  const c10::optional<at::Tensor>& raw_logits, const c10::optional<at::Tensor>& lse,
+                  const c10::optional<at::Tensor>& logprob) {
+    TORCH_CHECK(tokens.is_cuda() && tokens.scalar_type() == at::kLong && tokens.dim() == 2 &&
+                    (tokens.size(1) <= 1 || tokens.stride(1) == 1),
+                "token_commit: tokens must be an int64 GPU tensor [B, N], rows dense");
+    const int64_t B = tokens.size(0);
+    TORCH_CHECK(rng.is_cuda() && rng.scalar_type() == at::kLong && rng.is_contiguous() && rng.numel() == 2,
+                "token_commit: rng must be a contiguous int64 GPU tensor (seed, count)");
+    TORCH_CHECK(hist.has_value() || logprob.has_value(), "token_commit: nothing to do without hist or logprob");
+    CommitArgs a{};
+    a.tokens = (const long long*)tokens.data_ptr<int64_t>();
+    a.tok_ld = tokens.stride(0);
+    a.tok_n = (int)std::min<int64_t>(tokens.size(1), INT32_MAX);
+    a.rng = (const long long*)rng.data_ptr<int64_t>();
+    int64_t V = -1;
+    if (hist.has_value()) {
+        TORCH_CHECK(hist->is_cuda() && hist->scalar_type() == at::kInt && hist->is_contiguous() && hist->dim() == 2 &&
+                        hist->size(0) == B, "token_commit: hist must be a contiguous int32 GPU tensor [B, V]");
+        V = hist->size(1);
+        a.hist = hist->data_ptr<int>();
+    }
+    if (logprob.has_value()) {
+        TORCH_CHECK(raw_logits.has_value() && lse.has_value(), "token_commit: logprob needs raw_logits and lse");
+        TORCH_CHECK(raw_logits->is_cuda() && raw_logits->dim() == 2 && raw_logits->is_contiguous() &&
+                        raw_logits->size(0) == B && (V < 0 || raw_logits->size(1) == V),
+                    "token_commit: raw_logits must be a contiguous GPU tensor [B, V]");
+        V = raw_logits->size(1);
+        a.raw = raw_logits->data_ptr();
+        a.dtype = dt_code(*raw_logits);
+        TORCH_CHECK(lse->is_cuda() && lse->scalar_type() == at::kFloat && lse->is_contiguous() && lse->numel() == B,
+                    "token_commit: lse must be a contiguous fp32 GPU tensor [B]");
+        a.lse = lse->data_ptr<float>();
+        TORCH_CHECK(logprob->is_cuda() && logprob->scalar_type() == at::kFloat && logprob->dim() == 2 &&
+                        logprob->size(0) == B && (logprob->size(1) <= 1 || logprob->stride(1) == 1),
+                    "token_commit: logprob must be an fp32 GPU tensor [B, N], rows dense");
+        a.logprob = logprob->data_ptr<float>();
+        a.lp_ld = logprob->stride(0);
+        a.lp_n = (int)std::min<int64_t>(logprob->size(1), INT32_MAX);
+    }
+    TORCH_CHECK(V >= 1 && V <= SAMPLE_MAX_V, "token_commit: 1 <= V <= ", SAMPLE_MAX_V);
+    a.V = (int)V;
+    DevGuard g(tokens.device());
+    launch_token_commit(a, (int)B, cur_stream());
+}
+
 // ---------------------------------------------------------------- speculative verification (spec_verify.hip)
 // dense rows: [B, R, V] whose rows follow each other V elements apart, from any element offset
 bool spec_dense(const at::Tensor& x) {
@@ -1580,6 +1672,10 @@ TORCH_LIBRARY(bpe_hip, m) {
     m.def("sample_logits(Tensor logits, float temperature, int top_k, float top_p, Tensor u) -> Tensor");
     m.def("sample_step(Tensor logits, float temperature, int top_k, float top_p, Tensor rng, Tensor(a!) ids, "
           "Tensor(b!) out, Tensor(c!)? step, Tensor(d!) done, int eos, int col=-1) -> ()");
+    m.def("logit_process(Tensor logits, Tensor? hist, Tensor? bias, float rp, float inv_rp, float pp, float fp, "
+          "Tensor(a!)? out, Tensor(b!)? lse) -> ()");
+    m.def("token_commit(Tensor tokens, Tensor rng, Tensor(a!)? hist, Tensor? raw_logits, Tensor? lse, "
+          "Tensor(b!)? logprob) -> ()");
     m.def("spec_verify(Tensor target_logits, Tensor draft_tokens, Tensor? draft_logits, float temperature, "
           "Tensor? ua, Tensor? us, bool point_mass=False) -> (Tensor, Tensor)");
     m.def("spec_verify_step(Tensor target_logits, Tensor? draft_logits, float temperature, Tensor rng, "
@@ -1727,6 +1823,8 @@ TORCH_LIBRARY_IMPL(bpe_hip, CUDA, m) {
     m.impl("kv_dequant", &kv_dequant);
     m.impl("sample_logits", &sample_logits);
     m.impl("sample_step", &sample_step);
+    m.impl("logit_process", &logit_process);
+    m.impl("token_commit", &token_commit);
     m.impl("spec_verify", &spec_verify);
     m.impl("spec_verify_step", &spec_verify_step);
     m.impl("lookup_draft", &lookup_draft);

@@ -87,6 +87,36 @@ With ``K`` drafts and n-gram bounds ``1 <= n_lo <= n_hi``:
 Any drafts are valid for the verifier: the proposal is deterministic, so with ``point_mass=True`` the emitted tokens
 remain the target's (greedy) or distributed as the target's (sampling) whatever is proposed.  :func:`lookup_draft`
 writes ``d`` into ``win[b, 1..K]`` inside the captured round; token ids must fit int32.
+
+**Sampling controls** (``csrc/logit_process.hip``: logit bias, the repetition penalty of Keskar et al., "CTRL", 2019,
+as HF / vLLM apply it over prompt and output, and the OpenAI / vLLM presence and frequency penalties over the output
+only).  The state of sequence ``b`` is one row of an int32 table ``hist [B, V]``: ``hist[b, v] = 2 * (times v was
+emitted so far) + (1 if v occurs in the prompt)``, so ``seen = hist != 0`` and ``c = hist >> 1``.
+
+:func:`logit_process` takes a row ``x [V]`` (fp32 or bf16), an optional ``bias [V]`` (fp32, shared by all rows) and
+``rp > 0``, ``pp``, ``fp``; all arithmetic is fp32, in this order:
+
+1. ``y = x + bias[v]``.  A ``-inf`` bias is allowed and stays ``-inf`` through every later step; NaN is not supported.
+2. Where ``seen``: ``y = y * (1 / rp)`` if ``y > 0`` else ``y * rp``; ``1 / rp`` is computed once on the host in fp32
+   and passed in, so nothing divides on the device.
+3. ``y = y - fp * c - pp * (c > 0)``.
+4. ``y`` is rounded once to the row's dtype and written to ``out [B, V]``, which may be the input itself.
+
+An element with ``hist == 0`` and ``bias == 0`` (or without either) comes out bit-identical to its input -- its
+arithmetic is skipped, so ``-0.0`` stays ``-0.0``.  The same pass computes ``lse[b] = logsumexp(x[b, :])`` over the
+**unprocessed** row: an fp32 max and an fp32 sum of ``exp(x - max)``, a ``-inf`` logit contributing 0 (a row of
+``-inf`` has ``lse = -inf``).  Any of ``hist``, ``bias``, ``out``, ``lse`` may be absent: with only ``lse`` this is a
+log-sum-exp, with only the penalties no ``lse`` is written.
+
+:func:`token_commit` runs after :func:`sample_step` and before the caller advances ``rng[1]``.  For row ``b``, ``tok =
+tokens[b, count]`` with ``count = rng[1]``; if ``tok >= 0`` (the sampler wrote a token: an idle row holds the ``-1``
+``sample_step`` leaves in that column and writes nothing) then ``hist[b, tok] += 2`` and ``logprob[b, count] =
+float(raw_logits[b, tok]) - lse[b]``.  Either half (``hist``; ``raw_logits`` / ``lse`` / ``logprob``) may be absent, and
+a ``count`` outside ``logprob``'s columns writes nothing.  The log-prob is the token's log-probability under the
+model's own distribution -- unprocessed logits, T = 1, no filters -- and **not** under the warped distribution the
+token was sampled from (bias, penalties, temperature, top-k / top-p).
+
+:func:`prompt_hist` builds the table of a fresh batch: bit 0 for every prompt token, right-padding untouched.
 """
 
 from __future__ import annotations
@@ -385,3 +415,112 @@ def lookup_draft_reference(prompt, n_prompt, out, n_out, win, step, done, n_hi: 
                 end = int((m == best).nonzero()[-1])  # the most recent of the longest
                 start, p = end + 1, L - 1 - end
         win[b, 1:] = h[start + torch.arange(K, device=h.device) % p]
+
+
+# ---------------------------------------------------------------- sampling controls
+def _f32(v: float) -> float:
+    """``v`` rounded to fp32 (as a Python float)."""
+    return float(torch.tensor(float(v), dtype=torch.float32))
+
+
+def _inv_f32(rp: float) -> float:
+    """``1 / rp`` as the kernel receives it: one fp32 division of the fp32-rounded ``rp``, on the host."""
+    return float(torch.tensor(1.0, dtype=torch.float32) / torch.tensor(float(rp), dtype=torch.float32))
+
+
+def _check_process(logits: Tensor, hist, bias, rp: float, out, lse) -> None:
+    assert logits.dim() == 2 and logits.shape[1] >= 1 and logits.is_contiguous(), "logits: contiguous [B, V]"
+    assert logits.dtype in (torch.bfloat16, torch.float32), "logits: bf16 or fp32"
+    if not float(rp) > 0:
+        raise ValueError(f"repetition_penalty must be > 0, got {rp}")
+    B, V = logits.shape
+    assert hist is None or (hist.dtype == torch.int32 and tuple(hist.shape) == (B, V)), "hist: int32 [B, V]"
+    assert bias is None or (bias.dtype == torch.float32 and tuple(bias.shape) == (V,)), "bias: fp32 [V]"
+    assert out is None or (out.dtype == logits.dtype and tuple(out.shape) == (B, V)), "out: [B, V] of the logits' dtype"
+    assert lse is None or (lse.dtype == torch.float32 and lse.numel() == B), "lse: fp32 [B]"
+
+
+def logit_process(logits: Tensor, hist: Tensor | None = None, bias: Tensor | None = None,
+                  repetition_penalty: float = 1.0, presence_penalty: float = 0.0, frequency_penalty: float = 0.0,
+                  out: Tensor | None = None, lse: Tensor | None = None) -> None:
+    """Bias and penalties (module docstring, "Sampling controls") of ``logits [B, V]`` into ``out [B, V]`` (may be
+    ``logits``), and the log-sum-exp of the unprocessed rows into ``lse [B]``; ``hist`` int32 ``[B, V]``, ``bias``
+    fp32 ``[V]``.  Whatever is ``None`` is left out."""
+    _check_process(logits, hist, bias, repetition_penalty, out, lse)
+    if logits.is_cuda:
+        ops().logit_process(logits, hist, bias, _f32(repetition_penalty), _inv_f32(repetition_penalty),
+                            float(presence_penalty), float(frequency_penalty), out, lse)
+        return
+    logit_process_reference(logits, hist, bias, repetition_penalty, presence_penalty, frequency_penalty, out, lse)
+
+
+def logit_process_reference(logits, hist=None, bias=None, repetition_penalty=1.0, presence_penalty=0.0,
+                            frequency_penalty=0.0, out=None, lse=None) -> None:
+    """The same function in torch: fp32 arithmetic in the kernel's order (without relying on FMA), one rounding to
+    the row's dtype, untouched elements copied."""
+    x = logits.float()
+    if lse is not None:
+        m = x.amax(-1)
+        s = torch.exp(x - m[:, None]).sum(-1, dtype=torch.float32)  # exp(-inf) = 0
+        lse.view(-1).copy_(torch.where(m == -torch.inf, m, m + torch.log(s)))
+    if out is None:
+        return
+    y = x
+    touched = torch.zeros_like(x, dtype=torch.bool)
+    if bias is not None:
+        y = y + bias[None, :]
+        touched = touched | (bias != 0)[None, :]
+    if hist is not None:
+        one = torch.ones((), dtype=torch.float32, device=x.device)
+        rp, inv = one * _f32(repetition_penalty), one * _inv_f32(repetition_penalty)
+        pp, fp = one * _f32(presence_penalty), one * _f32(frequency_penalty)
+        seen = hist != 0
+        c = (hist >> 1).float()
+        y = torch.where(seen, torch.where(y > 0, y * inv, y * rp), y)
+        y = torch.where(c > 0, (y - fp * c) - pp, y)
+        touched = touched | seen
+    out.copy_(torch.where(touched, y.to(logits.dtype), logits))
+
+
+def token_commit(tokens: Tensor, rng: Tensor, hist: Tensor | None = None, raw_logits: Tensor | None = None,
+                 lse: Tensor | None = None, logprob: Tensor | None = None) -> None:
+    """After :func:`sample_step` (module docstring, "Sampling controls"): ``tokens`` int64 ``[B, N]`` is its ``out``
+    and ``rng`` its ``(seed, count)``.  Adds the token of column ``count`` to ``hist`` int32 ``[B, V]`` and writes
+    its log-probability ``float(raw_logits[b, tok]) - lse[b]`` into ``logprob`` fp32 ``[B, M]``, column ``count``; a
+    row that holds ``-1`` there writes nothing.  ``hist``, or ``raw_logits`` / ``lse`` / ``logprob``, may be ``None``."""
+    assert tokens.dim() == 2 and tokens.dtype == torch.long, "tokens: int64 [B, N]"
+    assert hist is not None or logprob is not None, "token_commit: hist, logprob or both"
+    assert logprob is None or (raw_logits is not None and lse is not None), "logprob needs raw_logits and lse"
+    if tokens.is_cuda:
+        if logprob is None:
+            raw_logits = lse = None
+        ops().token_commit(tokens, rng, hist, raw_logits, lse, logprob)
+        return
+    token_commit_reference(tokens, rng, hist, raw_logits, lse, logprob)
+
+
+def token_commit_reference(tokens, rng, hist=None, raw_logits=None, lse=None, logprob=None) -> None:
+    count = int(rng[1])
+    if not 0 <= count < tokens.shape[1]:
+        return
+    tok = tokens[:, count]
+    rows = (tok >= 0).nonzero().flatten()
+    tok = tok[rows]
+    if hist is not None:
+        hist[rows, tok] += 2
+    if logprob is not None and count < logprob.shape[1]:
+        logprob[rows, count] = raw_logits[rows, tok].float() - lse.view(-1)[rows]
+
+
+def prompt_hist(ids: Tensor, lengths, V: int) -> Tensor:
+    """The history table of a fresh batch: int32 ``[B, V]`` with bit 0 set for every token of ``ids[b, :lengths[b]]``
+    (``ids`` int64 ``[B, T]``, right-padded; ``lengths`` ``None``: the whole row).  The padding is not read."""
+    B, T = ids.shape
+    hist = torch.zeros(B, int(V), dtype=torch.int32, device=ids.device)
+    valid = torch.ones(B, T, dtype=torch.bool, device=ids.device)
+    if lengths is not None:
+        n = torch.as_tensor(lengths, device=ids.device).reshape(B, 1)
+        valid = torch.arange(T, device=ids.device)[None, :] < n
+    rows = torch.arange(B, device=ids.device)[:, None].expand(B, T)
+    hist[rows[valid], ids[valid]] = 1
+    return hist

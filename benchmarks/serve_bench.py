@@ -1,0 +1,153 @@
+"""Continuous batching benchmark: the request engine (``models/serving.py``) against static batching, and the per-row
+sampling graph against the scalar one.
+
+A fixed seeded trace of ``--requests`` requests (prompts of 16-512 tokens, ``max_new_tokens`` of 16-256, all present
+at time 0, one sampling parameter set, no EOS) is served two ways on the same model in one process, alternating:
+
+(a) ``engine``: ``ServingEngine(batch=B)``, slab cache, ``run()`` until the trace is drained;
+(b) ``static``: the same requests through ``DecodeSession.generate(sampler="device")`` in arrival-order groups of
+    ``B`` -- every group starts together and runs until its longest ``max_new_tokens``.
+
+Tokens per second count each request's own ``max_new_tokens`` on both sides (what a static group generates past a
+request's limit is waste).  One JSON line per batch with the medians and every round.
+
+(c) ``step``: the captured step of the per-row graph (decode -> ``sample_rows``) against the scalar graph (decode ->
+    ``sample_step`` -> ``rng[1] += 1``; ``sample_bench.py``'s step) at the same batch and cache fill: microseconds per
+    replay over ``--iters`` replays, device events, alternating rounds.
+
+    python benchmarks/serve_bench.py --model gpt2-small --batch 8 64
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+from bpe_transformer.models import DecodeSession, SamplingParams, ServingEngine, TransformerLM, get_preset  # noqa: E402
+
+T, TOP_K = 0.8, 50
+
+
+def trace(n, vocab, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    lens = torch.randint(16, 513, (n,), generator=g).tolist()
+    news = torch.randint(16, 257, (n,), generator=g).tolist()
+    return [(torch.randint(0, vocab, (ln,), generator=g), nw) for ln, nw in zip(lens, news)]
+
+
+def run_engine(eng, reqs):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for i, (p, new) in enumerate(reqs):
+        eng.submit(p, SamplingParams(temperature=T, top_k=TOP_K, seed=i, max_new_tokens=new))
+    outs = eng.run()
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    assert sum(len(o.tokens) for o in outs.values()) == sum(n for _, n in reqs)
+    return dt
+
+
+def run_static(sess, reqs, B):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for g0 in range(0, len(reqs), B):
+        group = reqs[g0 : g0 + B]
+        pad = [group[-1]] * (B - len(group))  # (a short last group: the session has B rows)
+        sess.generate([p for p, _ in group + pad], max(n for _, n in group), temperature=T, top_k=TOP_K,
+                      sampler="device", seed=g0)
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def serve_arm(model, cfg, B, reqs, rounds, sync_every):
+    max_len = max(p.numel() + n for p, n in reqs)
+    eng = ServingEngine(model, batch=B, max_len=max_len, sync_every=sync_every)
+    # (a static group needs room for its longest prompt plus its longest continuation, on every row)
+    sess = DecodeSession(model, B, max_len=max(p.numel() for p, _ in reqs) + max(n for _, n in reqs), ragged=True)
+    run_engine(eng, reqs[:B])  # capture and first-use costs outside the timed runs
+    run_static(sess, reqs[:B], B)
+    e, s = [], []
+    for _ in range(rounds):
+        s.append(run_static(sess, reqs, B))
+        e.append(run_engine(eng, reqs))
+    useful = sum(n for _, n in reqs)
+    me, ms = statistics.median(e), statistics.median(s)
+    print(json.dumps({"arm": "serve", "batch": B, "requests": len(reqs), "useful_tokens": useful,
+                      "sync_every": sync_every, "engine_tok_s": round(useful / me, 1),
+                      "static_tok_s": round(useful / ms, 1), "engine_s_rounds": [round(x, 4) for x in e],
+                      "static_s_rounds": [round(x, 4) for x in s], "speedup": round(ms / me, 3),
+                      "captures": eng.captures}), flush=True)
+    del eng, sess
+    torch.cuda.empty_cache()
+
+
+def event_us(fn, iters):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / iters * 1e3
+
+
+def step_arm(model, cfg, B, prompt_len, iters, rounds):
+    room = prompt_len + 16 + (rounds + 1) * iters
+    prompt = torch.randint(0, cfg.vocab_size, (B, prompt_len))
+    sess = DecodeSession(model, B, max_len=room, ragged=True)
+    sess.generate(list(prompt), 8, temperature=T, top_k=TOP_K, sampler="device", seed=1)  # prefill + capture
+    st = sess._samp
+    st["done"].zero_()
+    sess._step.fill_(1)
+    eng = ServingEngine(model, batch=B, max_len=room, sync_every=8)
+    for i in range(B):
+        eng.submit(prompt[i], SamplingParams(temperature=T, top_k=TOP_K, seed=i, max_new_tokens=room - prompt_len))
+    eng.step()  # admits all B, 8 tokens each: the same cache fill
+    scalar = lambda: sess._device_step(st)  # noqa: E731
+    rows = lambda: eng.session._device_step_rows(eng._st)  # noqa: E731
+    a, b = [], []
+    for fn in (scalar, rows):
+        event_us(fn, 8)
+    for _ in range(rounds):
+        a.append(event_us(scalar, iters))
+        b.append(event_us(rows, iters))
+    assert int(eng._st["table"].done.sum()) == 0, "a request ended inside the timed replays"
+    ma, mb = statistics.median(a), statistics.median(b)
+    print(json.dumps({"arm": "step", "batch": B, "prompt": prompt_len, "iters": iters,
+                      "scalar_step_us": round(ma, 2), "rows_step_us": round(mb, 2), "rows_minus_scalar_us": round(mb - ma, 2),
+                      "scalar_us_rounds": [round(x, 2) for x in a], "rows_us_rounds": [round(x, 2) for x in b]}),
+          flush=True)
+    del sess, eng
+    torch.cuda.empty_cache()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="gpt2-small")
+    ap.add_argument("--batch", type=int, nargs="+", default=[8, 64])
+    ap.add_argument("--requests", type=int, default=64)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--sync-every", type=int, default=8)
+    ap.add_argument("--iters", type=int, default=100, help="replays per timed window of the step arm")
+    ap.add_argument("--prompt", type=int, default=128, help="prompt length of the step arm")
+    ap.add_argument("--arms", nargs="+", default=["serve", "step"], choices=["serve", "step"])
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), "serve_bench needs a GPU"
+    cfg = get_preset(a.model)
+    torch.manual_seed(0)
+    reqs = trace(a.requests, cfg.vocab_size)
+    with torch.no_grad():
+        model = TransformerLM.from_config(cfg, device="cuda", dtype=torch.bfloat16).eval()
+        for B in a.batch:
+            if "serve" in a.arms:
+                serve_arm(model, cfg, B, reqs, a.rounds, a.sync_every)
+            if "step" in a.arms:
+                step_arm(model, cfg, B, a.prompt, a.iters, a.rounds)
+
+
+if __name__ == "__main__":
+    main()

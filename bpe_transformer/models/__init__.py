@@ -13,6 +13,7 @@ from .layers import (
     TransformerBlock,
 )
 from .generation import DecodeSession, KVCache, PromptLookupSession, SpeculativeSession
+from .serving import RequestOutput, SamplingParams, ServingEngine
 from .transformer import TransformerLM
 
 __all__ = [
@@ -26,7 +27,10 @@ __all__ = [
     "MultiHeadSelfAttention",
     "PromptLookupSession",
     "RMSNorm",
+    "RequestOutput",
     "RotaryPositionalEmbedding",
+    "SamplingParams",
+    "ServingEngine",
     "SpeculativeSession",
     "SwiGLU",
     "TransformerBlock",

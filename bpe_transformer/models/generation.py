@@ -709,6 +709,7 @@ class DecodeSession:
         self._step_host = [1] * batch  # what _step holds
         self._graph = None
         self._samp = None  # the device sampler's buffers and graph (_sampler_state)
+        self._samp_rows = None  # the per-row device sampler's (_sampler_state_rows)
         if self.fast:
             self._prepare_weights()
         elif self.w8:  # the definition of the feature: the oracle math on the dequantised model
@@ -1125,6 +1126,108 @@ class DecodeSession:
         sampling.sample_step(src, temperature, top_k, top_p, st["rng"], st["ids"], st["out"], st["step"], st["done"], eos)
         if ctl.penal or ctl.logprobs:
             sampling.token_commit(st["out"], st["rng"], hist, logits, lse, st["logprob"] if ctl.logprobs else None)
+
+    # ------------------------------------------------------------------ per-row device sampler (continuous batching)
+    def _sampler_state_rows(self, penal: bool = False, logprobs: bool = False, bias: Tensor | None = None):
+        """The per-row device sampler's static state (ragged sessions; ``models/serving.py`` drives it): a
+        :class:`~bpe_transformer.ops.sampling.SamplingTable` whose ``step`` is the session's own decode step, ``ids
+        [B, 1]``, ``out [B, max_len]`` and, once a switch asks for them, ``hist [B, V]``, ``proc [B, V]``, ``lse [B]``,
+        ``logprob [B, max_len]``, ``bias [V]``.  With ``use_graph`` the step -- decode -> ``logit_process_rows`` ->
+        ``sample_rows`` -> ``token_commit_rows`` (:meth:`_sample_rows`) -- is captured like ``_capture``: one stream,
+        no parallel branches.  Every sampling parameter is read from the table, so the graph's key holds only the
+        structural switches -- a penalty table is in use (``penal``), log-probs are recorded (``logprobs``), there is
+        a shared bias.  A switch stays on once it is on; turning one on later captures once more, a change of
+        parameter values never does.  ``st["captures"]`` counts the graphs captured.  During a capture's warm-up run
+        every slot is idle, so it writes nothing the running requests would see."""
+        from ..ops.sampling import SamplingTable
+
+        assert self.ragged, "the per-row sampler needs DecodeSession(..., ragged=True)"
+        B, dev, V = self.batch, self.device, self.model.lm_head.weight.shape[0]
+        st = self._samp_rows
+        if st is None:
+            st = self._samp_rows = {
+                "table": SamplingTable(B, dev, self._step),
+                "ids": torch.zeros(B, 1, dtype=torch.long, device=dev),
+                "out": torch.full((B, self.max_len), -1, dtype=torch.long, device=dev),
+                "penal": False, "logprobs": False, "bias": None, "hist": None, "proc": None, "lse": None,
+                "logprob": None, "graph": None, "key": None, "captures": 0,
+            }
+            self._step_host = [0] * B  # (what the table's step holds: every slot idle)
+        if penal and not st["penal"]:
+            st["penal"] = True
+            st["hist"] = torch.zeros(B, V, dtype=torch.int32, device=dev)
+        if logprobs and not st["logprobs"]:
+            st["logprobs"] = True
+            st["lse"] = torch.zeros(B, dtype=torch.float32, device=dev)
+            st["logprob"] = torch.full((B, self.max_len), math.nan, dtype=torch.float32, device=dev)
+        if bias is not None:
+            if st["bias"] is None:
+                st["bias"] = torch.zeros(V, dtype=torch.float32, device=dev)
+            st["bias"].copy_(bias)
+        if (st["penal"] or st["bias"] is not None) and st["proc"] is None and self.fast:
+            st["proc"] = torch.empty(B, V, dtype=self.model.lm_head.weight.dtype, device=dev)
+        key = (st["penal"], st["logprobs"], st["bias"] is not None)
+        if self.use_graph and st["key"] != key:
+            t = st["table"]
+
+            def run():
+                self._sample_rows(st, self._forward_fast(st["ids"], "decode", step=self._step))
+
+            pos0, done0, step0 = self.cache.pos.clone(), t.done.clone(), t.step.clone()
+            t.done.fill_(1)
+            t.step.zero_()
+            s = torch.cuda.Stream(device=self.device)
+            s.wait_stream(torch.cuda.current_stream(self.device))
+            with torch.cuda.stream(s):
+                run()
+            torch.cuda.current_stream(self.device).wait_stream(s)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                run()
+            self.cache.pos.copy_(pos0)
+            t.done.copy_(done0)
+            t.step.copy_(step0)
+            st["graph"], st["key"] = g, key
+            st["captures"] += 1
+        return st
+
+    def _sample_rows(self, st, logits: Tensor, rows=None) -> None:
+        """One sampling step on the per-row state: ``logit_process_rows`` (only with a penalty table, a bias or
+        log-probs) -> ``sample_rows`` -> ``token_commit_rows`` (only with a penalty table or log-probs).  ``logits``
+        are the whole batch's, or with ``rows`` those of the named slots (an admission's prefill)."""
+        from ..ops import sampling
+
+        t = st["table"]
+        if logits.dtype not in (torch.bfloat16, torch.float32):  # (an fp64 model off the fast path)
+            logits = logits.float()
+        logits = logits.contiguous()
+        src = logits
+        proc = st["penal"] or st["bias"] is not None
+        if proc:
+            full = st["proc"]
+            if rows is not None or full is None or full.dtype != logits.dtype:
+                src = torch.empty_like(logits)  # (an admission's single row; off the fast path)
+            else:
+                src = full
+        if proc or st["logprobs"]:
+            sampling.logit_process_rows(logits, t, st["hist"], st["bias"], src if proc else None, st["lse"], rows)
+        sampling.sample_rows(src, t, st["ids"], st["out"], rows)
+        if st["penal"] or st["logprobs"]:
+            sampling.token_commit_rows(st["out"], t, st["hist"], logits, st["lse"], st["logprob"], rows)
+
+    def _device_step_rows(self, st) -> None:
+        """Decode the tokens in ``st["ids"]`` and sample the next ones into it: one replay on the fast path."""
+        if self.use_graph:
+            st["graph"].replay()
+            return
+        if self.fast:
+            logits = self._forward_fast(st["ids"], "decode", step=self._step)
+        else:  # the oracle math reads host lengths: the step comes back per token
+            rows = list(range(self.batch))
+            n = [int(x) for x in st["table"].step.tolist()]
+            logits = self._forward_reference(st["ids"], n, rows)
+            self.cache.advance(rows, n)
+        self._sample_rows(st, logits)
 
     def _device_step(self, st) -> None:
         """Decode the token in ``st["ids"]`` and sample the next one into it: one replay on the fast path."""

@@ -270,6 +270,57 @@ struct CommitArgs {
 };
 void launch_token_commit(const CommitArgs& a, int B, hipStream_t s);
 
+// Per-row forms for continuous batching (ops/sampling.py states the functions).  R rows are launched; launched row
+// r is slot b = rows[r] of B (rows == nullptr: b = r; a b outside [0, B) does nothing).  Everything shaped like the
+// logits ([R][V]: x, out, raw) is indexed by r, every per-slot table ([B], hist [B][V], tokens / logprob [B][N])
+// by b.  A slot with done[b] != 0 or step[b] == 0 is idle: it writes nothing at all.
+//
+// sample_rows.hip: sample_kernel's algorithm with every parameter read from the slot's tables, plus min_p.  The
+// uniform is u[r], or Philox keyed by seed[b] at counter (count[b], 0, 0).  An active slot writes ids[b] =
+// out[b][count[b]] = token, then count[b] += 1; token == eos[b] (eos >= 0) or count[b] >= limit[b] sets done[b] = 1
+// and step[b] = 0.
+struct SampleRowsArgs {
+    const void* logits;  // [R][V]
+    int V, B;
+    const int* rows;     // [R], optional
+    const float* u;      // [R], optional
+    const float* temperature;  // [B]  <= 0: greedy
+    const int* top_k;          // [B]  0: off
+    const double* top_p;       // [B]  >= 1: off
+    const float* min_p;        // [B]  <= 0: off
+    const long long* seed;     // [B]
+    long long* count;          // [B]
+    const int* limit;          // [B]
+    const int* eos;            // [B]  < 0: none
+    int* step;                 // [B]
+    int* done;                 // [B]
+    long long* ids;            // [B]
+    long long* out;            // [B][out_n], row stride out_ld
+    long out_ld;
+    int out_n;
+};
+void launch_sample_rows(const SampleRowsArgs& a, int dtype, int R, hipStream_t s);
+// logit_process with rp / inv_rp / pp / fp fp32 [B] in place of a.rp ...; a.lse and a.hist are per slot.  A slot
+// whose penalties are all neutral keeps every bit that the bias does not touch.
+struct LogitRowsArgs {
+    LogitArgs a;
+    const float *rp, *inv_rp, *pp, *fp;
+    const int* rows;
+    int B;
+    const int *step, *done;
+};
+void launch_logit_process_rows(const LogitRowsArgs& a, int dtype, int R, hipStream_t s);
+// token_commit at column count[b] - 1, iff count[b] > committed[b] (the sampler emitted since the slot's last
+// commit); then committed[b] = count[b].  a.rng is unused.
+struct CommitRowsArgs {
+    CommitArgs a;
+    const long long* count;
+    long long* committed;
+    const int* rows;
+    int B;
+};
+void launch_token_commit_rows(const CommitRowsArgs& a, int R, hipStream_t s);
+
 // spec_verify.hip (speculative decoding: which draft tokens stand, and the token after them; ops/sampling.py states
 // the function).  One workgroup per sequence.  t [B][K + 1][V] target logits, s [B][K][V] draft logits (sampling
 // only), both dense rows of one dtype; draft[b * draft_ld + i] = draft token i + 1.  Uniforms: `ua` [B][K] and `us`

@@ -23,10 +23,15 @@
 //
 // token_commit_kernel: one thread per row, plain vector load / add / store on hist (no two rows share an address).
 //
+// logit_process_rows_kernel / token_commit_rows_kernel (continuous batching): the same two row bodies with rp,
+// 1 / rp, pp, fp read from fp32 [B] tables, an optional rows map (launched row r -> slot b) and the column taken
+// from a per-slot counter; an idle slot (done, or step == 0) writes nothing.
+//
 // Resources (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage), no scratch in any of them:
-//   logit_process_kernel<__bf16>: 30 VGPRs, 62 SGPRs, 128 B LDS, occupancy 8 waves / SIMD
+//   logit_process_kernel<__bf16>: 32 VGPRs, 62 SGPRs, 128 B LDS, occupancy 8 waves / SIMD
 //   logit_process_kernel<float>:  30 VGPRs, 52 SGPRs, 128 B LDS, occupancy 8 waves / SIMD
 //   token_commit_kernel:           8 VGPRs, 22 SGPRs, 0 LDS
+//   logit_process_rows_kernel: as logit_process_kernel of the same type; token_commit_rows_kernel: 12 VGPRs, 22 SGPRs
 #include "sample_common.h"
 
 namespace bpe {
@@ -52,12 +57,12 @@ __device__ __forceinline__ float block_reduce(float v, float* red, int lane, int
     return r;
 }
 
+// One row: x / out row `row`, hist / lse row `slot` (the same number for logit_process_kernel), with the penalty
+// values of `a`.
 template <typename T>
-__global__ void __launch_bounds__(S_NT) logit_process_kernel(LogitArgs a) {
+__device__ __forceinline__ void logit_process_row(const LogitArgs& a, int row, int slot, float (&red)[2][S_NW]) {
     typedef RowT<T> R;
     typedef typename R::raw_t raw_t;
-    __shared__ float red[2][S_NW];
-    const int row = blockIdx.x;
     Ctx<T> c;
     c.init(a.x, (long)row, a.V, reinterpret_cast<char*>(&red[0][0]));
 
@@ -87,14 +92,14 @@ __global__ void __launch_bounds__(S_NT) logit_process_kernel(LogitArgs a) {
             }
         }
         s = block_reduce<false>(s, red[1], c.lane, c.wave);  // its barrier: every read of x is done
-        if (threadIdx.x == 0) a.lse[row] = m > NINF ? m + logf(s) : NINF;
+        if (threadIdx.x == 0) a.lse[slot] = m > NINF ? m + logf(s) : NINF;
     }
 
     if (a.out == nullptr) return;
     raw_t* orow = reinterpret_cast<raw_t*>(a.out) + (long)row * a.V;
     const int ooff = (int)((reinterpret_cast<uintptr_t>(orow) / sizeof(raw_t)) % R::VEC);
     const bool same = ooff == c.off;  // then virtual vector v of the output row is aligned too
-    const int* hrow = a.hist != nullptr ? a.hist + (long)row * a.V : nullptr;
+    const int* hrow = a.hist != nullptr ? a.hist + (long)slot * a.V : nullptr;
     const unsigned FULL = (1u << R::VEC) - 1;
     for (int tile = c.wave; tile < c.ntiles; tile += S_NW) {
         const int v = tile * 64 + c.lane;
@@ -139,23 +144,68 @@ __global__ void __launch_bounds__(S_NT) logit_process_kernel(LogitArgs a) {
     }
 }
 
-__global__ void __launch_bounds__(256) token_commit_kernel(CommitArgs a, int B) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    const long long count = a.rng[1];
+template <typename T>
+__global__ void __launch_bounds__(S_NT) logit_process_kernel(LogitArgs a) {
+    __shared__ float red[2][S_NW];
+    logit_process_row<T>(a, blockIdx.x, blockIdx.x, red);
+}
+
+// logit_process with the penalty values read per slot: launched row r is slot b = rows[r] (nullptr: r).  A slot that
+// is done or whose step is 0 writes nothing; a slot whose penalties are all neutral (rp = 1, pp = fp = 0) runs
+// without the history, so that only a bias touches its row.
+template <typename T>
+__global__ void __launch_bounds__(S_NT) logit_process_rows_kernel(LogitRowsArgs ra) {
+    __shared__ float red[2][S_NW];
+    const int r = blockIdx.x;
+    const int b = ra.rows != nullptr ? ra.rows[r] : r;
+    if (b < 0 || b >= ra.B) return;
+    if (ra.done[b] != 0 || ra.step[b] == 0) return;  // (the whole workgroup: no barrier is left behind)
+    LogitArgs a = ra.a;
+    if (a.hist != nullptr) {
+        a.rp = ra.rp[b];
+        a.inv_rp = ra.inv_rp[b];
+        a.pp = ra.pp[b];
+        a.fp = ra.fp[b];
+        if (a.rp == 1.f && a.pp == 0.f && a.fp == 0.f) a.hist = nullptr;
+    }
+    logit_process_row<T>(a, r, b, red);
+}
+
+// the body of both commit kernels: column `col` of row `row` of tokens / logprob, row `row` of raw, row `slot` of
+// hist and lse
+__device__ __forceinline__ void token_commit_row(const CommitArgs& a, int row, int slot, long long count) {
     if (count < 0 || count >= a.tok_n) return;
-    const long long tok = a.tokens[(long)b * a.tok_ld + count];
+    const long long tok = a.tokens[(long)slot * a.tok_ld + count];
     if (tok < 0 || tok >= a.V) return;  // -1: an idle row
     if (a.hist != nullptr) {
-        int* h = a.hist + (long)b * a.V + tok;
+        int* h = a.hist + (long)slot * a.V + tok;
         *h = *h + 2;
     }
     if (a.logprob != nullptr && count < a.lp_n) {
-        const long i = (long)b * a.V + tok;
+        const long i = (long)row * a.V + tok;
         const float x = a.dtype == DT_BF16 ? bf2f(reinterpret_cast<const u16*>(a.raw)[i])
                                            : reinterpret_cast<const float*>(a.raw)[i];
-        a.logprob[(long)b * a.lp_ld + count] = x - a.lse[b];
+        a.logprob[(long)slot * a.lp_ld + count] = x - a.lse[slot];
     }
+}
+
+// token_commit on a per-slot counter: slot b = rows[r] commits column count[b] - 1 iff count[b] has moved past
+// committed[b] -- the sampler emitted since the last commit -- and then sets committed[b] = count[b].
+__global__ void __launch_bounds__(256) token_commit_rows_kernel(CommitRowsArgs ra, int R) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R) return;
+    const int b = ra.rows != nullptr ? ra.rows[r] : r;
+    if (b < 0 || b >= ra.B) return;
+    const long long n = ra.count[b];
+    if (n <= ra.committed[b]) return;
+    ra.committed[b] = n;
+    token_commit_row(ra.a, r, b, n - 1);
+}
+
+__global__ void __launch_bounds__(256) token_commit_kernel(CommitArgs a, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    token_commit_row(a, b, b, a.rng[1]);
 }
 
 }  // namespace
@@ -172,4 +222,15 @@ void launch_logit_process(const LogitArgs& a, int dtype, int B, hipStream_t s) {
 void launch_token_commit(const CommitArgs& a, int B, hipStream_t s) {
     if (B == 0 || (a.hist == nullptr && a.logprob == nullptr)) return;
     token_commit_kernel<<<(B + 255) / 256, 256, 0, s>>>(a, B);
+}
+
+void launch_logit_process_rows(const LogitRowsArgs& a, int dtype, int R, hipStream_t s) {
+    if (R == 0 || (a.a.out == nullptr && a.a.lse == nullptr)) return;
+    if (dtype == DT_BF16) logit_process_rows_kernel<__bf16><<<R, S_NT, 0, s>>>(a);
+    else logit_process_rows_kernel<float><<<R, S_NT, 0, s>>>(a);
+}
+
+void launch_token_commit_rows(const CommitRowsArgs& a, int R, hipStream_t s) {
+    if (R == 0 || (a.a.hist == nullptr && a.a.logprob == nullptr)) return;
+    token_commit_rows_kernel<<<(R + 255) / 256, 256, 0, s>>>(a, R);
 }

@@ -1,4 +1,4 @@
-// Device helpers shared by sample.hip and spec_verify.hip: one 1024-thread workgroup per logits row.
+// Device helpers shared by sample.hip, sample_rows.hip and spec_verify.hip: one 1024-thread workgroup per logits row.
 //
 //   * RowT / Ctx: a row of bf16 or fp32 logits that starts at any element offset, addressed in "virtual" 16-byte
 //     vectors that ARE aligned (sample.hip's header comment has the scheme); nothing outside [0, V) is touched.
@@ -6,6 +6,7 @@
 //   * row_argmax: highest order-preserving key, lowest index among equals.
 //   * row_total / prefix_find: masses as 64-bit fixed point (z * 2^40, z <= 1).  Integer sums do not depend on the
 //     order of the adds, so totals and the index-order inverse-CDF pick give the same bits every run.
+//   * Filt / radix_select / cut_ties: the top-k and top-p cut; sample_row: one row's token, min-p included.
 //
 // Everything lives in an unnamed namespace: each including file gets its own copy.
 #pragma once
@@ -288,6 +289,172 @@ __device__ int prefix_find(const Ctx<T>& c, WF weight, TF target_of) {
 __device__ __forceinline__ u64 draw_target(float u, u64 M) {
     const u64 t = (u64)((double)u * (double)M);
     return t < M ? t : M - 1;  // u >= 1 (or its product rounding up to M): the last token with mass
+}
+
+// ---- the top-k / top-p cut (sample.hip's header comment, steps 2 and 3), shared by sample.hip and sample_rows.hip
+// keep iff key > K, or key == K at an index <= I  (K = 0, I = V - 1: everything)
+struct Filt {
+    unsigned K;
+    int I;
+    __device__ __forceinline__ bool has(unsigned key, int i) const { return key > K || (key == K && i <= I); }
+};
+
+// One radix select inside the filter `in`.  MASS = false: the k-th key in rank order (target = k, on counts).
+// MASS = true: the key at which the mass ranked before reaches P = ceil(top_p * Z), Z the mass inside `in`.
+// Returns the key K and r: of the tokens inside `in` with key == K (n of them), the first r by index stay.
+template <typename T, bool MASS>
+__device__ void radix_select(const Ctx<T>& c, Filt in, u64 target, double top_p, unsigned& K, unsigned& r,
+                             unsigned& n) {
+    typedef RowT<T> R;
+    unsigned* cnt = reinterpret_cast<unsigned*>(c.smem + L_CNT);
+    u64* mass = reinterpret_cast<u64*>(c.smem + L_MASS);
+    u64* sel = reinterpret_cast<u64*>(c.smem + L_SEL);
+    unsigned* cntr = reinterpret_cast<unsigned*>(c.smem + L_CNTR);
+    u64* sc = c.scal();
+    unsigned prefix = 0;
+    u64 above = 0;  // count / mass of the keys above the current prefix's range
+    unsigned bincnt = 0;
+    for (int level = 0; level < R::KB / 8; ++level) {
+        const int shift = R::KB - 8 * (level + 1);
+        for (int i = threadIdx.x; i < S_BINS * S_REP; i += S_NT) {
+            cnt[i] = 0;
+            if (MASS) mass[i] = 0;
+        }
+        __syncthreads();
+        for (int tile = c.wave; tile < c.ntiles; tile += S_NW) {
+            const int v = tile * 64 + c.lane;
+            if (v >= c.nvec) continue;
+            unsigned raw[R::VEC];
+            const unsigned m = c.load(v, raw);
+#pragma unroll
+            for (int e = 0; e < R::VEC; ++e) {
+                if (!(m >> e & 1)) continue;
+                const unsigned key = R::key(raw[e]);
+                if (!in.has(key, v * R::VEC + e - c.off)) continue;
+                if (level > 0 && (key >> (shift + 8)) != prefix) continue;
+                const int slot = (int)((key >> shift) & 255u) * S_REP + (c.lane & (S_REP - 1));
+                atomicAdd(&cnt[slot], 1u);
+                if (MASS) atomicAdd(&mass[slot], c.zq(raw[e]));
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < S_BINS) {  // sum the replicas, each thread starting at its own bank
+            const int t = threadIdx.x;
+            unsigned cc = 0;
+            u64 mm = 0;
+            for (int q = 0; q < S_REP; ++q) {
+                const int s = t * S_REP + ((q + t) & (S_REP - 1));
+                cc += cnt[s];
+                if (MASS) mm += mass[s];
+            }
+            cntr[t] = cc;
+            sel[t] = MASS ? mm : (u64)cc;
+        }
+        __syncthreads();
+        if (c.wave == 0) {  // bins from 255 down, four per lane
+            u64 s[4], t = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { s[j] = sel[255 - 4 * c.lane - j]; t += s[j]; }
+            const u64 incl = wave_scan64(t, c.lane);
+            if (MASS && level == 0) {
+                const u64 Z = __shfl(incl, 63, 64);
+                u64 P = (u64)ceil(top_p * (double)Z);
+                if (P > Z) P = Z;
+                if (P < 1) P = 1;  // the first token in rank order always stays
+                target = P;
+            }
+            const u64 need = target - above;
+            const u64 hit = __ballot(incl >= need);
+            // (no lane only on a row of NaNs, where Z = 0: take the lowest bin, which keeps everything)
+            const int first = hit ? __ffsll((long long)hit) - 1 : 63;
+            if (c.lane == first) {
+                u64 acc = incl - t;
+                int j = 0;
+                for (; j < 3; ++j) {
+                    if (acc + s[j] >= need) break;
+                    acc += s[j];
+                }
+                const int bin = 255 - 4 * c.lane - j;
+                sc[0] = (u64)bin;
+                sc[1] = above + acc;
+                sc[2] = (u64)cntr[bin];
+                sc[3] = target;
+            }
+        }
+        __syncthreads();
+        prefix = (prefix << 8) | (unsigned)sc[0];
+        above = sc[1];
+        bincnt = (unsigned)sc[2];
+        target = sc[3];
+    }
+    K = prefix;
+    n = bincnt;
+    if (!MASS) {
+        r = (unsigned)(target - above);
+    } else {
+        // tie j (0-based, by index) of the n at K has above + j * zK ranked before it: it stays iff that is < P
+        const u64 zk = (u64)(fminf(__expf((R::key_val(K) - c.xmax) * c.invT), 1.f) * S_FIX);
+        const u64 rem = target > above ? target - above : 1;
+        const u64 rr = zk ? (rem + zk - 1) / zk : (u64)n;
+        r = (unsigned)(rr < (u64)n ? rr : (u64)n);
+    }
+    if (r < 1) r = 1;
+    if (r > n) r = n;
+}
+
+// the index cutoff that keeps exactly the first r of the n tokens inside `in` with key == K
+template <typename T>
+__device__ Filt cut_ties(const Ctx<T>& c, Filt in, unsigned K, unsigned r, unsigned n) {
+    int I = (K == in.K) ? in.I : c.V - 1;
+    if (r < n) {
+        const int i = prefix_find(
+            c, [&](unsigned, unsigned key, int i) -> u64 { return (key == K && in.has(key, i)) ? 1 : 0; },
+            [&](u64 total) -> u64 { const u64 t = r - 1; return t < total ? t : total - 1; });
+        if (i >= 0) I = i;
+    }
+    return Filt{K, I};
+}
+
+// The token of one row: the argmax (T <= 0, and what every degenerate row falls back to: always inside [0, V)),
+// else the draw at the uniform `u` among what top-k, top-p and min-p keep.  min_p > 0 keeps, of those, a token iff
+// its fixed-point mass zq >= ceil(min_p * zq_max), zq_max the argmax's (2^40: the argmax always stays).
+template <typename T>
+__device__ int sample_row(Ctx<T>& c, float temperature, int top_k, double top_p, float min_p, float u) {
+    typedef RowT<T> R;
+    unsigned bk;
+    int bi;
+    row_argmax(c, bk, bi);
+    int tok = bi;
+    if (temperature > 0.f) {
+        c.xmax = R::key_val(bk);
+        c.invT = 1.f / temperature;
+        Filt f{0u, c.V - 1};
+        unsigned K, r, n;
+        if (top_k > 0 && top_k < c.V) {
+            radix_select<T, false>(c, f, (u64)top_k, 0.0, K, r, n);
+            f = cut_ties(c, f, K, r, n);
+        }
+        if (top_p < 1.0) {
+            radix_select<T, true>(c, f, 0, top_p, K, r, n);
+            f = cut_ties(c, f, K, r, n);
+        }
+        u64 zmin = 0;
+        if (min_p > 0.f) {
+            const u64 zmax = c.zq(c.at(bi));
+            zmin = (u64)ceil((double)min_p * (double)zmax);
+            if (zmin > zmax) zmin = zmax;
+        }
+        const int i = prefix_find(
+            c,
+            [&](unsigned raw, unsigned key, int i) -> u64 {
+                if (!f.has(key, i)) return 0;
+                const u64 z = c.zq(raw);
+                return z >= zmin ? z : 0;
+            },
+            [&](u64 M) -> u64 { return draw_target(u, M); });
+        if (i >= 0 && i < c.V) tok = i;
+    }
+    return tok;
 }
 
 }  // namespace

@@ -1524,6 +1524,174 @@ void token_commit(const at::Tensor& tokens, const at::Tensor& rng, const c10::op
     launch_token_commit(a, (int)B, cur_stream());
 }
 
+// ---------------------------------------------------------------- per-row sampling (sample_rows.hip, logit_process.hip)
+// a contiguous per-slot table [B] of the given type on the GPU
+bool rows_tab(const at::Tensor& x, at::ScalarType t, int64_t B) {
+    return x.is_cuda() && x.scalar_type() == t && x.is_contiguous() && x.numel() == B;
+}
+// the optional rows map: int32 [R]; returns its pointer (nullptr: identity, which needs R == B)
+const int* rows_map(const c10::optional<at::Tensor>& rows, int64_t R, int64_t B, const char* op) {
+    if (!rows.has_value()) {
+        TORCH_CHECK(R == B, op, ": without a rows map the logits must have one row per slot");
+        return nullptr;
+    }
+    TORCH_CHECK(rows_tab(*rows, at::kInt, R), op, ": rows must be a contiguous int32 GPU tensor [R]");
+    return rows->data_ptr<int>();
+}
+
+void sample_rows(const at::Tensor& logits, const c10::optional<at::Tensor>& rows, const c10::optional<at::Tensor>& u,
+                 const at::Tensor& temperature, const at::Tensor& top_k, const at::Tensor& top_p,
+                 const at::Tensor& min_p, const at::Tensor& seed, at::Tensor count, const at::Tensor& limit,
+                 const at::Tensor& eos, at::Tensor step, at::Tensor done, at::Tensor ids, at::Tensor out) {
+    check_cuda(logits, "logits");
+    TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(), "sample_rows: logits must be contiguous [R, V]");
+    const int64_t R = logits.size(0), V = logits.size(1), B = done.numel();
+    TORCH_CHECK(V >= 1 && V <= SAMPLE_MAX_V, "sample_rows: 1 <= V <= ", SAMPLE_MAX_V);
+    TORCH_CHECK(B >= 1 && B <= INT32_MAX, "sample_rows: at least one slot");
+    SampleRowsArgs a{};
+    a.logits = logits.data_ptr();
+    a.V = (int)V;
+    a.B = (int)B;
+    a.rows = rows_map(rows, R, B, "sample_rows");
+    if (u.has_value()) {
+        TORCH_CHECK(rows_tab(*u, at::kFloat, R), "sample_rows: u must be a contiguous fp32 GPU tensor [R]");
+        a.u = u->data_ptr<float>();
+    }
+    TORCH_CHECK(rows_tab(temperature, at::kFloat, B) && rows_tab(min_p, at::kFloat, B),
+                "sample_rows: temperature and min_p must be contiguous fp32 GPU tensors [B]");
+    TORCH_CHECK(rows_tab(top_p, at::kDouble, B), "sample_rows: top_p must be a contiguous fp64 GPU tensor [B]");
+    TORCH_CHECK(rows_tab(top_k, at::kInt, B) && rows_tab(limit, at::kInt, B) && rows_tab(eos, at::kInt, B) &&
+                    rows_tab(step, at::kInt, B) && rows_tab(done, at::kInt, B),
+                "sample_rows: top_k, limit, eos, step and done must be contiguous int32 GPU tensors [B]");
+    TORCH_CHECK(rows_tab(seed, at::kLong, B) && rows_tab(count, at::kLong, B) && rows_tab(ids, at::kLong, B),
+                "sample_rows: seed, count and ids must be contiguous int64 GPU tensors [B]");
+    TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kLong && out.dim() == 2 && out.size(0) == B &&
+                    (out.size(1) <= 1 || out.stride(1) == 1), "sample_rows: out must be int64 [B, N], rows dense");
+    a.temperature = temperature.data_ptr<float>();
+    a.top_k = top_k.data_ptr<int>();
+    a.top_p = top_p.data_ptr<double>();
+    a.min_p = min_p.data_ptr<float>();
+    a.seed = (const long long*)seed.data_ptr<int64_t>();
+    a.count = (long long*)count.data_ptr<int64_t>();
+    a.limit = limit.data_ptr<int>();
+    a.eos = eos.data_ptr<int>();
+    a.step = step.data_ptr<int>();
+    a.done = done.data_ptr<int>();
+    a.ids = (long long*)ids.data_ptr<int64_t>();
+    a.out = (long long*)out.data_ptr<int64_t>();
+    a.out_ld = out.stride(0);
+    a.out_n = (int)std::min<int64_t>(out.size(1), INT32_MAX);
+    DevGuard g(logits.device());
+    launch_sample_rows(a, dt_code(logits), (int)R, cur_stream());
+}
+
+void logit_process_rows(const at::Tensor& logits, const c10::optional<at::Tensor>& rows,
+                        const c10::optional<at::Tensor>& hist, const c10::optional<at::Tensor>& bias,
+                        const at::Tensor& rp, const at::Tensor& inv_rp, const at::Tensor& pp, const at::Tensor& fp,
+                        const at::Tensor& step, const at::Tensor& done, const c10::optional<at::Tensor>& out,
+                        const c10::optional<at::Tensor>& lse) {
+    check_cuda(logits, "logits");
+    TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(), "logit_process_rows: logits must be contiguous [R, V]");
+    const int64_t R = logits.size(0), V = logits.size(1), B = done.numel();
+    TORCH_CHECK(V >= 1 && V <= SAMPLE_MAX_V, "logit_process_rows: 1 <= V <= ", SAMPLE_MAX_V);
+    TORCH_CHECK(B >= 1 && B <= INT32_MAX, "logit_process_rows: at least one slot");
+    LogitRowsArgs ra{};
+    LogitArgs& a = ra.a;
+    a.x = logits.data_ptr();
+    a.V = (int)V;
+    a.rp = a.inv_rp = 1.f;
+    ra.B = (int)B;
+    ra.rows = rows_map(rows, R, B, "logit_process_rows");
+    TORCH_CHECK(rows_tab(rp, at::kFloat, B) && rows_tab(inv_rp, at::kFloat, B) && rows_tab(pp, at::kFloat, B) &&
+                    rows_tab(fp, at::kFloat, B),
+                "logit_process_rows: rp, inv_rp, pp and fp must be contiguous fp32 GPU tensors [B]");
+    TORCH_CHECK(rows_tab(step, at::kInt, B) && rows_tab(done, at::kInt, B),
+                "logit_process_rows: step and done must be contiguous int32 GPU tensors [B]");
+    ra.rp = rp.data_ptr<float>();
+    ra.inv_rp = inv_rp.data_ptr<float>();
+    ra.pp = pp.data_ptr<float>();
+    ra.fp = fp.data_ptr<float>();
+    ra.step = step.data_ptr<int>();
+    ra.done = done.data_ptr<int>();
+    if (hist.has_value()) {
+        TORCH_CHECK(hist->is_cuda() && hist->scalar_type() == at::kInt && hist->is_contiguous() && hist->dim() == 2 &&
+                        hist->size(0) == B && hist->size(1) == V,
+                    "logit_process_rows: hist must be a contiguous int32 GPU tensor [B, V]");
+        a.hist = hist->data_ptr<int>();
+    }
+    if (bias.has_value()) {
+        TORCH_CHECK(bias->is_cuda() && bias->scalar_type() == at::kFloat && bias->is_contiguous() &&
+                        bias->dim() == 1 && bias->size(0) == V,
+                    "logit_process_rows: bias must be a contiguous fp32 GPU tensor [V]");
+        a.bias = bias->data_ptr<float>();
+    }
+    if (out.has_value()) {
+        TORCH_CHECK(out->is_cuda() && out->scalar_type() == logits.scalar_type() && out->is_contiguous() &&
+                        out->dim() == 2 && out->size(0) == R && out->size(1) == V,
+                    "logit_process_rows: out must be a contiguous GPU tensor [R, V] of the logits' dtype");
+        a.out = out->data_ptr();
+    }
+    if (lse.has_value()) {
+        TORCH_CHECK(rows_tab(*lse, at::kFloat, B), "logit_process_rows: lse must be a contiguous fp32 GPU tensor [B]");
+        a.lse = lse->data_ptr<float>();
+    }
+    DevGuard g(logits.device());
+    launch_logit_process_rows(ra, dt_code(logits), (int)R, cur_stream());
+}
+
+void token_commit_rows(const at::Tensor& tokens, const c10::optional<at::Tensor>& rows, const at::Tensor& count,
+                       at::Tensor committed, const c10::optional<at::Tensor>& hist,
+                       const c10::optional<at::Tensor>& raw_logits, const c10::optional<at::Tensor>& lse,
+                       const c10::optional<at::Tensor>& logprob) {
+    TORCH_CHECK(tokens.is_cuda() && tokens.scalar_type() == at::kLong && tokens.dim() == 2 &&
+                    (tokens.size(1) <= 1 || tokens.stride(1) == 1),
+                "token_commit_rows: tokens must be an int64 GPU tensor [B, N], rows dense");
+    const int64_t B = tokens.size(0);
+    TORCH_CHECK(B >= 1 && B <= INT32_MAX, "token_commit_rows: at least one slot");
+    TORCH_CHECK(rows_tab(count, at::kLong, B) && rows_tab(committed, at::kLong, B),
+                "token_commit_rows: count and committed must be contiguous int64 GPU tensors [B]");
+    TORCH_CHECK(hist.has_value() || logprob.has_value(), "token_commit_rows: nothing to do without hist or logprob");
+    int64_t R = rows.has_value() ? rows->numel() : B;
+    CommitRowsArgs ra{};
+    CommitArgs& a = ra.a;
+    a.tokens = (const long long*)tokens.data_ptr<int64_t>();
+    a.tok_ld = tokens.stride(0);
+    a.tok_n = (int)std::min<int64_t>(tokens.size(1), INT32_MAX);
+    ra.count = (const long long*)count.data_ptr<int64_t>();
+    ra.committed = (long long*)committed.data_ptr<int64_t>();
+    ra.B = (int)B;
+    int64_t V = -1;
+    if (hist.has_value()) {
+        TORCH_CHECK(hist->is_cuda() && hist->scalar_type() == at::kInt && hist->is_contiguous() && hist->dim() == 2 &&
+                        hist->size(0) == B, "token_commit_rows: hist must be a contiguous int32 GPU tensor [B, V]");
+        V = hist->size(1);
+        a.hist = hist->data_ptr<int>();
+    }
+    if (logprob.has_value()) {
+        TORCH_CHECK(raw_logits.has_value() && lse.has_value(), "token_commit_rows: logprob needs raw_logits and lse");
+        TORCH_CHECK(raw_logits->is_cuda() && raw_logits->dim() == 2 && raw_logits->is_contiguous() &&
+                        (V < 0 || raw_logits->size(1) == V),
+                    "token_commit_rows: raw_logits must be a contiguous GPU tensor [R, V]");
+        R = raw_logits->size(0);
+        V = raw_logits->size(1);
+        a.raw = raw_logits->data_ptr();
+        a.dtype = dt_code(*raw_logits);
+        TORCH_CHECK(rows_tab(*lse, at::kFloat, B), "token_commit_rows: lse must be a contiguous fp32 GPU tensor [B]");
+        a.lse = lse->data_ptr<float>();
+        TORCH_CHECK(logprob->is_cuda() && logprob->scalar_type() == at::kFloat && logprob->dim() == 2 &&
+                        logprob->size(0) == B && (logprob->size(1) <= 1 || logprob->stride(1) == 1),
+                    "token_commit_rows: logprob must be an fp32 GPU tensor [B, N], rows dense");
+        a.logprob = logprob->data_ptr<float>();
+        a.lp_ld = logprob->stride(0);
+        a.lp_n = (int)std::min<int64_t>(logprob->size(1), INT32_MAX);
+    }
+    TORCH_CHECK(V >= 1 && V <= SAMPLE_MAX_V, "token_commit_rows: 1 <= V <= ", SAMPLE_MAX_V);
+    a.V = (int)V;
+    ra.rows = rows_map(rows, R, B, "token_commit_rows");
+    DevGuard g(tokens.device());
+    launch_token_commit_rows(ra, (int)R, cur_stream());
+}
+
 // ---------------------------------------------------------------- speculative verification (spec_verify.hip)
 // dense rows: [B, R, V] whose rows follow each other V elements apart, from any element offset
 bool spec_dense(const at::Tensor& x) {
@@ -1676,6 +1844,13 @@ TORCH_LIBRARY(bpe_hip, m) {
           "Tensor(a!)? out, Tensor(b!)? lse) -> ()");
     m.def("token_commit(Tensor tokens, Tensor rng, Tensor(a!)? hist, Tensor? raw_logits, Tensor? lse, "
           "Tensor(b!)? logprob) -> ()");
+    m.def("sample_rows(Tensor logits, Tensor? rows, Tensor? u, Tensor temperature, Tensor top_k, Tensor top_p, "
+          "Tensor min_p, Tensor seed, Tensor(a!) count, Tensor limit, Tensor eos, Tensor(b!) step, Tensor(c!) done, "
+          "Tensor(d!) ids, Tensor(e!) out) -> ()");
+    m.def("logit_process_rows(Tensor logits, Tensor? rows, Tensor? hist, Tensor? bias, Tensor rp, Tensor inv_rp, "
+          "Tensor pp, Tensor fp, Tensor step, Tensor done, Tensor(a!)? out, Tensor(b!)? lse) -> ()");
+    m.def("token_commit_rows(Tensor tokens, Tensor? rows, Tensor count, Tensor(a!) committed, Tensor(b!)? hist, "
+          "Tensor? raw_logits, Tensor? lse, Tensor(c!)? logprob) -> ()");
     m.def("spec_verify(Tensor target_logits, Tensor draft_tokens, Tensor? draft_logits, float temperature, "
           "Tensor? ua, Tensor? us, bool point_mass=False) -> (Tensor, Tensor)");
     m.def("spec_verify_step(Tensor target_logits, Tensor? draft_logits, float temperature, Tensor rng, "
@@ -1825,6 +2000,9 @@ TORCH_LIBRARY_IMPL(bpe_hip, CUDA, m) {
     m.impl("sample_step", &sample_step);
     m.impl("logit_process", &logit_process);
     m.impl("token_commit", &token_commit);
+    m.impl("sample_rows", &sample_rows);
+    m.impl("logit_process_rows", &logit_process_rows);
+    m.impl("token_commit_rows", &token_commit_rows);
     m.impl("spec_verify", &spec_verify);
     m.impl("spec_verify_step", &spec_verify_step);
     m.impl("lookup_draft", &lookup_draft);

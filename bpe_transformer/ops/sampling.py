@@ -117,9 +117,51 @@ model's own distribution -- unprocessed logits, T = 1, no filters -- and **not**
 token was sampled from (bias, penalties, temperature, top-k / top-p).
 
 :func:`prompt_hist` builds the table of a fresh batch: bit 0 for every prompt token, right-padding untouched.
+
+**Per-row forms** (``csrc/sample_rows.hip``, ``csrc/logit_process.hip``; continuous batching).  :func:`sample_rows`,
+:func:`logit_process_rows` and :func:`token_commit_rows` are the three in-graph functions above with every parameter
+read per *slot* from a :class:`SamplingTable` of ``B`` slots, so that requests with different parameters, seeds and
+lengths share one captured graph and a change of values never captures again.  ``R`` rows are launched; an optional
+int32 ``rows [R]`` maps launched row ``r`` to slot ``b = rows[r]`` (``None``: ``b = r``, ``R = B``).  What is shaped
+like the logits (``logits``, ``out`` of ``logit_process_rows``, ``raw_logits``: ``[R, V]``) is indexed by ``r``;
+every table and ``ids [B, 1]``, ``out [B, N]``, ``hist [B, V]``, ``lse [B]``, ``logprob [B, N]`` by ``b``.
+
+A slot is *idle* iff ``done[b] != 0`` or ``step[b] == 0``.  An idle slot does nothing at all in any of the three: it
+writes nothing and its counter stands (``spec_verify_step``'s rule, not ``sample_step``'s ``-1``).
+
+:func:`sample_rows`, for an active slot, with ``c = count[b]``:
+
+1. ``u = u[r]`` if uniforms are given, else Philox4x32-10 keyed by ``seed[b]`` at counter ``(c, 0, 0)``.  The row
+   word is 0, not the slot: a request's random stream depends on neither its slot nor its neighbours, and equals
+   a one-row ``sample_step`` at ``rng = (seed[b], c)``.
+2. The token is the sampling function at the top of this docstring with ``temperature[b]`` (fp32), ``top_k[b]``
+   (int32), ``top_p[b]`` (fp64: the kernel computes ``ceil(top_p * Z)`` in double, as the scalar one does on its
+   double argument) and one more filter between steps 5 and 6: ``min_p[b] > 0`` (fp32; the min-p sampling of Nguyen
+   et al., "Turning Up the Heat: Min-p Sampling for Creative and Coherent LLM Outputs", 2024) keeps, of what top-k
+   and top-p kept, a token iff its mass is at least ``min_p`` times the largest mass.  In the kernel's fixed-point
+   masses ``zq_i = floor(z_i * 2^40)``: a token stays iff ``zq_i >= ceil(min_p * zq_max)`` (the product in fp64),
+   where ``zq_max = 2^40`` is the argmax's; the threshold is capped at ``zq_max``, so the argmax token always stays.
+   The reference applies the same integers to its fp64 ``z``.
+3. ``ids[b, 0] = out[b, c] = token`` (``out`` only where ``c`` is one of its columns) and ``count[b] = c + 1``.
+4. If ``token == eos[b]`` (``eos[b] < 0``: none) or ``count[b] >= limit[b]``: ``done[b] = 1`` and ``step[b] = 0``.
+
+The kernel advances the counter itself, so no ``rng[1] += 1`` launch follows it.
+
+:func:`logit_process_rows` is :func:`logit_process` with ``rp[b]``, ``1 / rp[b]``, ``pp[b]``, ``fp[b]`` (fp32
+``[B]``, the reciprocal made on the host when the slot is set).  A slot whose three penalties are neutral (``rp ==
+1``, ``pp == fp == 0``) is processed without its history: every element the shared ``bias [V]`` does not touch keeps
+its bits.  The bias is one ``[V]`` tensor for all slots; a per-request bias is not supported.
+
+:func:`token_commit_rows` is :func:`token_commit` at column ``count[b] - 1``, for every slot whose counter has moved
+since its last commit: the table keeps ``committed[b]``, a slot commits iff ``count[b] > committed[b]`` and then
+``committed[b] = count[b]``.  So the slot that has just drawn its last token (and is ``done`` now) still commits
+it, and a slot that drew nothing commits nothing.
 """
 
 from __future__ import annotations
+
+import dataclasses
+import math
 
 import torch
 from torch import Tensor
@@ -524,3 +566,238 @@ def prompt_hist(ids: Tensor, lengths, V: int) -> Tensor:
     rows = torch.arange(B, device=ids.device)[:, None].expand(B, T)
     hist[rows[valid], ids[valid]] = 1
     return hist
+
+
+# ---------------------------------------------------------------- per-row forms (continuous batching)
+@dataclasses.dataclass
+class SamplingParams:
+    """One request's sampling parameters: what :meth:`SamplingTable.set` writes into a slot."""
+
+    temperature: float = 1.0
+    top_k: int | None = None
+    top_p: float | None = None
+    min_p: float = 0.0
+    seed: int = 0
+    max_new_tokens: int = 16
+    eos_token_id: int | None = None
+    repetition_penalty: float = 1.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    logprobs: bool = False
+    logit_bias: object = None  # not supported per request (the bias is one [V] tensor for all slots): ValueError
+
+    @property
+    def penal(self) -> bool:
+        return self.repetition_penalty != 1.0 or self.presence_penalty != 0.0 or self.frequency_penalty != 0.0
+
+
+class SamplingTable:
+    """The per-slot device tables of the ``*_rows`` functions (module docstring, "Per-row forms"), ``B`` slots:
+    ``temperature``, ``min_p``, ``rp``, ``inv_rp``, ``pp``, ``fp`` fp32; ``top_p`` fp64; ``top_k``, ``limit``, ``eos``,
+    ``done``, ``step`` int32; ``seed``, ``count``, ``committed`` int64 -- all ``[B]``, contiguous and static, so a
+    captured graph reads them.  Tables of one type are the rows of one tensor: :meth:`set` is one small copy per
+    type, in stream order.  ``step`` may be a tensor the caller already owns (a ragged session's decode step).
+    Every slot starts idle (``done = 1``, ``step = 0``)."""
+
+    def __init__(self, B: int, device=None, step: Tensor | None = None):
+        self.B, self.device = int(B), device
+        self._f32 = torch.zeros(6, B, dtype=torch.float32, device=device)
+        self._f64 = torch.ones(1, B, dtype=torch.float64, device=device)
+        self._i32 = torch.zeros(4, B, dtype=torch.int32, device=device)
+        self._i64 = torch.zeros(3, B, dtype=torch.long, device=device)
+        self.temperature, self.min_p, self.rp, self.inv_rp, self.pp, self.fp = self._f32.unbind(0)
+        self.top_p = self._f64[0]
+        self.top_k, self.limit, self.eos, self.done = self._i32.unbind(0)
+        self.seed, self.count, self.committed = self._i64.unbind(0)
+        self.step = torch.zeros(B, dtype=torch.int32, device=device) if step is None else step
+        assert self.step.dtype == torch.int32 and self.step.numel() == B and self.step.is_contiguous()
+        self.rp.fill_(1.0)
+        self.inv_rp.fill_(1.0)
+        self.eos.fill_(-1)
+        self.done.fill_(1)
+        self.step.zero_()
+
+    def set(self, b: int, p: SamplingParams) -> None:
+        """Slot ``b`` takes the request ``p`` and becomes active at token 0."""
+        if not float(p.repetition_penalty) > 0:
+            raise ValueError(f"repetition_penalty must be > 0, got {p.repetition_penalty}")
+        if getattr(p, "logit_bias", None) is not None:
+            raise ValueError("a per-request logit_bias is not supported: the bias is shared by all slots")
+        top_k = int(p.top_k or 0)
+        if top_k < 0:
+            raise ValueError(f"top_k: 0 / None (off) or a positive count, got {p.top_k}")
+        s = slice(b, b + 1)
+        self._f32[:, s].copy_(torch.tensor(
+            [[float(p.temperature)], [float(p.min_p or 0.0)], [_f32(p.repetition_penalty)],
+             [_inv_f32(p.repetition_penalty)], [float(p.presence_penalty)], [float(p.frequency_penalty)]],
+            dtype=torch.float32))
+        self._f64[:, s].copy_(torch.tensor([[1.0 if p.top_p is None else float(p.top_p)]], dtype=torch.float64))
+        eos = -1 if p.eos_token_id is None else int(p.eos_token_id)
+        self._i32[:, s].copy_(torch.tensor([[min(top_k, 2**31 - 1)], [int(p.max_new_tokens)], [eos], [0]],
+                                           dtype=torch.int32))
+        seed = int(p.seed) & (2**64 - 1)
+        self._i64[:, s].copy_(torch.tensor([[seed - 2**64 if seed >= 2**63 else seed], [0], [0]], dtype=torch.long))
+        self.step[s].fill_(1)
+
+    def clear(self, b: int) -> None:
+        """Slot ``b`` becomes idle."""
+        self.done[b : b + 1].fill_(1)
+        self.step[b : b + 1].zero_()
+
+
+def _rows_arg(rows, R: int, B: int, device) -> Tensor | None:
+    if rows is None:
+        assert R == B, "without a rows map the logits have one row per slot"
+        return None
+    rows = torch.as_tensor(rows, dtype=torch.int32).reshape(-1).to(device)
+    assert rows.numel() == R, "rows: one slot per launched row"
+    return rows.contiguous()
+
+
+def sample_rows(logits: Tensor, table: SamplingTable, ids: Tensor, out: Tensor, rows=None,
+                u: Tensor | None = None) -> None:
+    """Sample one token per launched row of ``logits [R, V]`` in place, every parameter from ``table`` (module
+    docstring, "Per-row forms"): ``ids`` int64 ``[B, 1]`` and ``out`` int64 ``[B, N]`` take the token of slot ``b``,
+    ``table.count`` advances, ``table.done`` / ``table.step`` mark the end (EOS, or ``limit`` tokens).  ``rows``:
+    int32 ``[R]`` slots of the launched rows (``None``: all ``B``, in order); ``u``: fp32 ``[R]`` uniforms in place
+    of Philox."""
+    assert logits.dim() == 2 and logits.shape[1] >= 1, "logits: [R, V]"
+    assert logits.dtype in (torch.bfloat16, torch.float32), "logits: bf16 or fp32"
+    t = table
+    rows = _rows_arg(rows, logits.shape[0], t.B, logits.device)
+    if logits.is_cuda:
+        ops().sample_rows(logits.contiguous(), rows, None if u is None else u.to(logits.device, torch.float32).contiguous(),
+                          t.temperature, t.top_k, t.top_p, t.min_p, t.seed, t.count, t.limit, t.eos, t.step, t.done,
+                          ids, out)
+        return
+    sample_rows_reference(logits, table, ids, out, rows, u)
+
+
+def sample_min_p_reference(logits: Tensor, temperature: float, top_k: int, top_p: float, min_p: float,
+                           u: Tensor) -> Tensor:
+    """:func:`sample_logits_reference` with the min-p filter of the module docstring (``min_p <= 0``: exactly that
+    function)."""
+    if temperature <= 0 or not min_p > 0:
+        return sample_logits_reference(logits, temperature, top_k, top_p, u)
+    x = logits.double()
+    B, V = x.shape
+    z = torch.exp((x - x.amax(-1, keepdim=True)) / float(temperature))
+    order = torch.sort(x, dim=-1, descending=True, stable=True).indices
+    zs = z.gather(-1, order)
+    keep = torch.ones_like(zs, dtype=torch.bool)
+    if top_k > 0:
+        keep &= torch.arange(V, device=x.device)[None, :] < min(int(top_k), V)
+    if top_p < 1.0:
+        zk = zs * keep
+        keep &= zk.cumsum(-1) - zk < float(top_p) * zk.sum(-1, keepdim=True)
+        keep[:, 0] = True
+    thr = min(math.ceil(_f32(min_p) * 2.0**40), 2**40)  # ceil(min_p * zq_max), zq_max = 2^40
+    keep &= torch.floor(zs * 2.0**40) >= thr
+    keep[:, 0] = True
+    kept = torch.zeros_like(keep).scatter_(-1, order, keep)
+    zk = z * kept
+    cum = zk.cumsum(-1)
+    M = cum[:, -1:]
+    hit = (cum > u.to(x.device).double().reshape(B, 1) * M) & (zk > 0)
+    idx = torch.arange(V, device=x.device)
+    last = torch.where(zk > 0, idx, torch.zeros_like(idx)).amax(-1)
+    return torch.where(hit.any(-1), hit.int().argmax(-1), last)
+
+
+def sample_rows_reference(logits, table, ids, out, rows=None, u=None) -> None:
+    t = table
+    R = logits.shape[0]
+    for r in range(R):
+        b = r if rows is None else int(rows[r])
+        if not 0 <= b < t.B or int(t.done[b]) != 0 or int(t.step[b]) == 0:
+            continue
+        c = int(t.count[b])
+        ur = u[r : r + 1].float() if u is not None else philox_uniform(int(t.seed[b]), c, 1, logits.device)
+        tok = int(sample_min_p_reference(logits[r : r + 1], float(t.temperature[b]), int(t.top_k[b]),
+                                         float(t.top_p[b]), float(t.min_p[b]), ur))
+        ids.view(-1)[b] = tok
+        if 0 <= c < out.shape[1]:
+            out[b, c] = tok
+        t.count[b] = c + 1
+        eos = int(t.eos[b])
+        if (eos >= 0 and tok == eos) or c + 1 >= int(t.limit[b]):
+            t.done[b] = 1
+            t.step[b] = 0
+
+
+def logit_process_rows(logits: Tensor, table: SamplingTable, hist: Tensor | None = None, bias: Tensor | None = None,
+                       out: Tensor | None = None, lse: Tensor | None = None, rows=None) -> None:
+    """:func:`logit_process` with the penalties of ``table`` per slot (module docstring, "Per-row forms"): ``logits``
+    and ``out`` are ``[R, V]``, ``hist`` int32 ``[B, V]``, ``lse`` fp32 ``[B]``, ``bias`` fp32 ``[V]`` shared.  An idle
+    slot writes nothing; a slot with neutral penalties keeps every bit the bias does not touch."""
+    t = table
+    R, V = logits.shape
+    assert logits.is_contiguous() and logits.dtype in (torch.bfloat16, torch.float32), "logits: contiguous bf16 / fp32"
+    assert hist is None or (hist.dtype == torch.int32 and tuple(hist.shape) == (t.B, V)), "hist: int32 [B, V]"
+    assert bias is None or (bias.dtype == torch.float32 and tuple(bias.shape) == (V,)), "bias: fp32 [V]"
+    assert out is None or (out.dtype == logits.dtype and tuple(out.shape) == (R, V)), "out: [R, V] of the logits' dtype"
+    assert lse is None or (lse.dtype == torch.float32 and lse.numel() == t.B), "lse: fp32 [B]"
+    rows = _rows_arg(rows, R, t.B, logits.device)
+    if logits.is_cuda:
+        ops().logit_process_rows(logits, rows, hist, bias, t.rp, t.inv_rp, t.pp, t.fp, t.step, t.done, out, lse)
+        return
+    logit_process_rows_reference(logits, table, hist, bias, out, lse, rows)
+
+
+def logit_process_rows_reference(logits, table, hist=None, bias=None, out=None, lse=None, rows=None) -> None:
+    """One :func:`logit_process_reference` call per active slot, with that slot's values."""
+    t = table
+    for r in range(logits.shape[0]):
+        b = r if rows is None else int(rows[r])
+        if not 0 <= b < t.B or int(t.done[b]) != 0 or int(t.step[b]) == 0:
+            continue
+        rp, pp, fp = float(t.rp[b]), float(t.pp[b]), float(t.fp[b])
+        h = hist[b : b + 1] if hist is not None and not (rp == 1.0 and pp == 0.0 and fp == 0.0) else None
+        logit_process_reference(logits[r : r + 1], h, bias, rp, pp, fp, None if out is None else out[r : r + 1],
+                                None if lse is None else lse.view(-1)[b : b + 1])
+
+
+def token_commit_rows(tokens: Tensor, table: SamplingTable, hist: Tensor | None = None,
+                      raw_logits: Tensor | None = None, lse: Tensor | None = None, logprob: Tensor | None = None,
+                      rows=None) -> None:
+    """:func:`token_commit` on the per-slot counter (module docstring, "Per-row forms"): every launched slot with
+    ``count[b] > committed[b]`` adds ``tokens[b, count[b] - 1]`` to ``hist [B, V]``, writes its log-probability
+    ``float(raw_logits[r, tok]) - lse[b]`` into ``logprob [B, M]`` at that column, and sets ``committed[b] =
+    count[b]``.  ``raw_logits`` is ``[R, V]``; ``rows`` as in :func:`sample_rows`."""
+    assert tokens.dim() == 2 and tokens.dtype == torch.long and tokens.shape[0] == table.B, "tokens: int64 [B, N]"
+    assert hist is not None or logprob is not None, "token_commit_rows: hist, logprob or both"
+    assert logprob is None or (raw_logits is not None and lse is not None), "logprob needs raw_logits and lse"
+    t = table
+    R = t.B if rows is None else len(rows)
+    if raw_logits is not None:
+        R = raw_logits.shape[0]
+    rows = _rows_arg(rows, R, t.B, tokens.device)
+    if tokens.is_cuda:
+        if logprob is None:
+            raw_logits = lse = None
+        ops().token_commit_rows(tokens, rows, t.count, t.committed, hist, raw_logits, lse, logprob)
+        return
+    token_commit_rows_reference(tokens, table, hist, raw_logits, lse, logprob, rows)
+
+
+def token_commit_rows_reference(tokens, table, hist=None, raw_logits=None, lse=None, logprob=None, rows=None) -> None:
+    t = table
+    R = t.B if rows is None else len(rows)
+    for r in range(R):
+        b = r if rows is None else int(rows[r])
+        if not 0 <= b < t.B:
+            continue
+        n = int(t.count[b])
+        if n <= int(t.committed[b]):
+            continue
+        t.committed[b] = n
+        col = n - 1
+        if not 0 <= col < tokens.shape[1]:
+            continue
+        tok = int(tokens[b, col])
+        if tok < 0 or (hist is not None and tok >= hist.shape[1]):
+            continue
+        if hist is not None:
+            hist[b, tok] += 2
+        if logprob is not None and col < logprob.shape[1]:
+            logprob[b, col] = raw_logits[r, tok].float() - lse.view(-1)[b]

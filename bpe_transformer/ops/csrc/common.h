@@ -158,14 +158,23 @@ __host__ __forceinline__ int stream_grid(size_t work_items, int block, int cap =
 constexpr float FP8_E4M3_MAX = 448.f;     // OCP e4m3fn: activations / weights
 constexpr float FP8_E5M2_MAX = 57344.f;   // OCP e5m2: gradients (wider range, 2 mantissa bits)
 
-// FMT 0 = e4m3fn (v_cvt_pk_fp8_f32), 1 = e5m2 (v_cvt_pk_bf8_f32); saturating: clamp before the convert
+// FMT 0 = e4m3fn (v_cvt_pk_fp8_f32), 1 = e5m2 (v_cvt_pk_bf8_f32).  Saturating: finite values beyond the range and
+// +-inf are clamped to +-max before the convert.  NaN stays NaN: fmaxf / fminf return their non-NaN operand, which
+// would turn a NaN into the finite code of -max, so the clamp is skipped for it and the convert instruction writes
+// the format's NaN code (a NaN activation must reach the loss and the optimizer's non-finite skip in fp8 mode as
+// it does in bf16).  -0 keeps its sign, fp32 subnormals are converted, not flushed.
+template <int FMT>
+__device__ __forceinline__ float sat_fp8(float a) {
+    constexpr float M = FMT == 0 ? FP8_E4M3_MAX : FP8_E5M2_MAX;
+    return a != a ? a : fminf(fmaxf(a, -M), M);
+}
+
 template <int FMT>
 __device__ __forceinline__ unsigned pack4_fp8(float a, float b, float c, float d) {
-    constexpr float M = FMT == 0 ? FP8_E4M3_MAX : FP8_E5M2_MAX;
-    a = fminf(fmaxf(a, -M), M);
-    b = fminf(fmaxf(b, -M), M);
-    c = fminf(fmaxf(c, -M), M);
-    d = fminf(fmaxf(d, -M), M);
+    a = sat_fp8<FMT>(a);
+    b = sat_fp8<FMT>(b);
+    c = sat_fp8<FMT>(c);
+    d = sat_fp8<FMT>(d);
     int w;
     if constexpr (FMT == 0) {
         w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false);  // bytes 0,1

@@ -30,6 +30,16 @@
 //     amax into its history ring, recompute scale and 1/scale.
 // gfx950 uses the OCP e4m3fn encoding (not MI300's fnuz); the conversion is
 // v_cvt_pk_fp8_f32 after an explicit clamp to +-448 (saturating cast).
+//
+// Contract of every cast here (common.h pack4_fp8; tests/fp8_refs.py is the reference):
+//   * code = RNE_fp8(fl32(x * s)): one fp32 product, one round-to-nearest-even onto the finite codes, ties to the
+//     even mantissa, fp8 and fp32 subnormals kept, -0 keeps its sign;
+//   * finite values beyond the range and +-inf saturate to +-max; NaN gives the format's NaN code;
+//   * amax = max |x| over the non-NaN values (fmaxf drops NaN), +inf counts -- update_scales then sees a non-finite
+//     window maximum and falls back to scale 1;
+//   * update_scales: scale = 2^floor(log2(fmax / (m * margin))) clamped to [2^-126, 2^126], so scale and 1 / scale
+//     are normal fp32 numbers for every positive finite window maximum m, subnormal ones included (a bf16 tensor
+//     can hold 1e-40); scale = 1 for m = 0 or a non-finite m.
 #include "common.h"
 #include "kernels.h"
 
@@ -513,11 +523,16 @@ __global__ void __launch_bounds__(256) update_scales_kernel(unsigned* __restrict
     hist[(size_t)i * H + pos] = a;
     float m = 0.f;
     for (int k = 0; k < H; ++k) m = fmaxf(m, hist[(size_t)i * H + k]);
-    float s = (m > 0.f && isfinite(m)) ? fmax / (m * margin) : 1.f;
-    // keep scales powers of two: exact dequantisation, no rounding drift between steps
-    s = exp2f(floorf(log2f(s)));
+    const float q = (m > 0.f && isfinite(m)) ? fmax / (m * margin) : 1.f;
+    // keep scales powers of two (exact dequantisation, no rounding drift between steps): 2^floor(log2 q) is q's own
+    // exponent field -- no log2f / exp2f rounding at exact powers of two -- clamped to [1, 253], i.e. 2^-126 ..
+    // 2^126, so that the scale AND its inverse are normal fp32 numbers: q overflows to inf for a subnormal m (field
+    // 255) and is 0 or subnormal when m * margin overflows (field 0)
+    const unsigned qe = (__float_as_uint(q) >> 23) & 0xFFu;
+    const unsigned e = qe < 1u ? 1u : (qe > 253u ? 253u : qe);
+    const float s = __uint_as_float(e << 23);
     scale[i] = s;
-    inv_scale[i] = 1.f / s;
+    inv_scale[i] = __uint_as_float((254u - e) << 23);  // 2^-(e - 127), exact
 }
 
 }  // namespace bpe

@@ -88,7 +88,8 @@ def generate_s(sess, prompt, tokens, T, k, p, sampler, controls=None):
 def generate_arm(model, cfg, B, prompt_len, tokens, rounds, grid=GRID, controls=None):
     prompt = torch.randint(0, cfg.vocab_size, (B, prompt_len), device="cuda")
     sess = DecodeSession(model, B, max_len=prompt_len + tokens)
-    # the controls' graph is another graph of the same session: it has one of its own, so that neither side re-captures
+    # the controls side has a session of its own (one session would hold both graphs, one per set of switches; two keep
+    # the sides' caches and buffers apart, as in the figures recorded so far)
     csess = DecodeSession(model, B, max_len=prompt_len + tokens) if controls else None
     for name, T, k, p in grid:
         for s in ("host", "device"):  # graph capture and first-use costs outside the timed runs

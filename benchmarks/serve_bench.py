@@ -1,5 +1,4 @@
-"""Continuous batching benchmark: the request engine (``models/serving.py``) against static batching, and the per-row
-sampling graph against the scalar one.
+"""Continuous batching benchmark: the request engine (``models/serving.py``) against static batching.
 
 A fixed seeded trace of ``--requests`` requests (prompts of 16-512 tokens, ``max_new_tokens`` of 16-256, all present
 at time 0, one sampling parameter set, no EOS) is served two ways on the same model in one process, alternating:
@@ -11,9 +10,7 @@ at time 0, one sampling parameter set, no EOS) is served two ways on the same mo
 Tokens per second count each request's own ``max_new_tokens`` on both sides (what a static group generates past a
 request's limit is waste).  One JSON line per batch with the medians and every round.
 
-(c) ``step``: the captured step of the per-row graph (decode -> ``sample_rows``) against the scalar graph (decode ->
-    ``sample_step`` -> ``rng[1] += 1``; ``sample_bench.py``'s step) at the same batch and cache fill: microseconds per
-    replay over ``--iters`` replays, device events, alternating rounds.
+Both sides replay the same captured step (decode -> ``sample_rows``); ``sample_bench.py`` times it per token.
 
     python benchmarks/serve_bench.py --model gpt2-small --batch 8 64
 """
@@ -85,46 +82,6 @@ def serve_arm(model, cfg, B, reqs, rounds, sync_every):
     torch.cuda.empty_cache()
 
 
-def event_us(fn, iters):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(iters):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / iters * 1e3
-
-
-def step_arm(model, cfg, B, prompt_len, iters, rounds):
-    room = prompt_len + 16 + (rounds + 1) * iters
-    prompt = torch.randint(0, cfg.vocab_size, (B, prompt_len))
-    sess = DecodeSession(model, B, max_len=room, ragged=True)
-    sess.generate(list(prompt), 8, temperature=T, top_k=TOP_K, sampler="device", seed=1)  # prefill + capture
-    st = sess._samp
-    st["done"].zero_()
-    sess._step.fill_(1)
-    eng = ServingEngine(model, batch=B, max_len=room, sync_every=8)
-    for i in range(B):
-        eng.submit(prompt[i], SamplingParams(temperature=T, top_k=TOP_K, seed=i, max_new_tokens=room - prompt_len))
-    eng.step()  # admits all B, 8 tokens each: the same cache fill
-    scalar = lambda: sess._device_step(st)  # noqa: E731
-    rows = lambda: eng.session._device_step_rows(eng._st)  # noqa: E731
-    a, b = [], []
-    for fn in (scalar, rows):
-        event_us(fn, 8)
-    for _ in range(rounds):
-        a.append(event_us(scalar, iters))
-        b.append(event_us(rows, iters))
-    assert int(eng._st["table"].done.sum()) == 0, "a request ended inside the timed replays"
-    ma, mb = statistics.median(a), statistics.median(b)
-    print(json.dumps({"arm": "step", "batch": B, "prompt": prompt_len, "iters": iters,
-                      "scalar_step_us": round(ma, 2), "rows_step_us": round(mb, 2), "rows_minus_scalar_us": round(mb - ma, 2),
-                      "scalar_us_rounds": [round(x, 2) for x in a], "rows_us_rounds": [round(x, 2) for x in b]}),
-          flush=True)
-    del sess, eng
-    torch.cuda.empty_cache()
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="gpt2-small")
@@ -132,9 +89,6 @@ def main():
     ap.add_argument("--requests", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--sync-every", type=int, default=8)
-    ap.add_argument("--iters", type=int, default=100, help="replays per timed window of the step arm")
-    ap.add_argument("--prompt", type=int, default=128, help="prompt length of the step arm")
-    ap.add_argument("--arms", nargs="+", default=["serve", "step"], choices=["serve", "step"])
     a = ap.parse_args()
     assert torch.cuda.is_available(), "serve_bench needs a GPU"
     cfg = get_preset(a.model)
@@ -143,10 +97,7 @@ def main():
     with torch.no_grad():
         model = TransformerLM.from_config(cfg, device="cuda", dtype=torch.bfloat16).eval()
         for B in a.batch:
-            if "serve" in a.arms:
-                serve_arm(model, cfg, B, reqs, a.rounds, a.sync_every)
-            if "step" in a.arms:
-                step_arm(model, cfg, B, a.prompt, a.iters, a.rounds)
+            serve_arm(model, cfg, B, reqs, a.rounds, a.sync_every)
 
 
 if __name__ == "__main__":

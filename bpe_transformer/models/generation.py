@@ -124,6 +124,13 @@ sequence (``cache.pos [B]``, stride 1, host mirror ``cache.lengths``).  So
 * ``generate`` takes a list of 1-D prompts and returns a list of 1-D tensors,
   each ending with its first EOS; a finished sequence becomes inactive.
 
+**One device sampler.**  ``generate(sampler="device")`` and the request engine (``models/serving.py``) share one
+state (``_sampler_state``): a ``SamplingTable`` with every sampling parameter per slot, and one captured step --
+decode -> [``logit_process_rows``] -> ``sample_rows`` -> [``token_commit_rows``] -- per set of structural switches
+(penalty table, log-probs, bias).  ``generate`` fills every slot with the call's values, one seed and the row as the
+Philox row word, and bounds the count on the host; the engine fills a slot per request.  Values never capture.
+Every graph of this module is captured by ``_capture_graph``.
+
 Cache rows at and past ``pos[b]`` may hold pad-token (or inactive-step) values.
 They are never visible -- every read of sequence ``b`` stops at ``pos[b]`` plus
 its own new tokens -- and are overwritten as the sequence grows.
@@ -190,6 +197,25 @@ def _append_plan(T: int, G: int, filled: bool, prefill_chunk: int | None = None,
             d = max(1, 8 // G)
             plan += [(t0 + u, min(d, w - u), "decode") for u in range(0, w, d)]
     return plan
+
+
+def _capture_graph(device, run, restore):
+    """``run`` captured into a HIP graph -> ``(graph, what run returned inside the capture)``: a warm-up run on a side
+    stream (first-use allocations and lazy initialisation must not happen inside a capture), then the capture on the
+    current stream -- one stream, so the graph has no parallel branches.  ``restore`` puts back what the warm-up run
+    wrote and the caller needs as it was; it runs after the warm-up and again after the capture (which executes
+    nothing, but the invariant stays explicit)."""
+    s = torch.cuda.Stream(device=device)
+    s.wait_stream(torch.cuda.current_stream(device))
+    with torch.cuda.stream(s):
+        run()
+    torch.cuda.current_stream(device).wait_stream(s)
+    restore()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        out = run()
+    restore()
+    return g, out
 
 
 def _gemv_ok(m: int, k: int) -> bool:
@@ -567,14 +593,12 @@ def _sample(logits: Tensor, temperature: float, top_p: float | None, generator, 
 class _Controls:
     """The sampling controls of one ``generate`` call that are not at their defaults (``ops/sampling.py``, "Sampling
     controls"): ``penal`` -- a penalty is on, so the token history is kept; ``proc`` -- the sampler reads processed
-    logits; ``logprobs`` -- the log-sum-exp and the emitted tokens' log-probs are wanted.  ``key`` is what a captured
-    graph bakes in: the penalty values and the two booleans (the bias values live in a static buffer)."""
+    logits; ``logprobs`` -- the log-sum-exp and the emitted tokens' log-probs are wanted."""
 
     def __init__(self, rp: float, pp: float, fp: float, bias: Tensor | None, logprobs: bool):
         self.rp, self.pp, self.fp, self.bias, self.logprobs = float(rp), float(pp), float(fp), bias, bool(logprobs)
         self.penal = self.rp != 1.0 or self.pp != 0.0 or self.fp != 0.0
         self.proc = self.penal or bias is not None
-        self.key = (self.rp, self.pp, self.fp, bias is not None, self.logprobs)
 
 
 def _controls(V: int, device, repetition_penalty, presence_penalty, frequency_penalty, logit_bias,
@@ -708,8 +732,7 @@ class DecodeSession:
         self._step = torch.ones(batch, device=self.device, dtype=torch.int32) if ragged and self.fast else None
         self._step_host = [1] * batch  # what _step holds
         self._graph = None
-        self._samp = None  # the device sampler's buffers and graph (_sampler_state)
-        self._samp_rows = None  # the per-row device sampler's (_sampler_state_rows)
+        self._samp = None  # the device sampler's table, buffers and graphs (_sampler_state)
         if self.fast:
             self._prepare_weights()
         elif self.w8:  # the definition of the feature: the oracle math on the dequantised model
@@ -949,10 +972,13 @@ class DecodeSession:
         ``top_k`` keeps the ``top_k`` most likely tokens (applied before ``top_p``; ``None``: off).
 
         ``sampler="host"`` (default) samples in PyTorch from ``generator`` and looks at every token on the host.
-        ``sampler="device"`` samples with ``ops.sample_step`` (``ops/sampling.py`` states the function), on the fast
-        path inside a second captured graph -- decode step -> ``sample_step`` -> ``rng[1] += 1`` -- that writes the
-        next token straight into its own input; EOS and the ragged active mask are handled on the device, and the
-        host only reads the ``done`` flags every ``sync_every`` tokens (never, without ``eos_token_id``).  Its random
+        ``sampler="device"`` samples with ``ops.sample_rows`` on the session's sampling table (``ops/sampling.py``
+        states the function: ``ops.sample_step``'s, row by row), on the fast path inside a second captured graph --
+        decode step -> ``sample_rows`` -- that writes the next token straight into its own input and advances the
+        token counters itself.  Temperature, ``top_k``, ``top_p``, EOS, the seed and the penalty values are read from
+        the table, so one graph serves every call and a change of values never captures.  EOS and the ragged active
+        mask are handled on the device, and the host only reads the ``done`` flags every ``sync_every`` tokens (never,
+        without ``eos_token_id``).  Its random
         stream is Philox keyed by ``seed`` at counter (token index, row); ``seed=None`` draws one from ``generator``
         (else from torch's default generator), which is all ``generator`` is used for in this mode.  The results have
         the shapes of the host sampler's; ``prompt + max_new_tokens <= max_len`` is checked once, up front.
@@ -961,8 +987,11 @@ class DecodeSession:
         ``repetition_penalty`` (> 0; over prompt and output), ``presence_penalty`` / ``frequency_penalty`` (over the
         output) and ``logit_bias`` (a ``{token: value}`` dict or a ``[V]`` tensor; ``-inf`` bans a token) change the
         logits the sampler reads -- ``ops.logit_process`` before every sample, ``ops.token_commit`` after it, with the
-        per-sequence token history on the device; with ``sampler="device"`` both run inside the captured step: decode
-        -> ``logit_process`` -> ``sample_step`` -> ``token_commit`` -> ``rng[1] += 1``.  ``return_logprobs`` makes
+        per-sequence token history on the device; with ``sampler="device"`` their per-row forms run inside the
+        captured step: decode -> ``logit_process_rows`` -> ``sample_rows`` -> ``token_commit_rows``.  Which of them
+        run is decided per call by three switches -- a penalty is on, log-probs are wanted, there is a bias -- and a
+        graph is captured once per set of switches it meets; a call with none replays the plain graph, whatever the
+        calls before it used.  ``return_logprobs`` makes
         the result ``(tokens, logprobs)``: fp32 ``[B, n]`` (a list of 1-D tensors for list prompts), aligned with the
         emitted tokens and trimmed as they are, each the token's log-probability under the model's own
         distribution (unprocessed logits, T = 1, no filters), not under the warped one it was sampled from."""
@@ -1038,187 +1067,90 @@ class DecodeSession:
         return out
 
     # ------------------------------------------------------------------ device sampler
-    def _sampler_state(self, temperature: float, top_k: int, top_p: float, eos: int, ctl: "_Controls | None" = None):
-        """The device sampler's static buffers -- ``ids [B, 1]`` (the next token: the step's input), ``out
-        [B, max_len]`` (token ``i`` of the continuation in column ``i``), ``done [B]``, ``rng = (seed, count)`` --
-        and, with ``use_graph``, the graph of one decode step + ``sample_step`` + ``rng[1] += 1`` for these sampling
-        parameters (they are baked into the graph: other parameters capture it again).  With sampling controls
-        (``ctl``) the state gains static ``hist [B, V]``, ``bias [V]``, ``lse [B]``, ``proc [B, V]`` and ``logprob
-        [B, max_len]``, and the captured step is decode -> ``logit_process`` -> ``sample_step`` on ``proc`` ->
-        ``token_commit`` -> ``rng[1] += 1`` (:meth:`_sample_controlled`).  Captured like ``_capture``:
-        one stream, so no parallel branches; the warm-up run's writes are all re-initialised by the caller."""
-        from ..ops import sampling
-
-        st = self._samp
-        if st is None:
-            B, dev = self.batch, self.device
-            st = self._samp = {
-                "ids": torch.zeros(B, 1, dtype=torch.long, device=dev),
-                "out": torch.full((B, self.max_len), -1, dtype=torch.long, device=dev),
-                "done": torch.zeros(B, dtype=torch.int32, device=dev),
-                "rng": torch.zeros(2, dtype=torch.long, device=dev),
-                # a ragged session off the fast path has no static step: the sampler's own
-                "step": self._step if self._step is not None else (
-                    torch.ones(B, dtype=torch.int32, device=dev) if self.ragged else None),
-                "graph": None, "key": None,
-            }
-        key = (float(temperature), top_k, top_p, eos)
-        st["params"] = key
-        st["ctl"] = ctl
-        if ctl is not None:
-            # the controls' static buffers (module ops/sampling.py, "Sampling controls"); their contents are the
-            # caller's to initialise.  The penalty values and the two booleans join the graph key; with every
-            # control at its default the key is the old one and selects the graph that exists without them.
-            key = key + ctl.key
-            if "hist" not in st:
-                B, dev, V = self.batch, self.device, self.model.lm_head.weight.shape[0]
-                st["hist"] = torch.zeros(B, V, dtype=torch.int32, device=dev)
-                st["bias"] = torch.zeros(V, dtype=torch.float32, device=dev)
-                st["lse"] = torch.zeros(B, dtype=torch.float32, device=dev)
-                st["logprob"] = torch.full((B, self.max_len), math.nan, dtype=torch.float32, device=dev)
-                # the processed logits, [B, V] of the logits' dtype (off the fast path: made by the first step)
-                st["proc"] = torch.empty(B, V, dtype=self.model.lm_head.weight.dtype, device=dev) if self.fast else None
-            if ctl.bias is not None:
-                st["bias"].copy_(ctl.bias)
-        if self.use_graph and st["key"] != key:
-            def run():
-                logits = self._forward_fast(st["ids"], "decode", step=self._step)
-                if ctl is None:
-                    sampling.sample_step(logits, *key[:3], st["rng"], st["ids"], st["out"], st["step"], st["done"], eos)
-                else:
-                    self._sample_controlled(st, logits)
-                st["rng"][1:].add_(1)
-
-            pos0 = self.cache.pos.clone()
-            s = torch.cuda.Stream(device=self.device)
-            s.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(s):
-                run()
-            torch.cuda.current_stream(self.device).wait_stream(s)
-            self.cache.pos.copy_(pos0)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                run()
-            self.cache.pos.copy_(pos0)
-            st["graph"], st["key"] = g, key
-        return st
-
-    def _sample_controlled(self, st, logits: Tensor) -> None:
-        """``sample_step`` with the call's sampling controls around it, all on the sampler's static buffers:
-        ``logit_process`` (``logits`` -> ``proc``, the raw rows' ``lse``) -> ``sample_step`` on ``proc`` ->
-        ``token_commit`` (history, log-probs).  Three launches on one stream; the caller advances ``rng[1]``."""
-        from ..ops import sampling
-
-        temperature, top_k, top_p, eos = st["params"]
-        ctl = st["ctl"]
-        if logits.dtype not in (torch.bfloat16, torch.float32):  # (an fp64 model off the fast path)
-            logits = logits.float()
-        logits = logits.contiguous()
-        src = logits
-        if ctl.proc:
-            if st["proc"] is None or st["proc"].dtype != logits.dtype:
-                st["proc"] = torch.empty_like(logits)
-            src = st["proc"]
-        hist = st["hist"] if ctl.penal else None
-        lse = st["lse"] if ctl.logprobs else None
-        sampling.logit_process(logits, hist, st["bias"] if ctl.bias is not None else None, ctl.rp, ctl.pp, ctl.fp,
-                               src if ctl.proc else None, lse)
-        sampling.sample_step(src, temperature, top_k, top_p, st["rng"], st["ids"], st["out"], st["step"], st["done"], eos)
-        if ctl.penal or ctl.logprobs:
-            sampling.token_commit(st["out"], st["rng"], hist, logits, lse, st["logprob"] if ctl.logprobs else None)
-
-    # ------------------------------------------------------------------ per-row device sampler (continuous batching)
-    def _sampler_state_rows(self, penal: bool = False, logprobs: bool = False, bias: Tensor | None = None):
-        """The per-row device sampler's static state (ragged sessions; ``models/serving.py`` drives it): a
-        :class:`~bpe_transformer.ops.sampling.SamplingTable` whose ``step`` is the session's own decode step, ``ids
-        [B, 1]``, ``out [B, max_len]`` and, once a switch asks for them, ``hist [B, V]``, ``proc [B, V]``, ``lse [B]``,
-        ``logprob [B, max_len]``, ``bias [V]``.  With ``use_graph`` the step -- decode -> ``logit_process_rows`` ->
-        ``sample_rows`` -> ``token_commit_rows`` (:meth:`_sample_rows`) -- is captured like ``_capture``: one stream,
-        no parallel branches.  Every sampling parameter is read from the table, so the graph's key holds only the
-        structural switches -- a penalty table is in use (``penal``), log-probs are recorded (``logprobs``), there is
-        a shared bias.  A switch stays on once it is on; turning one on later captures once more, a change of
-        parameter values never does.  ``st["captures"]`` counts the graphs captured.  During a capture's warm-up run
-        every slot is idle, so it writes nothing the running requests would see."""
+    def _sampler_state(self, penal: bool = False, logprobs: bool = False, bias: Tensor | None = None):
+        """The device sampler's static state, shared by ``generate(sampler="device")`` and ``models/serving.py``: a
+        :class:`~bpe_transformer.ops.sampling.SamplingTable` (its ``step`` is a ragged fast session's own decode step,
+        else the table's own), ``ids [B, 1]`` (the next token: the step's input), ``out [B, max_len]`` (token ``i`` of
+        a slot in column ``i``) and, once a switch asks for them, ``hist [B, V]``, ``proc [B, V]``, ``lse [B]``,
+        ``logprob [B, max_len]``, ``bias [V]``; their contents are the caller's to initialise.  Every sampling
+        parameter is read from the table, so only the three structural switches select what runs: a penalty table is
+        in use (``penal``), log-probs are recorded (``logprobs``), there is a shared bias.  They are this call's, not
+        sticky: ``st["key"]`` holds them, :meth:`_sample_rows` passes only the buffers they name, and with all three
+        off nothing but ``sample_rows`` runs.  With ``use_graph`` the step -- decode -> ``logit_process_rows`` ->
+        ``sample_rows`` -> ``token_commit_rows`` -- is captured once per key (``st["graphs"]``; ``st["captures"]``
+        counts them) and a change of parameter values never captures.  During a capture's warm-up run every slot is
+        idle, so it writes nothing the running requests would see."""
         from ..ops.sampling import SamplingTable
 
-        assert self.ragged, "the per-row sampler needs DecodeSession(..., ragged=True)"
         B, dev, V = self.batch, self.device, self.model.lm_head.weight.shape[0]
-        st = self._samp_rows
+        st = self._samp
         if st is None:
-            st = self._samp_rows = {
+            st = self._samp = {
                 "table": SamplingTable(B, dev, self._step),
                 "ids": torch.zeros(B, 1, dtype=torch.long, device=dev),
                 "out": torch.full((B, self.max_len), -1, dtype=torch.long, device=dev),
-                "penal": False, "logprobs": False, "bias": None, "hist": None, "proc": None, "lse": None,
-                "logprob": None, "graph": None, "key": None, "captures": 0,
+                "hist": None, "proc": None, "lse": None, "logprob": None, "bias": None,
+                "key": None, "graphs": {}, "captures": 0,
             }
             self._step_host = [0] * B  # (what the table's step holds: every slot idle)
-        if penal and not st["penal"]:
-            st["penal"] = True
+        if penal and st["hist"] is None:
             st["hist"] = torch.zeros(B, V, dtype=torch.int32, device=dev)
-        if logprobs and not st["logprobs"]:
-            st["logprobs"] = True
+        if logprobs and st["lse"] is None:
             st["lse"] = torch.zeros(B, dtype=torch.float32, device=dev)
             st["logprob"] = torch.full((B, self.max_len), math.nan, dtype=torch.float32, device=dev)
         if bias is not None:
             if st["bias"] is None:
                 st["bias"] = torch.zeros(V, dtype=torch.float32, device=dev)
             st["bias"].copy_(bias)
-        if (st["penal"] or st["bias"] is not None) and st["proc"] is None and self.fast:
+        if (penal or bias is not None) and st["proc"] is None and self.fast:
             st["proc"] = torch.empty(B, V, dtype=self.model.lm_head.weight.dtype, device=dev)
-        key = (st["penal"], st["logprobs"], st["bias"] is not None)
-        if self.use_graph and st["key"] != key:
+        st["key"] = key = (bool(penal), bool(logprobs), bias is not None)
+        if self.use_graph and key not in st["graphs"]:
             t = st["table"]
-
-            def run():
-                self._sample_rows(st, self._forward_fast(st["ids"], "decode", step=self._step))
-
             pos0, done0, step0 = self.cache.pos.clone(), t.done.clone(), t.step.clone()
             t.done.fill_(1)
             t.step.zero_()
-            s = torch.cuda.Stream(device=self.device)
-            s.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(s):
-                run()
-            torch.cuda.current_stream(self.device).wait_stream(s)
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                run()
-            self.cache.pos.copy_(pos0)
+            st["graphs"][key], _ = _capture_graph(
+                dev, lambda: self._sample_rows(st, self._forward_fast(st["ids"], "decode", step=self._step)),
+                lambda: self.cache.pos.copy_(pos0))
             t.done.copy_(done0)
             t.step.copy_(step0)
-            st["graph"], st["key"] = g, key
             st["captures"] += 1
         return st
 
     def _sample_rows(self, st, logits: Tensor, rows=None) -> None:
-        """One sampling step on the per-row state: ``logit_process_rows`` (only with a penalty table, a bias or
-        log-probs) -> ``sample_rows`` -> ``token_commit_rows`` (only with a penalty table or log-probs).  ``logits``
-        are the whole batch's, or with ``rows`` those of the named slots (an admission's prefill)."""
+        """One sampling step on the sampler's state, for the switches in ``st["key"]``: ``logit_process_rows`` (only
+        with a penalty table, a bias or log-probs) -> ``sample_rows`` -> ``token_commit_rows`` (only with a penalty
+        table or log-probs).  ``logits`` are the whole batch's, or with ``rows`` those of the named slots (an
+        admission's prefill)."""
         from ..ops import sampling
 
         t = st["table"]
+        penal, logprobs, biased = st["key"]
+        hist = st["hist"] if penal else None
+        bias = st["bias"] if biased else None
+        lse, logprob = (st["lse"], st["logprob"]) if logprobs else (None, None)
         if logits.dtype not in (torch.bfloat16, torch.float32):  # (an fp64 model off the fast path)
             logits = logits.float()
         logits = logits.contiguous()
         src = logits
-        proc = st["penal"] or st["bias"] is not None
+        proc = penal or biased
         if proc:
             full = st["proc"]
             if rows is not None or full is None or full.dtype != logits.dtype:
                 src = torch.empty_like(logits)  # (an admission's single row; off the fast path)
             else:
                 src = full
-        if proc or st["logprobs"]:
-            sampling.logit_process_rows(logits, t, st["hist"], st["bias"], src if proc else None, st["lse"], rows)
+        if proc or logprobs:
+            sampling.logit_process_rows(logits, t, hist, bias, src if proc else None, lse, rows)
         sampling.sample_rows(src, t, st["ids"], st["out"], rows)
-        if st["penal"] or st["logprobs"]:
-            sampling.token_commit_rows(st["out"], t, st["hist"], logits, st["lse"], st["logprob"], rows)
+        if penal or logprobs:
+            sampling.token_commit_rows(st["out"], t, hist, logits, lse, logprob, rows)
 
-    def _device_step_rows(self, st) -> None:
+    def _device_step(self, st) -> None:
         """Decode the tokens in ``st["ids"]`` and sample the next ones into it: one replay on the fast path."""
         if self.use_graph:
-            st["graph"].replay()
+            st["graphs"][st["key"]].replay()
             return
         if self.fast:
             logits = self._forward_fast(st["ids"], "decode", step=self._step)
@@ -1228,29 +1160,6 @@ class DecodeSession:
             logits = self._forward_reference(st["ids"], n, rows)
             self.cache.advance(rows, n)
         self._sample_rows(st, logits)
-
-    def _device_step(self, st) -> None:
-        """Decode the token in ``st["ids"]`` and sample the next one into it: one replay on the fast path."""
-        from ..ops import sampling
-
-        if self.use_graph:
-            st["graph"].replay()
-            return
-        step = st["step"]
-        if self.fast:
-            logits = self._forward_fast(st["ids"], "decode", step=self._step)
-        else:  # the oracle math reads host lengths: the step comes back per token (no graph to keep fed here)
-            rows = list(range(self.batch))
-            n = [1] * self.batch if step is None else [int(x) for x in step.tolist()]
-            logits = self._forward_reference(st["ids"], n, rows)
-            self.cache.advance(rows, n)
-        temperature, top_k, top_p, eos = st["params"]
-        if st["ctl"] is None:
-            sampling.sample_step(logits, temperature, top_k, top_p, st["rng"], st["ids"], st["out"], step, st["done"],
-                                 eos)
-        else:
-            self._sample_controlled(st, logits)
-        st["rng"][1:].add_(1)
 
     def _generate_device(self, prompt, max_new_tokens, temperature, top_k, top_p, eos_token_id, generator, seed,
                          sync_every, ctl=None):
@@ -1274,35 +1183,34 @@ class DecodeSession:
             gdev = generator.device if generator is not None else "cpu"
             seed = int(torch.randint(0, 2**62, (1,), generator=generator, device=gdev))
         eos = -1 if eos_token_id is None else int(eos_token_id)
-        top_k = int(top_k or 0)
-        top_p = 1.0 if top_p is None else float(top_p)
-        # A tensor prompt's finished rows keep generating until every row has finished, as with the host sampler, so
-        # their tokens are needed: no EOS for the kernel there, and `done` is read off `out` at each sync instead.
+        assert int(top_k or 0) >= 0, "top_k: 0 (off) or a positive count"
+        penal, bias = ctl is not None and ctl.penal, None if ctl is None else ctl.bias
         self.reset()
-        st = self._sampler_state(temperature, top_k, top_p, eos if as_list else -1, ctl)
-        st["rng"].copy_(torch.tensor([seed, 0], dtype=torch.long))
+        st = self._sampler_state(penal, lp, bias)
+        # Every slot takes the call's parameters and one seed; the Philox row word is the row, so row b draws token i
+        # at counter (i, b): `sample_step`'s stream.  The host loop bounds the count (no limit in the table: a row
+        # that has not finished keeps step 1).  A tensor prompt's finished rows keep generating until every row has
+        # finished, as with the host sampler, so their tokens are needed: no EOS for the kernel there, and `done` is
+        # read off `out` at each sync instead.
+        t = st["table"]
+        rp, pp, fp = (ctl.rp, ctl.pp, ctl.fp) if ctl is not None else (1.0, 0.0, 0.0)
+        t.set(slice(0, B), sampling.SamplingParams(
+            temperature=temperature, top_k=top_k, top_p=top_p, min_p=0.0, seed=seed, max_new_tokens=2**31 - 1,
+            eos_token_id=eos if as_list and eos >= 0 else None, repetition_penalty=rp, presence_penalty=pp,
+            frequency_penalty=fp))
+        t.philox_row.copy_(torch.arange(B, dtype=torch.int32))
+        self._step_host = [1] * B
         st["out"].fill_(-1)
-        st["done"].zero_()
-        if ctl is not None:  # (after _sampler_state: a capture's warm-up run has written all of them)
-            if ctl.penal:
-                st["hist"].copy_(sampling.prompt_hist(ids, n if as_list else None, st["hist"].shape[1]))
+        if penal:
+            st["hist"].copy_(sampling.prompt_hist(ids, n if as_list else None, st["hist"].shape[1]))
+        if lp:
             st["logprob"].fill_(math.nan)
-        step = st["step"]
-        if step is not None:
-            step.fill_(1)
-            self._step_host = [1] * B
-        logits = self.prefill(ids, n if as_list else None)
-        if ctl is None:
-            sampling.sample_step(logits, temperature, top_k, top_p, st["rng"], st["ids"], st["out"], step, st["done"],
-                                 st["params"][3])
-        else:
-            self._sample_controlled(st, logits)
-        st["rng"][1:].add_(1)
+        self._sample_rows(st, self.prefill(ids, n if as_list else None))
         made = 1  # tokens sampled per row
         upto = 0  # a paged cache has pages for the first `upto` fed tokens of every row
         while made < max_new_tokens:
             if eos >= 0 and made % sync_every == 0:  # the only host sync of the loop
-                done = st["done"] != 0 if as_list else (st["out"][:, :made] == eos).any(1)
+                done = t.done != 0 if as_list else (st["out"][:, :made] == eos).any(1)
                 if bool(done.all()):
                     break
             if made > upto:
@@ -1342,17 +1250,9 @@ class DecodeSession:
         the current position (rewritten by the first replay) and the position is restored afterwards."""
         self._static_ids = torch.zeros(self.batch, 1, dtype=torch.long, device=self.device)
         pos0 = self.cache.pos.clone()
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            self._forward_fast(self._static_ids, "decode", step=self._step)
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        self.cache.pos.copy_(pos0)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._static_logits = self._forward_fast(self._static_ids, "decode", step=self._step)
-        self.cache.pos.copy_(pos0)  # capture does not execute, but keep the invariant explicit
-        self._graph = g
+        self._graph, self._static_logits = _capture_graph(
+            self.device, lambda: self._forward_fast(self._static_ids, "decode", step=self._step),
+            lambda: self.cache.pos.copy_(pos0))
 
     def _hip(self):
         """The HIP ops handle both fast forwards run on (the one seam: a test substitutes a spy here)."""
@@ -1630,21 +1530,13 @@ class SpeculativeSession:
             s.cache._len[:] = [int(x) for x in s.cache.pos.tolist()]
 
     def _capture(self, key) -> None:
-        """Capture one round for ``key = (temperature, eos, max_new_tokens)`` (baked into the graph), like
-        ``DecodeSession._capture``: a warm-up run on a side stream, then the capture, on benign state at position 0
-        (the caller initialises every buffer afterwards)."""
+        """Capture one round for ``key = (temperature, eos, max_new_tokens)`` (baked into the graph) with
+        ``_capture_graph``, on benign state at position 0 (the caller initialises every buffer afterwards)."""
         temperature, eos, n = key
         out = self._st["out"][:, :n]
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(s):
-            self._round(temperature, eos, out)
-        torch.cuda.current_stream(self.device).wait_stream(s)
-        self._init_state(0)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._round(temperature, eos, out)
-        self._graph, self._key = g, key
+        self._graph, _ = _capture_graph(self.device, lambda: self._round(temperature, eos, out),
+                                        lambda: self._init_state(0))
+        self._key = key
 
     def _init_state(self, seed: int) -> None:
         st, K = self._st, self.K

@@ -14,8 +14,10 @@ limit are one column of the session's :class:`~bpe_transformer.ops.sampling.Samp
 ``sample_rows`` / ``logit_process_rows`` / ``token_commit_rows`` (``ops/sampling.py``, "Per-row forms"), so one
 captured graph -- decode step, then those three -- serves every mix of requests: ``eng.captures`` stays 1 whatever
 the parameters are (a request that is the first to use a penalty, or the first to ask for log-probs, switches the
-corresponding table on and captures once more).  A request's random stream is Philox keyed by its own seed at its
-own token index, so its tokens do not depend on its slot, its neighbours or its arrival time.
+corresponding table on and captures once more; the session's switches are per call, so the engine asks with what
+it has used so far and a switch stays on once it is on).  A request's random stream is Philox keyed by its own seed
+at its own token index, so its tokens do not depend on its slot, its neighbours or its arrival time.
+``DecodeSession.generate(sampler="device")`` runs on the same table and the same captured step.
 
 One :meth:`ServingEngine.step` is one *window*:
 
@@ -99,7 +101,7 @@ class ServingEngine:
         self.batch, self.max_len, self.sync_every = int(batch), s.max_len, int(sync_every)
         self.vocab = model.lm_head.weight.shape[0]
         ctl = _controls(self.vocab, s.device, 1.0, 0.0, 0.0, logit_bias, False)
-        self._st = s._sampler_state_rows(penal=penalties, logprobs=logprobs, bias=None if ctl is None else ctl.bias)
+        self._st = s._sampler_state(penal=penalties, logprobs=logprobs, bias=None if ctl is None else ctl.bias)
         self._slots: list[_Request | None] = [None] * self.batch
         self._waiting: collections.deque[_Request] = collections.deque()
         self._next_rid = 0
@@ -179,12 +181,16 @@ class ServingEngine:
                 return  # first come first served: nobody overtakes it
             self._waiting.popleft()
             b, p = free[0], req.params
-            if (p.penal and not st["penal"]) or (p.logprobs and not st["logprobs"]):
-                s._sampler_state_rows(penal=p.penal, logprobs=p.logprobs)  # a structural switch: captures once more
+            penal, logprobs, biased = st["key"]
+            if (p.penal and not penal) or (p.logprobs and not logprobs):
+                # a structural switch, on once it is on (the session's are per call: ask with what was used so far);
+                # captures once more
+                penal, logprobs = penal or p.penal, logprobs or p.logprobs
+                s._sampler_state(penal, logprobs, st["bias"] if biased else None)
             st["table"].set(b, p)
-            if st["penal"]:
+            if penal:
                 st["hist"][b].copy_(prompt_hist(req.prompt[None].to(s.device), None, self.vocab)[0])
-            if st["logprobs"]:
+            if logprobs:
                 st["logprob"][b].fill_(math.nan)
             st["out"][b].fill_(-1)
             self._slots[b] = req
@@ -207,7 +213,7 @@ class ServingEngine:
         if n > 0:
             c.reserve(live, [min(c._len[b] + n, tot) for b, tot in zip(live, total)])
             for _ in range(n):
-                s._device_step_rows(st)
+                s._device_step(st)
         done, count = t.done.tolist(), t.count.tolist()  # the window's one sync
         finished = []
         for b in live:

@@ -276,7 +276,7 @@ void launch_token_commit(const CommitArgs& a, int B, hipStream_t s);
 // by b.  A slot with done[b] != 0 or step[b] == 0 is idle: it writes nothing at all.
 //
 // sample_rows.hip: sample_kernel's algorithm with every parameter read from the slot's tables, plus min_p.  The
-// uniform is u[r], or Philox keyed by seed[b] at counter (count[b], 0, 0).  An active slot writes ids[b] =
+// uniform is u[r], or Philox keyed by seed[b] at counter (count[b], philox_row[b], 0).  An active slot writes ids[b] =
 // out[b][count[b]] = token, then count[b] += 1; token == eos[b] (eos >= 0) or count[b] >= limit[b] sets done[b] = 1
 // and step[b] = 0.
 struct SampleRowsArgs {
@@ -289,6 +289,7 @@ struct SampleRowsArgs {
     const double* top_p;       // [B]  >= 1: off
     const float* min_p;        // [B]  <= 0: off
     const long long* seed;     // [B]
+    const int* philox_row;     // [B]  the Philox row word (sample_kernel's: the row)
     long long* count;          // [B]
     const int* limit;          // [B]
     const int* eos;            // [B]  < 0: none

@@ -27,8 +27,9 @@
 // are, so equal logits (most of a row shares a few exponent bins) never serialise the atomics.
 //
 // The row addressing, Philox, the argmax, the order-independent sums and the index-order draw live in
-// sample_common.h, which spec_verify.hip shares; so do the radix select and the tie cut (Filt, radix_select,
-// cut_ties), which sample_rows.hip -- this kernel with every parameter read per row -- shares.
+// sample_common.h, which spec_verify.hip shares; so do the radix select, the tie cut and the row's whole draw (Filt,
+// radix_select, cut_ties, sample_row), which sample_rows.hip -- this kernel with every parameter read per row --
+// shares: this kernel is sample_row with min_p = 0 plus the scalar epilogue.
 #include "sample_common.h"
 
 namespace bpe {
@@ -36,17 +37,10 @@ namespace {
 
 template <typename T>
 __global__ void __launch_bounds__(S_NT) sample_kernel(SampleArgs a) {
-    typedef RowT<T> R;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int row = blockIdx.x;
     Ctx<T> c;
     c.init(a.logits, (long)row, a.V, smem);
-
-    // ---- argmax: highest key, lowest index among equals
-    unsigned bk;
-    int bi;
-    row_argmax(c, bk, bi);
-    int tok = bi;  // greedy, and what every degenerate row (all NaN, no mass) falls back to: always inside [0, V)
 
     // ---- the uniform: given, or Philox4x32-10 keyed by the seed at counter (count, row, 0)
     long long count = 0;
@@ -59,24 +53,8 @@ __global__ void __launch_bounds__(S_NT) sample_kernel(SampleArgs a) {
         u = a.u[row];
     }
 
-    if (a.temperature > 0.f) {
-        c.xmax = R::key_val(bk);
-        c.invT = 1.f / a.temperature;
-        Filt f{0u, a.V - 1};
-        unsigned K, r, n;
-        if (a.top_k > 0 && a.top_k < a.V) {
-            radix_select<T, false>(c, f, (u64)a.top_k, 0.0, K, r, n);
-            f = cut_ties(c, f, K, r, n);
-        }
-        if (a.top_p < 1.0) {
-            radix_select<T, true>(c, f, 0, a.top_p, K, r, n);
-            f = cut_ties(c, f, K, r, n);
-        }
-        const int i = prefix_find(
-            c, [&](unsigned raw, unsigned key, int i) -> u64 { return f.has(key, i) ? c.zq(raw) : 0; },
-            [&](u64 M) -> u64 { return draw_target(u, M); });
-        if (i >= 0 && i < a.V) tok = i;
-    }
+    // ---- the token (sample_common.h): steps 1-4 of the header; min_p = 0 keeps every mass z >= 0
+    const int tok = sample_row(c, a.temperature, a.top_k, a.top_p, 0.f, u);
 
     if (threadIdx.x == 0) {
         if (a.res != nullptr) a.res[row] = tok;

@@ -5,8 +5,9 @@
 // The function (ops/sampling.py states it in full; tests/sample_rows_refs.py is its fp64 oracle).  Launched row r is
 // slot b = rows[r] (no map: b = r).  The logits are row r of [R][V]; everything else is indexed by b:
 //   * idle: done[b] != 0 or step[b] == 0 -> the workgroup returns before its first barrier and writes nothing;
-//   * u = u[r] if given, else Philox4x32-10 keyed by seed[b] at counter (count[b], 0, 0): the row word is 0, not
-//     the slot, so a request's stream depends on neither its slot nor its neighbours;
+//   * u = u[r] if given, else Philox4x32-10 keyed by seed[b] at counter (count[b], philox_row[b], 0): the row word
+//     comes from the table, not from the slot.  0 (a served request) makes the stream depend on neither the slot nor
+//     its neighbours; philox_row[b] = b with one seed for all slots is sample.hip's stream (generate);
 //   * token = sample.hip's draw with temperature[b], top_k[b], top_p[b] (fp64, as the scalar kernel's ceil(top_p * Z)
 //     is computed in double) and, new here, min_p[b]: of what top-k and top-p kept, a token stays iff its fixed-point
 //     mass zq >= ceil(min_p * zq_max); zq_max = 2^40 is the argmax's, so the argmax always stays (sample_row,
@@ -34,7 +35,7 @@ __global__ void __launch_bounds__(S_NT) sample_rows_kernel(SampleRowsArgs a) {
     c.init(a.logits, (long)r, a.V, smem);
 
     const long long count = a.count[b];
-    const float u = a.u != nullptr ? a.u[r] : philox_u((u64)a.seed[b], (u64)count, 0u, 0u);
+    const float u = a.u != nullptr ? a.u[r] : philox_u((u64)a.seed[b], (u64)count, (unsigned)a.philox_row[b], 0u);
     int top_k = a.top_k[b];
     if (top_k > a.V) top_k = a.V;
     const int tok = sample_row(c, a.temperature[b], top_k, a.top_p[b], a.min_p[b], u);

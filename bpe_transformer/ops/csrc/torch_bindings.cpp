@@ -1541,8 +1541,8 @@ const int* rows_map(const c10::optional<at::Tensor>& rows, int64_t R, int64_t B,
 
 void sample_rows(const at::Tensor& logits, const c10::optional<at::Tensor>& rows, const c10::optional<at::Tensor>& u,
                  const at::Tensor& temperature, const at::Tensor& top_k, const at::Tensor& top_p,
-                 const at::Tensor& min_p, const at::Tensor& seed, at::Tensor count, const at::Tensor& limit,
-                 const at::Tensor& eos, at::Tensor step, at::Tensor done, at::Tensor ids, at::Tensor out) {
+                 const at::Tensor& min_p, const at::Tensor& seed, const at::Tensor& philox_row, at::Tensor count,
+                 const at::Tensor& limit, const at::Tensor& eos, at::Tensor step, at::Tensor done, at::Tensor ids, at::Tensor out) {
     check_cuda(logits, "logits");
     TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(), "sample_rows: logits must be contiguous [R, V]");
     const int64_t R = logits.size(0), V = logits.size(1), B = done.numel();
@@ -1561,8 +1561,8 @@ void sample_rows(const at::Tensor& logits, const c10::optional<at::Tensor>& rows
                 "sample_rows: temperature and min_p must be contiguous fp32 GPU tensors [B]");
     TORCH_CHECK(rows_tab(top_p, at::kDouble, B), "sample_rows: top_p must be a contiguous fp64 GPU tensor [B]");
     TORCH_CHECK(rows_tab(top_k, at::kInt, B) && rows_tab(limit, at::kInt, B) && rows_tab(eos, at::kInt, B) &&
-                    rows_tab(step, at::kInt, B) && rows_tab(done, at::kInt, B),
-                "sample_rows: top_k, limit, eos, step and done must be contiguous int32 GPU tensors [B]");
+                    rows_tab(step, at::kInt, B) && rows_tab(done, at::kInt, B) && rows_tab(philox_row, at::kInt, B),
+                "sample_rows: top_k, limit, eos, step, done and philox_row must be contiguous int32 GPU tensors [B]");
     TORCH_CHECK(rows_tab(seed, at::kLong, B) && rows_tab(count, at::kLong, B) && rows_tab(ids, at::kLong, B),
                 "sample_rows: seed, count and ids must be contiguous int64 GPU tensors [B]");
     TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kLong && out.dim() == 2 && out.size(0) == B &&
@@ -1572,6 +1572,7 @@ void sample_rows(const at::Tensor& logits, const c10::optional<at::Tensor>& rows
     a.top_p = top_p.data_ptr<double>();
     a.min_p = min_p.data_ptr<float>();
     a.seed = (const long long*)seed.data_ptr<int64_t>();
+    a.philox_row = philox_row.data_ptr<int>();
     a.count = (long long*)count.data_ptr<int64_t>();
     a.limit = limit.data_ptr<int>();
     a.eos = eos.data_ptr<int>();
@@ -1845,7 +1846,7 @@ TORCH_LIBRARY(bpe_hip, m) {
     m.def("token_commit(Tensor tokens, Tensor rng, Tensor(a!)? hist, Tensor? raw_logits, Tensor? lse, "
           "Tensor(b!)? logprob) -> ()");
     m.def("sample_rows(Tensor logits, Tensor? rows, Tensor? u, Tensor temperature, Tensor top_k, Tensor top_p, "
-          "Tensor min_p, Tensor seed, Tensor(a!) count, Tensor limit, Tensor eos, Tensor(b!) step, Tensor(c!) done, "
+          "Tensor min_p, Tensor seed, Tensor philox_row, Tensor(a!) count, Tensor limit, Tensor eos, Tensor(b!) step, Tensor(c!) done, "
           "Tensor(d!) ids, Tensor(e!) out) -> ()");
     m.def("logit_process_rows(Tensor logits, Tensor? rows, Tensor? hist, Tensor? bias, Tensor rp, Tensor inv_rp, "
           "Tensor pp, Tensor fp, Tensor step, Tensor done, Tensor(a!)? out, Tensor(b!)? lse) -> ()");

@@ -131,9 +131,11 @@ writes nothing and its counter stands (``spec_verify_step``'s rule, not ``sample
 
 :func:`sample_rows`, for an active slot, with ``c = count[b]``:
 
-1. ``u = u[r]`` if uniforms are given, else Philox4x32-10 keyed by ``seed[b]`` at counter ``(c, 0, 0)``.  The row
-   word is 0, not the slot: a request's random stream depends on neither its slot nor its neighbours, and equals
-   a one-row ``sample_step`` at ``rng = (seed[b], c)``.
+1. ``u = u[r]`` if uniforms are given, else Philox4x32-10 keyed by ``seed[b]`` at counter ``(c, philox_row[b], 0)``.
+   The row word is a column of the table, not the slot.  Its default 0 is a served request's: the random stream
+   depends on neither the slot nor its neighbours, and equals a one-row ``sample_step`` at ``rng = (seed[b], c)``.
+   ``philox_row[b] = b`` with one seed in every slot is ``sample_step``'s stream at ``rng = (seed, c)``, which is
+   how ``generate(sampler="device")`` runs on this function.
 2. The token is the sampling function at the top of this docstring with ``temperature[b]`` (fp32), ``top_k[b]``
    (int32), ``top_p[b]`` (fp64: the kernel computes ``ceil(top_p * Z)`` in double, as the scalar one does on its
    double argument) and one more filter between steps 5 and 6: ``min_p[b] > 0`` (fp32; the min-p sampling of Nguyen
@@ -182,12 +184,13 @@ def philox4x32(key: tuple[int, int], counter: tuple[int, int, int, int], rounds:
     return c0, c1, c2, c3
 
 
-def philox_uniform(seed: int, count: int, B: int, device=None, stream: int = 0) -> Tensor:
-    """The uniforms :func:`sample_step` draws for rows ``0 .. B-1`` at ``rng = (seed, count)``: fp32 ``[B]``.
-    ``stream`` is the fourth counter word (1, 2: the accept tests and the final draw of :func:`spec_verify_step`)."""
+def philox_uniform(seed: int, count: int, B: int, device=None, stream: int = 0, row0: int = 0) -> Tensor:
+    """The uniforms :func:`sample_step` draws for rows ``row0 .. row0 + B - 1`` at ``rng = (seed, count)``: fp32
+    ``[B]``.  ``stream`` is the fourth counter word (1, 2: the accept tests and the final draw of
+    :func:`spec_verify_step`)."""
     seed, count = int(seed) & (2**64 - 1), int(count) & (2**64 - 1)
     key = (seed & _M32, seed >> 32)
-    x0 = [philox4x32(key, (count & _M32, count >> 32, b, int(stream)))[0] for b in range(B)]
+    x0 = [philox4x32(key, (count & _M32, count >> 32, (row0 + b) & _M32, int(stream)))[0] for b in range(B)]
     u = (torch.tensor([x >> 8 for x in x0], dtype=torch.float64) + 0.5) * 2.0**-24
     return u.to(torch.float32).to(device)
 
@@ -207,13 +210,16 @@ def sample_logits(logits: Tensor, temperature: float, top_k: int, top_p: float, 
     return sample_logits_reference(logits, temperature, top_k, top_p, u)
 
 
-def sample_logits_reference(logits: Tensor, temperature: float, top_k: int, top_p: float, u: Tensor) -> Tensor:
-    """The function of the module docstring in torch: fp64 masses, a stable sort for the rank order."""
+def sample_logits_reference(logits: Tensor, temperature: float, top_k: int, top_p: float, u: Tensor,
+                            min_p: float = 0.0) -> Tensor:
+    """The function of the module docstring in torch: fp64 masses, a stable sort for the rank order.  ``temperature``
+    counts as the kernels receive it, rounded to fp32.  ``min_p > 0`` adds the min-p filter of "Per-row forms"."""
     x = logits.double()
     B, V = x.shape
+    temperature = _f32(temperature)
     if temperature <= 0:
         return (x == x.amax(-1, keepdim=True)).int().argmax(-1)  # (argmax of a 0/1 row: its first 1)
-    z = torch.exp((x - x.amax(-1, keepdim=True)) / float(temperature))
+    z = torch.exp((x - x.amax(-1, keepdim=True)) / temperature)
     order = torch.sort(x, dim=-1, descending=True, stable=True).indices  # equal x stay in index order
     zs = z.gather(-1, order)
     keep = torch.ones_like(zs, dtype=torch.bool)
@@ -222,6 +228,10 @@ def sample_logits_reference(logits: Tensor, temperature: float, top_k: int, top_
     if top_p < 1.0:
         zk = zs * keep
         keep &= zk.cumsum(-1) - zk < float(top_p) * zk.sum(-1, keepdim=True)
+        keep[:, 0] = True
+    if min_p > 0:
+        thr = min(math.ceil(_f32(min_p) * 2.0**40), 2**40)  # ceil(min_p * zq_max), zq_max = 2^40
+        keep &= torch.floor(zs * 2.0**40) >= thr
         keep[:, 0] = True
     kept = torch.zeros_like(keep).scatter_(-1, order, keep)
     zk = z * kept
@@ -585,6 +595,7 @@ class SamplingParams:
     frequency_penalty: float = 0.0
     logprobs: bool = False
     logit_bias: object = None  # not supported per request (the bias is one [V] tensor for all slots): ValueError
+    philox_row: int = 0  # the Philox row word: the request's stream is (seed, its own token index, philox_row)
 
     @property
     def penal(self) -> bool:
@@ -594,8 +605,8 @@ class SamplingParams:
 class SamplingTable:
     """The per-slot device tables of the ``*_rows`` functions (module docstring, "Per-row forms"), ``B`` slots:
     ``temperature``, ``min_p``, ``rp``, ``inv_rp``, ``pp``, ``fp`` fp32; ``top_p`` fp64; ``top_k``, ``limit``, ``eos``,
-    ``done``, ``step`` int32; ``seed``, ``count``, ``committed`` int64 -- all ``[B]``, contiguous and static, so a
-    captured graph reads them.  Tables of one type are the rows of one tensor: :meth:`set` is one small copy per
+    ``done``, ``philox_row``, ``step`` int32; ``seed``, ``count``, ``committed`` int64 -- all ``[B]``, contiguous and
+    static, so a captured graph reads them.  Tables of one type are the rows of one tensor: :meth:`set` is one small copy per
     type, in stream order.  ``step`` may be a tensor the caller already owns (a ragged session's decode step).
     Every slot starts idle (``done = 1``, ``step = 0``)."""
 
@@ -603,11 +614,11 @@ class SamplingTable:
         self.B, self.device = int(B), device
         self._f32 = torch.zeros(6, B, dtype=torch.float32, device=device)
         self._f64 = torch.ones(1, B, dtype=torch.float64, device=device)
-        self._i32 = torch.zeros(4, B, dtype=torch.int32, device=device)
+        self._i32 = torch.zeros(5, B, dtype=torch.int32, device=device)
         self._i64 = torch.zeros(3, B, dtype=torch.long, device=device)
         self.temperature, self.min_p, self.rp, self.inv_rp, self.pp, self.fp = self._f32.unbind(0)
         self.top_p = self._f64[0]
-        self.top_k, self.limit, self.eos, self.done = self._i32.unbind(0)
+        self.top_k, self.limit, self.eos, self.done, self.philox_row = self._i32.unbind(0)
         self.seed, self.count, self.committed = self._i64.unbind(0)
         self.step = torch.zeros(B, dtype=torch.int32, device=device) if step is None else step
         assert self.step.dtype == torch.int32 and self.step.numel() == B and self.step.is_contiguous()
@@ -617,8 +628,8 @@ class SamplingTable:
         self.done.fill_(1)
         self.step.zero_()
 
-    def set(self, b: int, p: SamplingParams) -> None:
-        """Slot ``b`` takes the request ``p`` and becomes active at token 0."""
+    def set(self, b: int | slice, p: SamplingParams) -> None:
+        """Slot ``b`` (a slice: every slot of it) takes the request ``p`` and becomes active at token 0."""
         if not float(p.repetition_penalty) > 0:
             raise ValueError(f"repetition_penalty must be > 0, got {p.repetition_penalty}")
         if getattr(p, "logit_bias", None) is not None:
@@ -626,15 +637,16 @@ class SamplingTable:
         top_k = int(p.top_k or 0)
         if top_k < 0:
             raise ValueError(f"top_k: 0 / None (off) or a positive count, got {p.top_k}")
-        s = slice(b, b + 1)
+        s = b if isinstance(b, slice) else slice(b, b + 1)
         self._f32[:, s].copy_(torch.tensor(
             [[float(p.temperature)], [float(p.min_p or 0.0)], [_f32(p.repetition_penalty)],
              [_inv_f32(p.repetition_penalty)], [float(p.presence_penalty)], [float(p.frequency_penalty)]],
             dtype=torch.float32))
         self._f64[:, s].copy_(torch.tensor([[1.0 if p.top_p is None else float(p.top_p)]], dtype=torch.float64))
         eos = -1 if p.eos_token_id is None else int(p.eos_token_id)
-        self._i32[:, s].copy_(torch.tensor([[min(top_k, 2**31 - 1)], [int(p.max_new_tokens)], [eos], [0]],
-                                           dtype=torch.int32))
+        row = int(p.philox_row) & _M32
+        self._i32[:, s].copy_(torch.tensor([[min(top_k, 2**31 - 1)], [int(p.max_new_tokens)], [eos], [0],
+                                            [row - 2**32 if row >= 2**31 else row]], dtype=torch.int32))
         seed = int(p.seed) & (2**64 - 1)
         self._i64[:, s].copy_(torch.tensor([[seed - 2**64 if seed >= 2**63 else seed], [0], [0]], dtype=torch.long))
         self.step[s].fill_(1)
@@ -667,41 +679,10 @@ def sample_rows(logits: Tensor, table: SamplingTable, ids: Tensor, out: Tensor, 
     rows = _rows_arg(rows, logits.shape[0], t.B, logits.device)
     if logits.is_cuda:
         ops().sample_rows(logits.contiguous(), rows, None if u is None else u.to(logits.device, torch.float32).contiguous(),
-                          t.temperature, t.top_k, t.top_p, t.min_p, t.seed, t.count, t.limit, t.eos, t.step, t.done,
-                          ids, out)
+                          t.temperature, t.top_k, t.top_p, t.min_p, t.seed, t.philox_row, t.count, t.limit, t.eos,
+                          t.step, t.done, ids, out)
         return
     sample_rows_reference(logits, table, ids, out, rows, u)
-
-
-def sample_min_p_reference(logits: Tensor, temperature: float, top_k: int, top_p: float, min_p: float,
-                           u: Tensor) -> Tensor:
-    """:func:`sample_logits_reference` with the min-p filter of the module docstring (``min_p <= 0``: exactly that
-    function)."""
-    if temperature <= 0 or not min_p > 0:
-        return sample_logits_reference(logits, temperature, top_k, top_p, u)
-    x = logits.double()
-    B, V = x.shape
-    z = torch.exp((x - x.amax(-1, keepdim=True)) / float(temperature))
-    order = torch.sort(x, dim=-1, descending=True, stable=True).indices
-    zs = z.gather(-1, order)
-    keep = torch.ones_like(zs, dtype=torch.bool)
-    if top_k > 0:
-        keep &= torch.arange(V, device=x.device)[None, :] < min(int(top_k), V)
-    if top_p < 1.0:
-        zk = zs * keep
-        keep &= zk.cumsum(-1) - zk < float(top_p) * zk.sum(-1, keepdim=True)
-        keep[:, 0] = True
-    thr = min(math.ceil(_f32(min_p) * 2.0**40), 2**40)  # ceil(min_p * zq_max), zq_max = 2^40
-    keep &= torch.floor(zs * 2.0**40) >= thr
-    keep[:, 0] = True
-    kept = torch.zeros_like(keep).scatter_(-1, order, keep)
-    zk = z * kept
-    cum = zk.cumsum(-1)
-    M = cum[:, -1:]
-    hit = (cum > u.to(x.device).double().reshape(B, 1) * M) & (zk > 0)
-    idx = torch.arange(V, device=x.device)
-    last = torch.where(zk > 0, idx, torch.zeros_like(idx)).amax(-1)
-    return torch.where(hit.any(-1), hit.int().argmax(-1), last)
 
 
 def sample_rows_reference(logits, table, ids, out, rows=None, u=None) -> None:
@@ -712,9 +693,10 @@ def sample_rows_reference(logits, table, ids, out, rows=None, u=None) -> None:
         if not 0 <= b < t.B or int(t.done[b]) != 0 or int(t.step[b]) == 0:
             continue
         c = int(t.count[b])
-        ur = u[r : r + 1].float() if u is not None else philox_uniform(int(t.seed[b]), c, 1, logits.device)
-        tok = int(sample_min_p_reference(logits[r : r + 1], float(t.temperature[b]), int(t.top_k[b]),
-                                         float(t.top_p[b]), float(t.min_p[b]), ur))
+        ur = u[r : r + 1].float() if u is not None else philox_uniform(int(t.seed[b]), c, 1, logits.device,
+                                                                       row0=int(t.philox_row[b]))
+        tok = int(sample_logits_reference(logits[r : r + 1], float(t.temperature[b]), int(t.top_k[b]),
+                                          float(t.top_p[b]), ur, float(t.min_p[b])))
         ids.view(-1)[b] = tok
         if 0 <= c < out.shape[1]:
             out[b, c] = tok

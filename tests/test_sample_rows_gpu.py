@@ -184,3 +184,33 @@ def test_process_and_commit_rows_equal_scalar_kernels(gpu_device, V, dtype):
     again = (h2.clone(), lp.clone())
     S.token_commit_rows(toks, t, h2, x, lse, lp)  # nothing drawn since: nothing committed
     assert torch.equal(h2, again[0]) and torch.equal(lp.nan_to_num(), again[1].nan_to_num())
+
+
+MODES = ((0.0, 0, 1.0), (0.8, 50, 1.0), (0.8, 0, 0.95), (0.8, 50, 0.95))  # greedy, top-k, top-p, both
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=("bf16", "fp32"))
+@pytest.mark.parametrize("V", (1025, 50257))
+def test_philox_row_is_sample_step_row(gpu_device, V, dtype):
+    """One seed in every slot and ``philox_row[b] = b``: ``sample_step``'s stream at ``rng = (seed, count)``, token
+    for token (how ``generate`` runs on the table); a slot left at the default 0 is a one-row ``sample_step``."""
+    B, seed, dev = 4, 2**40 + 5, gpu_device
+    x = SR.random_rows(V + 2, B, V, dtype).to(dev)
+    for T, k, p in MODES if V == 1025 else MODES[3:]:
+        for count in (0, 1, 2**32 + 5):
+            t = S.SamplingTable(B, dev)
+            t.set(slice(0, B), S.SamplingParams(temperature=T, top_k=k, top_p=p, seed=seed, max_new_tokens=2**31 - 1))
+            t.philox_row.copy_(torch.tensor([0, 1, 2, 0], dtype=torch.int32))
+            t.count.fill_(count)
+            ids, out = buffers(dev, B)
+            S.sample_rows(x, t, ids, out)
+            rng = torch.tensor([seed, count], device=dev)
+            i1, o1 = buffers(dev, B, 1)
+            S.sample_step(x, T, k, p, rng, i1, o1, None, torch.zeros(B, dtype=torch.int32, device=dev), -1)
+            i2, o2 = buffers(dev, 1, 1)
+            S.sample_step(x[3:4], T, k, p, rng, i2, o2, None, torch.zeros(1, dtype=torch.int32, device=dev), -1)
+            assert ids.view(-1).tolist() == i1.view(-1).tolist()[:3] + [int(i2)], (T, k, p, count)
+            fin = int(count + 1 >= 2**31 - 1)  # (the limit is the table's largest: only a count past it ends a slot)
+            assert t.count.tolist() == [count + 1] * B and t.done.tolist() == [fin] * B and t.step.tolist() == [1 - fin] * B
+            if count < N_OUT:
+                assert out[:, count].tolist() == ids.view(-1).tolist()

@@ -152,3 +152,34 @@ def test_process_and_commit_rows_equal_scalar_reference(dtype):
     again = (h2.clone(), lp.clone())
     S.token_commit_rows_reference(toks, t, h2, x, lse, lp)  # nothing drawn since: nothing committed
     assert torch.equal(h2, again[0]) and torch.equal(lp.nan_to_num(), again[1].nan_to_num())
+
+
+MODES = ((0.0, 0, 1.0), (0.8, 50, 1.0), (0.8, 0, 0.95), (0.8, 50, 0.95))  # greedy, top-k, top-p, both
+
+
+@pytest.mark.parametrize("dtype", DTYPES, ids=("bf16", "fp32"))
+def test_philox_row_is_sample_step_row(dtype):
+    """One seed in every slot and ``philox_row[b] = b``: ``sample_step``'s stream at ``rng = (seed, count)``, token
+    for token (how ``generate`` runs on the table); a slot left at the default 0 is a one-row ``sample_step``."""
+    V, B, seed = 1025, 4, 2**40 + 5
+    x = SR.random_rows(V + 2, B, V, dtype)
+    for T, k, p in MODES:
+        for count in (0, 1, 2**32 + 5):
+            t = S.SamplingTable(B)
+            for b in range(B):
+                t.set(b, S.SamplingParams(temperature=T, top_k=k, top_p=p, seed=seed, max_new_tokens=2**31 - 1,
+                                          **({"philox_row": b} if b < 3 else {})))
+            assert t.philox_row.tolist() == [0, 1, 2, 0]
+            t.count.fill_(count)
+            ids, out = buffers(B)
+            S.sample_rows_reference(x, t, ids, out)
+            rng = torch.tensor([seed, count])
+            i1, o1 = buffers(B, 1)
+            S.sample_step_reference(x, T, k, p, rng, i1, o1, None, torch.zeros(B, dtype=torch.int32), -1)
+            i2, o2 = buffers(1, 1)
+            S.sample_step_reference(x[3:4], T, k, p, rng, i2, o2, None, torch.zeros(1, dtype=torch.int32), -1)
+            assert ids.view(-1).tolist() == i1.view(-1).tolist()[:3] + [int(i2)], (T, k, p, count)
+            fin = int(count + 1 >= 2**31 - 1)  # (the limit is the table's largest: only a count past it ends a slot)
+            assert t.count.tolist() == [count + 1] * B and t.done.tolist() == [fin] * B and t.step.tolist() == [1 - fin] * B
+    # the row word is read: rows 1 and 2 draw other uniforms than row 0
+    assert len({float(u) for u in S.philox_uniform(seed, 1, 3)}) == 3

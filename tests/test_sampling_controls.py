@@ -72,7 +72,8 @@ def test_minus_inf_bias_bans_the_argmax(model, sampler, temperature):
 @pytest.mark.parametrize("as_list", [False, True])
 def test_defaults_change_nothing_and_launch_nothing(model, monkeypatch, sampler, as_list):
     calls = []
-    for name in ("logit_process", "token_commit", "prompt_hist"):
+    # (the host sampler runs the scalar ops, the device sampler their per-row forms: neither may run by default)
+    for name in ("logit_process", "token_commit", "prompt_hist", "logit_process_rows", "token_commit_rows"):
         real = getattr(S, name)
         monkeypatch.setattr(S, name, lambda *a, _n=name, _r=real, **k: (calls.append(_n), _r(*a, **k))[1])
     prompt = [_prompt(1, m, seed=m)[0] for m in (3, 7)] if as_list else _prompt()
@@ -87,7 +88,8 @@ def test_defaults_change_nothing_and_launch_nothing(model, monkeypatch, sampler,
                       repetition_penalty=1.0, logit_bias={})
     assert (all(torch.equal(x, y) for x, y in zip(a, c)) if as_list else torch.equal(a, c)) and calls == []
     run(repetition_penalty=1.1, return_logprobs=True)
-    assert {"logit_process", "token_commit", "prompt_hist"} <= set(calls)  # (the spy does see them when they run)
+    ran = {c.removesuffix("_rows") for c in calls}
+    assert {"logit_process", "token_commit", "prompt_hist"} <= ran  # (the spy does see them when they run)
 
 
 def _model_logprobs(model, seq: torch.Tensor, n_prompt: int) -> tuple[torch.Tensor, torch.Tensor]:

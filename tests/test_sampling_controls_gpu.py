@@ -1,6 +1,8 @@
 """``generate(sampler="device", ...)`` with sampling controls on the MI355X: the captured step decode ->
-``logit_process`` -> ``sample_step`` -> ``token_commit`` must give exactly the tokens and log-probs of a hand loop over
-the public pieces on the same device (``prefill`` / ``decode`` without a graph, then the three ops)."""
+``logit_process_rows`` -> ``sample_rows`` -> ``token_commit_rows``, every value read from the sampling table, must give
+exactly the tokens and log-probs of a hand loop over the public scalar pieces on the same device (``prefill`` /
+``decode`` without a graph, then ``logit_process`` -> ``sample_step`` -> ``token_commit``).  The graphs are keyed by
+the three structural switches alone: values never capture, and a call leaves nothing behind for the next."""
 
 from __future__ import annotations
 
@@ -157,10 +159,10 @@ def test_changing_a_penalty_recaptures(gpu_device):
                                     return_logprobs=True, **c)
     sess = DecodeSession(model, 3, max_len=32)
     first = run(sess, **CTL)
-    g0, k0 = sess._samp["graph"], sess._samp["key"]
     other = dict(CTL, frequency_penalty=0.9)
     second = run(sess, **other)
-    assert sess._samp["graph"] is not g0 and sess._samp["key"] != k0
+    # the values live in the sampling table: another value replays the graph of the same three switches
+    assert sess._samp["captures"] == 1 and sess._samp["key"] == (True, True, True)
     fresh = run(DecodeSession(model, 3, max_len=32), **other)
     _same(second, (fresh[0].cpu(), fresh[1].cpu()), False)
     assert not torch.equal(first[0], second[0])
@@ -168,7 +170,7 @@ def test_changing_a_penalty_recaptures(gpu_device):
     _same(run(sess, **CTL), (first[0].cpu(), first[1].cpu()), False)
     # no controls at all: the key and the graph of a session that never had any
     plain = sess.generate(prompt, n, T, P, None, None, K, "device", SEED, 4)
-    assert sess._samp["key"] == (T, K, P, -1)
+    assert sess._samp["key"] == (False, False, False) and sess._samp["captures"] == 2
     assert torch.equal(plain, DecodeSession(model, 3, max_len=32).generate(prompt, n, T, P, None, None, K, "device",
                                                                            SEED, 4))
 
@@ -185,3 +187,79 @@ def test_gpt2_vocabulary_once(gpu_device):
                          **CTL)
     _same(got, want, False)
     assert not torch.isin(got[0][:, 6:], torch.tensor([11], device=gpu_device)).any()
+
+
+def _cpu(r):
+    """A ``generate`` result (a tensor, a list, or a ``(tokens, logprobs)`` pair of either) as a flat list on the CPU."""
+    parts = r if isinstance(r, tuple) else (r,)
+    return [x.cpu() for part in parts for x in (part if isinstance(part, list) else [part])]
+
+
+def _equal(a, b) -> bool:
+    a, b = _cpu(a), _cpu(b)
+    return len(a) == len(b) and all(torch.equal(x, y) for x, y in zip(a, b))
+
+
+def test_captures_once_per_set_of_switches_never_per_value(gpu_device):
+    model = _model(gpu_device)
+    prompt, n = _prompts(gpu_device, 1025, True), 10
+    bias = _bias(gpu_device, 1025)
+    sess = DecodeSession(model, 3, max_len=32, ragged=True)
+    gen = lambda t=T, k=K, p=P, eos=None, s=sess, **c: s.generate(prompt, n, t, p, eos, None, k, "device", SEED, 4, **c)  # noqa: E731
+    state = lambda s=sess: (s._samp["captures"], s._samp["key"])  # noqa: E731
+    first = gen()
+    assert state() == (1, (False, False, False))
+    for t, k, p, eos in ((0.0, None, None, None), (1.3, 5, None, 7), (0.7, None, 0.5, 300), (T, K, P, int(first[0][-2]))):
+        gen(t, k, p, eos)
+        assert state() == (1, (False, False, False)), (t, k, p, eos)
+    for c in (CTL, dict(CTL, frequency_penalty=0.9), dict(repetition_penalty=0.7), dict(presence_penalty=-0.5)):
+        gen(**c)
+        assert state() == (2, (True, False, False)), c
+    gen(return_logprobs=True)
+    assert state() == (3, (False, True, False))
+    gen(logit_bias=bias, return_logprobs=True, **CTL)
+    gen(0.5, 7, 0.8, 11, logit_bias={3: 1.5}, return_logprobs=True, **dict(CTL, presence_penalty=0.0))
+    assert state() == (4, (True, True, True))
+    gen(**CTL)  # a graph captured earlier is replayed, not captured again
+    assert state() == (4, (True, False, False))
+    # a plain call after controlled ones: the tokens and the key of a session that never had any
+    fresh = DecodeSession(model, 3, max_len=32, ragged=True)
+    assert _equal(gen(), gen(s=fresh)) and _equal(gen(), first)
+    assert state() == (4, (False, False, False)) and state(fresh) == (1, (False, False, False))
+
+
+@pytest.mark.parametrize("as_list", [False, True], ids=["tensor", "ragged"])
+def test_no_bias_leak(gpu_device, as_list):
+    model = _model(gpu_device)
+    prompt, n = _prompts(gpu_device, 1025, as_list), 10
+    gen = lambda s, **c: s.generate(prompt, n, T, P, None, None, K, "device", SEED, 4, **c)  # noqa: E731
+    want = gen(DecodeSession(model, 3, max_len=32, ragged=as_list))
+    # the bias bans every token the plain call emits: values left in the shared buffer would show
+    new = lambda r: torch.cat([x[-n:] for x in r]) if as_list else r[:, -n:].reshape(-1)  # noqa: E731
+    emitted = new(want)
+    sess = DecodeSession(model, 3, max_len=32, ragged=as_list)
+    banned = gen(sess, logit_bias={int(v): -math.inf for v in emitted.unique()})
+    assert not torch.isin(new(banned), emitted).any()
+    assert _equal(gen(sess), want) and sess._samp["key"] == (False, False, False)
+
+
+@pytest.mark.parametrize("as_list", [False, True], ids=["tensor-shared-pos", "ragged"])
+def test_generate_leaves_nothing_behind(gpu_device, as_list):
+    """After a ``generate`` without EOS every row is still active: one more ``decode`` of all rows advances every
+    length by one and returns the logits of a session without a graph that was driven the same way."""
+    model = _model(gpu_device)
+    prompt, n = _prompts(gpu_device, 1025, as_list), 9
+    got = []
+    for use_graph in (True, False):
+        sess = DecodeSession(model, 3, max_len=32, ragged=as_list, use_graph=use_graph)
+        toks = sess.generate(prompt, n, T, P, None, None, K, "device", SEED, 4)
+        t = sess._samp["table"]
+        assert t.done.tolist() == [0] * 3 and t.step.tolist() == [1] * 3 and t.count.tolist() == [n] * 3
+        before = list(sess.cache._len)
+        assert before == [len(p) + n - 1 for p in prompt]
+        last = torch.stack([x[-1] for x in toks]) if as_list else toks[:, -1]
+        logits = sess.decode(last)
+        assert sess.cache._len == [x + 1 for x in before]
+        assert sess.cache.pos.tolist() == (sess.cache._len if as_list else sess.cache._len[:1])
+        got.append((toks, logits))
+    assert _equal(got[0][0], got[1][0]) and torch.equal(got[0][1], got[1][1])

@@ -516,6 +516,43 @@ __device__ __forceinline__ void tile_rc(int t, int tiles_m, int tiles_n, int gm,
     tj = wb / rows;
 }
 
+// The staging half of epilogue_bf16: this lane's accumulators of tile rows [r0, r0 + 256 / NPASS) rounded to bf16
+// into the LDS image at stg.  ADDC (the plain GEMM with beta != 0): beta * C joins the fp32 accumulator here, read
+// from c0 (the first output element of the pass) as the 8-byte pieces of the accumulator layout, so the sum is
+// rounded to bf16 once -- as gemm.hip and splitk_reduce do.  (Adding C to the staged bf16 value in the write-back
+// rounded twice: acc 257, C 1 gave 256.)
+template <int F8, bool ADDC>
+__device__ __forceinline__ void stage_rows(const f32x4 (&acc)[8][4], char* stg, int g, int wl, int l, int r0,
+                                           float osc, const __bf16* c0, long ldc, float beta) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    // ADDC: buffer loads from the wave-uniform c0 -- one VGPR (this lane's byte offset in the pass) addresses all 32
+    // pieces, the (ib, jq) part of the offset is uniform; 64-bit addresses per piece spilled beside the accumulators
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    const auto rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)c0, 0, 0x7fffffff, 0x00020000);
+    const unsigned lane_off =
+        (unsigned)(((long)(128 * g + (l & 15) - r0) * ldc + 64 * wl + 4 * (l >> 4)) * 2);
+#endif
+#pragma unroll
+    for (int ib = 0; ib < 8; ++ib)
+#pragma unroll
+        for (int jq = 0; jq < 4; ++jq) {
+            const int i = 128 * g + 16 * ib + (l & 15) - r0;
+            const int j = 64 * wl + 16 * jq + 4 * (l >> 4);
+            f32x4 v = F8 != 0 ? acc[ib][jq] * osc : acc[ib][jq];
+            if constexpr (ADDC) {
+#if defined(__HIP_DEVICE_COMPILE__)
+                const u32x2 w = __builtin_amdgcn_raw_buffer_load_b64(
+                    rsrc, lane_off, (unsigned)(((long)(16 * ib) * ldc + 16 * jq) * 2), 0);
+                const u16x4 o = __builtin_bit_cast(u16x4, w);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] += beta * bf2f(o[e]);
+#endif
+            }
+            const u16x4 p = u16x4{f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
+            *reinterpret_cast<u16x4*>(stg + i * 512 + ((((j >> 3) ^ (i & 15))) << 4) + ((j & 7) << 1)) = p;
+        }
+}
+
 // bf16 epilogue: the tile is staged through LDS at stg as [256 / NPASS][512 B] images (16-byte chunk c of row i at
 // c ^ (i & 15)) and written back as whole rows.  NPASS 1: the whole tile at once (128 KiB, the one-tile kernel);
 // NPASS 2: group h's rows [128 h, +128) in pass h through one 64 KiB image (the persistent kernel, whose other
@@ -532,16 +569,13 @@ __device__ __forceinline__ void epilogue_bf16(const f32x4 (&acc)[8][4], char* st
     for (int h = 0; h < NPASS; ++h) {
         const int r0 = h * RP;  // first tile row of this pass
         if (NPASS == 1 || g == h) {
-#pragma unroll
-            for (int ib = 0; ib < 8; ++ib)
-#pragma unroll
-                for (int jq = 0; jq < 4; ++jq) {
-                    const int i = 128 * g + 16 * ib + (l & 15) - r0;
-                    const int j = 64 * wl + 16 * jq + 4 * (l >> 4);
-                    const f32x4 v = F8 != 0 ? acc[ib][jq] * osc : acc[ib][jq];
-                    const u16x4 p = u16x4{f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
-                    *reinterpret_cast<u16x4*>(stg + i * 512 + ((((j >> 3) ^ (i & 15))) << 4) + ((j & 7) << 1)) = p;
-                }
+            if constexpr (EPI == EPI_NONE) {
+                const __bf16* c0 = C + (long)(i0 + r0) * ldc + j0;
+                if (beta != 0.f) stage_rows<F8, true>(acc, stg, g, wl, l, r0, osc, c0, ldc, beta);
+                else stage_rows<F8, false>(acc, stg, g, wl, l, r0, osc, c0, ldc, beta);
+            } else {
+                stage_rows<F8, false>(acc, stg, g, wl, l, r0, osc, nullptr, 0, 0.f);
+            }
         }
         if constexpr (EPI == EPI_SWIGLU_BWD) {
             // every g / u load of this thread's row segments is issued before the barrier (the accumulators are in
@@ -703,14 +737,8 @@ __device__ __forceinline__ void epilogue_bf16(const f32x4 (&acc)[8][4], char* st
 #pragma unroll 4
             for (int q = 0; q < 16 / NPASS; ++q) {
                 const int i = q * 16 + (tid >> 5), c = tid & 31;
-                u16x8 v = *reinterpret_cast<const u16x8*>(stg + i * 512 + ((c ^ (i & 15)) << 4));
-                __bf16* cp = C + (long)(i0 + r0 + i) * ldc + j0 + c * 8;
-                if (beta != 0.f) {
-                    const u16x8 o = *reinterpret_cast<const u16x8*>(cp);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = f2bf(bf2f(v[e]) + beta * bf2f(o[e]));
-                }
-                *reinterpret_cast<u16x8*>(cp) = v;
+                const u16x8 v = *reinterpret_cast<const u16x8*>(stg + i * 512 + ((c ^ (i & 15)) << 4));
+                *reinterpret_cast<u16x8*>(C + (long)(i0 + r0 + i) * ldc + j0 + c * 8) = v;  // beta * C: added above
             }
         }
         if (h + 1 < NPASS || tail) {  // every read of the image retired before it is rewritten

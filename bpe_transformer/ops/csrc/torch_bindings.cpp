@@ -409,7 +409,8 @@ void gemm_pp(const at::Tensor& A, bool a_kmajor, const at::Tensor& B, bool b_kma
                 "gemm_pp: B shape mismatch");
     TORCH_CHECK(gemm_pp_shape_ok(M, N, R, (int)splits), "gemm_pp: M, N must be multiples of 256, R of 64 (>= splits)");
     TORCH_CHECK(A.stride(0) % 8 == 0 && B.stride(0) % 8 == 0 && C.stride(0) % 8 == 0, "gemm_pp: 16-byte row alignment");
-    TORCH_CHECK((A.stride(0) * 256) < (1L << 31) && (B.stride(0) * 256) < (1L << 31),
+    TORCH_CHECK((A.stride(0) * 256) < (1L << 31) && (B.stride(0) * 256) < (1L << 31) &&
+                    (C.stride(0) * 256) < (1L << 31),  // C: the one-pass beta != 0 epilogue reads it by tile offset
                 "gemm_pp: leading dimension too large for 32-bit tile offsets");
     DevGuard g(C.device());
     at::Tensor slab;

@@ -199,6 +199,20 @@ def _append_plan(T: int, G: int, filled: bool, prefill_chunk: int | None = None,
     return plan
 
 
+def _packed_groups(n: list[int], budget: int | None) -> list[list[int]]:
+    """Indices ``0 .. len(n) - 1`` cut, in order, into groups whose token counts ``n[i]`` sum to at most ``budget``
+    (``None``: one group).  A sequence is never split: one longer than the budget is a group of its own."""
+    groups, tot = [], 0
+    for i, x in enumerate(n):
+        if groups and (budget is None or tot + x <= budget):
+            groups[-1].append(i)
+            tot += x
+        else:
+            groups.append([i])
+            tot = x
+    return groups
+
+
 def _capture_graph(device, run, restore):
     """``run`` captured into a HIP graph -> ``(graph, what run returned inside the capture)``: a warm-up run on a side
     stream (first-use allocations and lazy initialisation must not happen inside a capture), then the capture on the
@@ -526,6 +540,26 @@ class KVView:
             return h.cache_attn_fp8(q, k, v, ks, vs, pos, H, scale, T, *self.pg)
         return h.decode_attn_fp8(q, k, v, ks, vs, pos, H, scale, combine, T, *self.pg)
 
+    def append_packed(self, h, qkv: Tensor, li: int, H: int, rope, pk) -> Tensor:
+        """:meth:`append` of packed rows (``ops/decode.py``, "Packed prefill"; ``pk`` a ``PackedPrompts``): each
+        sequence to its own slot of the whole cache's view, at that slot's position."""
+        assert self.n == self.cache.batch, "a packed pass runs on the whole cache"
+        if self.scales is None:
+            return h.kv_append_packed(qkv, self.k[li], self.v[li], rope[0], rope[1], self.pos, pk.seq, pk.seq_host, H,
+                                      rope[2], *self.pg)
+        ks, vs = self.scales
+        return h.kv_append_packed_fp8(qkv, self.k[li], self.v[li], ks[li], vs[li], rope[0], rope[1], self.pos, pk.seq,
+                                      pk.seq_host, H, rope[2], *self.pg)
+
+    def attend_packed(self, h, q: Tensor, li: int, H: int, pk) -> Tensor:
+        """``cache_attn_packed`` (fp8: ``cache_attn_packed_fp8``) of the packed rows just appended."""
+        k, v = self.k[li], self.v[li]
+        scale, work = 1.0 / math.sqrt(k.shape[-1]), pk.work(H // k.shape[1])
+        if self.scales is None:
+            return h.cache_attn_packed(q, k, v, self.pos, pk.seq, pk.seq_host, work, H, scale, *self.pg)
+        return h.cache_attn_packed_fp8(q, k, v, self.scales[0][li], self.scales[1][li], self.pos, pk.seq, pk.seq_host,
+                                       work, H, scale, *self.pg)
+
     def decode_qkv(self, h, xr: Tensor, xd, ln1: Tensor, eps: float, wqkv: Tensor, li: int, H: int, rope, ws=()):
         """QKV step of the skinny decode route -> ``(q, x + xd)``: the fused ``decode_qkv`` (projection, RoPE, cache
         write), or for fp8 ``decode_gemv`` with the plain epilogue followed by :meth:`append` (a row's amax spans
@@ -675,7 +709,8 @@ class DecodeSession:
     ``prefill`` / ``prefill_slot`` on a cache that already holds tokens (a second turn, a slot with a kept prefix)
     is one pass over the layers for the whole window (``cache_attn``), as on an empty cache.  ``prefill_chunk=c``
     cuts every prefill or append, ragged or not, into chunks of at most ``c`` tokens, which bounds activation memory
-    by ``B * c`` rows.
+    by ``B * c`` rows.  ``prefill_slots`` hands several slots to new requests in one pass over the layers on their
+    packed prompts (no padding: ``kv_append_packed`` + ``cache_attn_packed``, each sequence at its slot's own position).
 
     ``kv_dtype="fp8"`` keeps the cache as e4m3 rows with one power-of-two scale each (``csrc/kv_fp8.hip``;
     ``ops/decode.py`` states the format): ``(D + 4) / (2 D)`` of the bf16 cache's bytes.  Every step appends with
@@ -913,6 +948,43 @@ class DecodeSession:
         assert self.ragged, "slots need DecodeSession(..., ragged=True)"
         ids = ids.reshape(1, -1).to(self.device)
         return self._append(ids, [ids.shape[1]], [b])
+
+    @torch.no_grad()
+    def prefill_slots(self, rows: list[int], prompts: list[Tensor]) -> Tensor:
+        """Ragged sessions: append ``prompts[i]`` (``[T_i]`` ids) to sequence ``rows[i]`` for several distinct slots
+        at once; returns their logits ``[len(rows), V]``.  On the fast path the prompts are *packed* -- concatenated,
+        no padding -- and take one pass over the layers (``kv_append_packed`` + ``cache_attn_packed`` on the whole
+        cache, every sequence at its slot's own position; ``ops/decode.py``, "Packed prefill").  A slot may already
+        hold tokens (a second turn, a forked prefix): every sequence attends the cache as stored.  Pages for all the
+        rows are reserved first, so a pool that runs out raises before anything is launched.  The other slots' cache
+        rows and positions do not change and no address does, so a captured decode graph stays valid.
+
+        ``prefill_chunk`` splits a call whose packed token count exceeds it at sequence boundaries into several
+        passes; a single prompt longer than it goes through :meth:`prefill_slot`, which chunks it.  A row's logits
+        are those of :meth:`prefill_slot` up to GEMM rounding (the GEMMs' M is the packed count).  Off the fast path
+        the call is a loop over :meth:`prefill_slot`, the same function with the same bits."""
+        assert self.ragged, "slots need DecodeSession(..., ragged=True)"
+        rows = [int(r) for r in rows]
+        assert len(rows) == len(prompts) >= 1, "prefill_slots: one prompt per row, at least one"
+        assert len(set(rows)) == len(rows), "prefill_slots: rows must be distinct"
+        assert all(0 <= r < self.batch for r in rows), "prefill_slots: a row outside the batch"
+        prompts = [p.reshape(-1) for p in prompts]
+        n = [int(p.numel()) for p in prompts]
+        assert all(x >= 1 for x in n), "prefill_slots: empty prompt"
+        c = self.cache
+        assert all(c._len[r] + x <= self.max_len for r, x in zip(rows, n)), "KV cache full"
+        c.reserve(rows, [c._len[r] + x for r, x in zip(rows, n)])
+        if not self.fast:
+            return torch.cat([self.prefill_slot(r, p) for r, p in zip(rows, prompts)])
+        out = [None] * len(rows)
+        for grp in _packed_groups(n, self.prefill_chunk):
+            if len(grp) == 1 and self.prefill_chunk is not None and n[grp[0]] > self.prefill_chunk:
+                out[grp[0]] = self.prefill_slot(rows[grp[0]], prompts[grp[0]])
+                continue
+            lg = self._forward_packed([rows[i] for i in grp], [prompts[i] for i in grp])
+            for j, i in enumerate(grp):
+                out[i] = lg[j : j + 1]
+        return out[0] if len(out) == 1 else torch.cat(out)
 
     def _append(self, ids: Tensor, n: list[int], rows: list[int]) -> Tensor:
         """Every prefill: the first ``n[i]`` tokens of ``ids[i]`` (right-padded) go to sequence ``rows[i]`` -- the
@@ -1309,6 +1381,39 @@ class DecodeSession:
         logits = torch.matmul(hf, self._wide(h, self._head).t())
         if advance:
             kv.pos.add_(T if step is None else step)
+        return logits
+
+    def _forward_packed(self, rows: list[int], prompts: list[Tensor]) -> Tensor:
+        """One pass over the layers on the packed tokens of ``prompts`` (``prefill_slots``): ``_forward_fast``'s
+        launches on ``[N, .]`` rows, with ``kv_append_packed`` + ``cache_attn_packed`` on the whole cache; each
+        sequence's last row goes through the final norm and the head; ``pos[rows]`` advances by a device index add
+        and the host mirror follows.  Pages are reserved by the caller."""
+        from ..ops.decode import PackedPrompts
+
+        h, rope = self._hip(), self._rope
+        m, c, H = self.model, self.cache, self.H
+        n = [int(p.numel()) for p in prompts]
+        pk = PackedPrompts(rows, n, self.device, pos_host=[c._len[r] for r in rows])
+        kv = c.view()
+        xr = m.token_embeddings(torch.cat(prompts).to(self.device)).reshape(pk.N, -1)
+        xd = None
+        for li, (ln1, wqkv, wo, ln2, w13, w2, eps) in enumerate(self._w):
+            if xd is None:
+                h1, _ = h.rmsnorm_fwd(xr, ln1, eps)
+            else:
+                xr, h1, _ = h.add_rmsnorm_fwd(xr, xd, ln1, eps)
+            qkv = torch.matmul(h1, self._wide(h, wqkv).t())
+            o = kv.attend_packed(h, kv.append_packed(h, qkv, li, H, rope, pk), li, H, pk)
+            g1 = torch.matmul(o, self._wide(h, wo).t())
+            xr, h2, _ = h.add_rmsnorm_fwd(xr, g1, ln2, eps)
+            a = h.swiglu_fwd(torch.matmul(h2, self._wide(h, w13).t()))
+            xd = torch.matmul(a, self._wide(h, w2).t())
+        last = torch.tensor([off + x - 1 for off, x in zip(pk.offs, n)]).to(self.device)
+        fin = m.ln_final
+        _, hf, _ = h.add_rmsnorm_fwd(xr[last].contiguous(), xd[last].contiguous(), fin.weight, fin.eps)
+        logits = torch.matmul(hf, self._wide(h, self._head).t())
+        c.pos.index_add_(0, torch.tensor(rows).to(self.device), torch.tensor(n, dtype=torch.int32).to(self.device))
+        c.advance(rows, n)
         return logits
 
     def _gemv_fits(self, m: int) -> bool:

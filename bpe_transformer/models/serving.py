@@ -40,6 +40,18 @@ cannot run out mid-flight, and no request is ever preempted (preemption with rec
 whose budget does not fit waits, and those behind it wait with it (first come first served).  With
 ``kv_layout="slab"`` the rule is simply a free slot.
 
+**Packed admission** (``prefill_tokens=N``, off by default).  A window's admissions are selected first, by the same
+rules -- first come first served, lowest free slot, page budget, nobody overtakes a request that does not fit -- and
+then prefilled together: in arrival order they are cut into groups of at most ``N`` prompt tokens (a longer prompt is
+a group of its own), and a group costs one ``prefill_slots`` call -- one pass over the layers on the packed prompts,
+no padding -- and one ``sample_rows`` launch for all its first tokens, where the default pays one pass and one launch
+per request.  A structural switch that a request of the group needs is made before the group is prefilled.  What the
+option changes about the invariance claim above: a request's prompt now goes through GEMMs whose M depends on the
+requests admitted with it, so its first logits are equal up to GEMM rounding, not bit for bit, to those it would get
+alone, and a sampled or greedy near-tie may resolve differently.  The decode steps, the random stream (keyed by the
+request's seed and token index) and everything under ``prefill_tokens=None`` are unchanged; off the fast path
+``prefill_slots`` is a loop over ``prefill_slot`` and the two settings give the same tokens.
+
 Works with the fp8 cache, fp8 weights, chunked prefill, ``use_graph=False``, and off the fast path (CPU, fp32) on
 the reference ops, where it computes the same function.
 """
@@ -55,7 +67,7 @@ from torch import Tensor
 
 from ..ops.decode import KV_PAGE
 from ..ops.sampling import SamplingParams, prompt_hist
-from .generation import DecodeSession, _controls
+from .generation import DecodeSession, _controls, _packed_groups
 
 __all__ = ["RequestOutput", "SamplingParams", "ServingEngine"]
 
@@ -86,14 +98,19 @@ class ServingEngine:
     ``kv_layout`` / ``num_pages``, ``kv_dtype``, ``weight_dtype``, ``prefill_chunk`` and ``use_graph`` as
     :class:`DecodeSession` takes them; ``sync_every`` is the window.  ``logit_bias`` (a ``{token: value}`` dict or a
     ``[V]`` tensor) is one bias for every request of the engine.  ``penalties`` / ``logprobs`` switch the penalty
-    table / the log-prob record on from the start, so that the first request to use one does not capture again."""
+    table / the log-prob record on from the start, so that the first request to use one does not capture again.
+    ``prefill_tokens``: ``None``, one prefill pass and one sampling launch per admitted request; a positive token
+    budget, packed admission (module docstring)."""
 
     def __init__(self, model, batch: int, max_len: int | None = None, kv_layout: str = "slab",
                  num_pages: int | None = None, kv_dtype: str = "bf16", weight_dtype: str = "bf16",
                  sync_every: int = 8, prefill_chunk: int | None = None, use_graph: bool = True, logit_bias=None,
-                 penalties: bool = False, logprobs: bool = False):
+                 penalties: bool = False, logprobs: bool = False, prefill_tokens: int | None = None):
         if int(sync_every) < 1:
             raise ValueError(f"sync_every: a positive number of tokens, got {sync_every}")
+        if prefill_tokens is not None and int(prefill_tokens) < 1:
+            raise ValueError(f"prefill_tokens: None or a positive number of tokens, got {prefill_tokens}")
+        self.prefill_tokens = None if prefill_tokens is None else int(prefill_tokens)
         self.session = DecodeSession(model, batch, max_len=max_len, use_graph=use_graph, ragged=True,
                                      prefill_chunk=prefill_chunk, kv_dtype=kv_dtype, weight_dtype=weight_dtype,
                                      kv_layout=kv_layout, num_pages=num_pages)
@@ -169,7 +186,50 @@ class ServingEngine:
         self._waiting.append(req)
         return req.rid
 
+    def _switch(self, reqs) -> tuple[bool, bool]:
+        """Make the structural switches the requests ``reqs`` need (on once they are on: the session's are per call,
+        so ask with what was used so far; captures once more) -> the ``(penal, logprobs)`` in force."""
+        s, st = self.session, self._st
+        penal, logprobs, biased = st["key"]
+        want = (penal or any(r.params.penal for r in reqs), logprobs or any(r.params.logprobs for r in reqs))
+        if want != (penal, logprobs):
+            s._sampler_state(want[0], want[1], st["bias"] if biased else None)
+        return want
+
+    def _admit_packed(self) -> None:
+        """Packed admission (module docstring): select by :meth:`_admit`'s rules, then one ``prefill_slots`` and one
+        ``sample_rows`` per group of at most ``prefill_tokens`` prompt tokens."""
+        s, st = self.session, self._st
+        c = s.cache
+        free = [b for b, r in enumerate(self._slots) if r is None]
+        used = sum(r.pages for r in self._slots if r is not None)
+        picked: list[tuple[int, _Request]] = []
+        while self._waiting and free:
+            req = self._waiting[0]
+            if c.paged and used + req.pages > c.num_pages:
+                break  # first come first served: nobody overtakes it
+            self._waiting.popleft()
+            b = free.pop(0)
+            used += req.pages
+            self._slots[b] = req
+            picked.append((b, req))
+        for grp in _packed_groups([int(r.prompt.numel()) for _, r in picked], self.prefill_tokens):
+            members = [picked[i] for i in grp]
+            penal, logprobs = self._switch([r for _, r in members])
+            for b, req in members:
+                st["table"].set(b, req.params)
+                if penal:
+                    st["hist"][b].copy_(prompt_hist(req.prompt[None].to(s.device), None, self.vocab)[0])
+                if logprobs:
+                    st["logprob"][b].fill_(math.nan)
+                st["out"][b].fill_(-1)
+            rows = [b for b, _ in members]
+            logits = s.prefill_slots(rows, [r.prompt for _, r in members])
+            s._sample_rows(st, logits, rows=rows)
+
     def _admit(self) -> None:
+        if self.prefill_tokens is not None:
+            return self._admit_packed()
         s, st = self.session, self._st
         c = s.cache
         while self._waiting:

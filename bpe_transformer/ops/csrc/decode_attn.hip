@@ -43,7 +43,7 @@
 //   decode_attn_kernel<128, MR, Fp8Cache>   VGPRs 94 / 112 / 120 / 180   SGPRs 61 / 67 / 72 / 66   waves/SIMD 5 / 4 / 4 / 2
 //   LDS bytes, either format: D 64: 2336 / 4640 / 9248 / 18464, D 128: 3616 / 7200 / 14368 / 28704
 //   kv_append_kernel VGPRs 44, SGPRs 69   kv_append_fp8_kernel VGPRs 44, SGPRs 79   kv_dequant_kernel VGPRs 29   (8 waves)
-//   cache_attn_kernel<64 / 128, Bf16Cache>  VGPRs 118 / 176   SGPRs 43 / 43   LDS 32768 / 65536   waves/SIMD 4 / 2
+//   cache_attn_kernel<64 / 128, Bf16Cache>  VGPRs 118 / 176   SGPRs 41 / 41   LDS 32768 / 65536   waves/SIMD 4 / 2
 //   cache_attn_kernel<64 / 128, Fp8Cache>   VGPRs 122 / 184   SGPRs 52 / 54   LDS 25104 / 49680   waves/SIMD 4 / 2
 //     (flash_attn_cache.hip)
 // The format's scale loads and multiplies exist only in the Fp8Cache instantiations (`if constexpr`).
@@ -56,6 +56,15 @@
 //   kv_append_kernel<PagedLayout> VGPRs 42, SGPRs 72   kv_append_fp8_kernel<PagedLayout> VGPRs 42, SGPRs 83   (8 waves)
 //   cache_attn_kernel<64 / 128, Bf16Cache, PagedLayout>  VGPRs 118 / 176   SGPRs 48 / 47   waves/SIMD 4 / 2
 //   cache_attn_kernel<64 / 128, Fp8Cache, PagedLayout>   VGPRs 122 / 184   SGPRs 60 / 62   waves/SIMD 4 / 2
+// Packed map (kv_cache.h PackedMap / flash_attn_cache.hip PackedWork: the prompts of several slots in one launch).  One
+// body serves both maps; the rows above are the UniformMap instantiations, unchanged by it (cache_attn_kernel<., Bf16Cache>
+// on slabs went from 43 to 41 SGPRs).  The packed instantiations, slab / paged, LDS as the uniform twin, scratch 0:
+//   kv_append_kernel<., PackedMap>      VGPRs 42 / 40   SGPRs 69 / 72   kv_append_fp8_kernel<., PackedMap>  VGPRs 42 / 40
+//                                       SGPRs 81 / 84   (8 waves)
+//   cache_attn_kernel<64 / 128, Bf16Cache, SlabLayout, PackedWork>   VGPRs 118 / 176   SGPRs 40 / 40   waves/SIMD 4 / 2
+//   cache_attn_kernel<64 / 128, Bf16Cache, PagedLayout, PackedWork>  VGPRs 118 / 176   SGPRs 48 / 47   waves/SIMD 4 / 2
+//   cache_attn_kernel<64 / 128, Fp8Cache, SlabLayout, PackedWork>    VGPRs 122 / 184   SGPRs 52 / 54   waves/SIMD 4 / 2
+//   cache_attn_kernel<64 / 128, Fp8Cache, PagedLayout, PackedWork>   VGPRs 122 / 184   SGPRs 60 / 62   waves/SIMD 4 / 2
 #include "kv_cache.h"
 #include "kernels.h"
 
@@ -258,17 +267,20 @@ __global__ void __launch_bounds__(D) decode_combine_kernel(const float* __restri
 
 // KV-cache append into the bf16 cache: append_vec's (kv_cache.h) vector goes to q [B*T, H*D] or, roped K / plain V,
 // into the caches [B, Hkv, Lmax, D] (paged: the pools, through the block table).
-template <class Lay>
+// Map (kv_cache.h): UniformMap, B * T rows of T tokens per sequence, or PackedMap, the rows of several prompts end to
+// end, each to its own slot (kv_append_packed); the uniform instantiations take an empty `map`.
+template <class Lay, class Map>
 __global__ void __launch_bounds__(256) kv_append_kernel(const __bf16* __restrict__ qkv, long ld,
                                                         __bf16* __restrict__ qo, __bf16* __restrict__ Kc,
                                                         __bf16* __restrict__ Vc, const float* __restrict__ cosT,
                                                         const float* __restrict__ sinT, const int* __restrict__ pos,
                                                         int pstride, int T, int H, int Hkv, int D, int Lmax,
-                                                        long total, Lay lay) {
+                                                        long total, Lay lay, Map map) {
     const int pshared = pos[0];
     for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
         AppendVec a;
-        if (!append_vec(a, idx, total, qkv, ld, cosT, sinT, pos, pstride, pshared, T, H, Hkv, D, Lmax, lay)) continue;
+        if (!append_vec(a, idx, total, qkv, ld, cosT, sinT, pos, pstride, pshared, T, H, Hkv, D, Lmax, lay, map))
+            continue;
         __bf16* dst;
         if (a.hh < H) dst = qo + a.r * (long)H * D + (long)a.hh * D + a.d0;
         else dst = (a.hh < H + Hkv ? Kc : Vc) + a.row * D + a.d0;
@@ -327,17 +339,33 @@ void launch_decode_attn(const void* q, const void* k, const void* v, const float
     else launch_lay(q, k, v, ks, vs, part, out, pos, pos_stride, B, T, H, Hkv, D, Lmax, scale, SlabLayout{}, s);
 }
 
-void launch_kv_append(const void* qkv, long ld, void* qo, void* Kc, void* Vc, const float* cosT, const float* sinT,
-                      const int* pos, int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax, hipStream_t s,
-                      const KvPages& pg) {
-    const long total = (long)B * T * (H + 2 * Hkv) * (D / 8);
+// `rows` token rows in all: B * T of the uniform map, N of the packed one
+template <class Map>
+static void append_launch(const void* qkv, long ld, void* qo, void* Kc, void* Vc, const float* cosT, const float* sinT,
+                          const int* pos, int pos_stride, long rows, int T, int H, int Hkv, int D, int Lmax, Map map,
+                          hipStream_t s, const KvPages& pg) {
+    const long total = rows * (H + 2 * Hkv) * (D / 8);
     const long want = (total + 255) / 256;
     const int grid = (int)(want < 8192 ? want : 8192);
     if (pg.table != nullptr)
         kv_append_kernel<<<grid, 256, 0, s>>>((const __bf16*)qkv, ld, (__bf16*)qo, (__bf16*)Kc, (__bf16*)Vc, cosT,
                                               sinT, pos, pos_stride, T, H, Hkv, D, Lmax, total,
-                                              PagedLayout{pg.table, pg.NB, pg.P});
+                                              PagedLayout{pg.table, pg.NB, pg.P}, map);
     else
         kv_append_kernel<<<grid, 256, 0, s>>>((const __bf16*)qkv, ld, (__bf16*)qo, (__bf16*)Kc, (__bf16*)Vc, cosT,
-                                              sinT, pos, pos_stride, T, H, Hkv, D, Lmax, total, SlabLayout{});
+                                              sinT, pos, pos_stride, T, H, Hkv, D, Lmax, total, SlabLayout{}, map);
+}
+
+void launch_kv_append(const void* qkv, long ld, void* qo, void* Kc, void* Vc, const float* cosT, const float* sinT,
+                      const int* pos, int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax, hipStream_t s,
+                      const KvPages& pg) {
+    append_launch(qkv, ld, qo, Kc, Vc, cosT, sinT, pos, pos_stride, (long)B * T, T, H, Hkv, D, Lmax, UniformMap{}, s,
+                  pg);
+}
+
+void launch_kv_append_packed(const void* qkv, long ld, void* qo, void* Kc, void* Vc, const float* cosT,
+                             const float* sinT, const int* pos, const KvPacked& pk, int B, int H, int Hkv, int D,
+                             int Lmax, hipStream_t s, const KvPages& pg) {
+    append_launch(qkv, ld, qo, Kc, Vc, cosT, sinT, pos, 1, (long)pk.N, 1, H, Hkv, D, Lmax, PackedMap{pk.seq, pk.S, B},
+                  s, pg);
 }

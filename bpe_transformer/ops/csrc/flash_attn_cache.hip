@@ -193,12 +193,28 @@ template <int D> struct PagedRequest<D, kvc::Fp8Cache> {
     }
 };
 
+// The packed form's work (kv_cache.h PackedMap; cache_attn_packed): workgroup blockIdx.x is kv head blockIdx.x % Hkv of
+// item blockIdx.x / Hkv of a host-built list `work [W, 2]` of (sequence, 128-row query block), heaviest first.  A
+// sequence's blocks count from its own row 0, so a block never straddles two sequences and everything a workgroup
+// computes -- q0, p0, L, the limits, ntiles -- is what the uniform kernel computes for that slot alone with T = n: the
+// same bits.  The table and the list are device data like pos: every value read from them is clamped into range, so
+// no content of either addresses outside q / o (N rows) or the cache.
+struct PackedWork {
+    static constexpr bool packed = true;
+    kvc::PackedMap map;
+    const int* work;
+    int N;
+};
+
 // Lay (kv_cache.h): the cache layout.  The slab instantiations take an empty `lay` and are the code they were.
-template <int D, class C, class Lay = kvc::SlabLayout>
+// Map: kvc::UniformMap (B sequences of Tu tokens, workgroups from blockIdx and nqb; an empty `map`) or PackedWork
+// (Tu, nqb and pstride are not read).
+template <int D, class C, class Lay = kvc::SlabLayout, class Map = kvc::UniformMap>
 __global__ void __launch_bounds__(256, 2)
 cache_attn_kernel(const __bf16* __restrict__ Q, const typename C::elem* __restrict__ Kc,
                   const typename C::elem* __restrict__ Vc, __bf16* __restrict__ O, const int* __restrict__ pos,
-                  int pstride, int H, int Hkv, int Lmax, int T, float scale_log2, int nqb, Scales<C> sc, Lay lay) {
+                  int pstride, int H, int Hkv, int Lmax, int Tu, float scale_log2, int nqb, Scales<C> sc, Lay lay,
+                  Map map) {
     constexpr int RB = D * 2;      // bytes per LDS row
     constexpr int TILE = 64 * RB;  // bytes per 64-key tile
     constexpr int KS = D / 16;     // k-steps over the head dim
@@ -214,13 +230,32 @@ cache_attn_kernel(const __bf16* __restrict__ Q, const typename C::elem* __restri
 
     const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, l31 = l & 31, hh = l >> 5;
     const int wu = __builtin_amdgcn_readfirstlane(w);
-    const int BK = (int)gridDim.x / nqb;
-    const int bk = (int)blockIdx.x % BK;               // b * Hkv + hk
-    const int qb = nqb - 1 - (int)blockIdx.x / BK;     // heaviest (last) row blocks first
-    const int b = bk / Hkv, hk = bk % Hkv;
+    int bk, qb, b, hk, T;
+    [[maybe_unused]] int qoff = 0;  // packed: first row of the sequence in Q / O
+    if constexpr (Map::packed) {
+        const int item = (int)blockIdx.x / Hkv;
+        hk = (int)blockIdx.x % Hkv;
+        const int i = min(max(map.work[2 * item], 0), map.map.S - 1);
+        qb = max(map.work[2 * item + 1], 0);
+        b = map.map.slot(i);
+        T = min(max(map.map.n(i), 1), map.N);
+        qoff = min(max(map.map.off(i), 0), map.N - T);
+        bk = b * Hkv + hk;
+    } else {
+        const int BK = (int)gridDim.x / nqb;
+        bk = (int)blockIdx.x % BK;               // b * Hkv + hk
+        qb = nqb - 1 - (int)blockIdx.x / BK;     // heaviest (last) row blocks first
+        b = bk / Hkv, hk = bk % Hkv;
+        T = Tu;
+    }
+    // row of token `tok` of this sequence in Q / O
+    const auto qo_row = [&](int tok) -> long {
+        if constexpr (Map::packed) return (long)qoff + tok;
+        else return (long)b * T + tok;
+    };
     const int G = H / Hkv, R = G * T;
     // any int32 contents of pos give in-range tiles: 0 <= p0 <= Lmax, 1 <= L <= Lmax
-    const int p0 = min(max(pos[b * pstride], 0), Lmax);
+    const int p0 = min(max(pos[Map::packed ? b : b * pstride], 0), Lmax);
     const int L = min(p0 + T, Lmax);  // rows of the slab that hold this sequence's keys
     const int q0 = qb * 128, qw0 = q0 + 32 * wu;
     const int qrow = qw0 + l31;
@@ -231,7 +266,7 @@ cache_attn_kernel(const __bf16* __restrict__ Q, const typename C::elem* __restri
     // the Q rows and K / V tile 0 are requested before any is waited for
     u16x8 qr[KS];
     {
-        const __bf16* qp = Q + (((long)b * T + tok) * H + head) * D;
+        const __bf16* qp = Q + (qo_row(tok) * H + head) * D;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) qr[ks] = *reinterpret_cast<const u16x8*>(qp + 16 * ks + 8 * hh);
     }
@@ -382,7 +417,7 @@ cache_attn_kernel(const __bf16* __restrict__ Q, const typename C::elem* __restri
             // conversion pass, and with it the last atomicMin, lies before a barrier this wave has passed)
             if (*vbad <= lim) inv = __uint_as_float(0x7fc00000u);
         }
-        __bf16* op = O + (((long)b * T + tok) * H + head) * D;
+        __bf16* op = O + (qo_row(tok) * H + head) * D;
 #pragma unroll
         for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
@@ -427,7 +462,27 @@ static void cache_launch_lay(const void* q, const void* k, const void* v, cache:
     typedef const typename C::elem* cptr;
     const int nqb = ((H / Hkv) * T + 127) / 128;
     cache::cache_attn_kernel<D, C, Lay><<<nqb * B * Hkv, 256, cache::lds_bytes<D, C>(), s>>>(
-        (const __bf16*)q, (cptr)k, (cptr)v, (__bf16*)out, pos, pstride, H, Hkv, Lmax, T, scale * LOG2E, nqb, sc, lay);
+        (const __bf16*)q, (cptr)k, (cptr)v, (__bf16*)out, pos, pstride, H, Hkv, Lmax, T, scale * LOG2E, nqb, sc, lay,
+        kvc::UniformMap{});
+}
+
+// The packed form: one workgroup per (work item, kv head), in the list's order (the host sorts it heaviest first).
+template <int D, class C>
+static void cache_launch_packed(const void* q, const void* k, const void* v, cache::Scales<C> sc, void* out,
+                                const int* pos, const KvPacked& pk, int B, int H, int Hkv, int Lmax, float scale,
+                                const KvPages& pg, hipStream_t s) {
+    typedef const typename C::elem* cptr;
+    const cache::PackedWork map{kvc::PackedMap{pk.seq, pk.S, B}, pk.work, pk.N};
+    const int grid = pk.W * Hkv;
+    if (pg.table != nullptr)
+        cache::cache_attn_kernel<D, C, kvc::PagedLayout, cache::PackedWork>
+            <<<grid, 256, cache::lds_bytes<D, C>(), s>>>((const __bf16*)q, (cptr)k, (cptr)v, (__bf16*)out, pos, 1, H,
+                                                         Hkv, Lmax, 0, scale * LOG2E, 0, sc,
+                                                         kvc::PagedLayout{pg.table, pg.NB, pg.P}, map);
+    else
+        cache::cache_attn_kernel<D, C, kvc::SlabLayout, cache::PackedWork>
+            <<<grid, 256, cache::lds_bytes<D, C>(), s>>>((const __bf16*)q, (cptr)k, (cptr)v, (__bf16*)out, pos, 1, H,
+                                                         Hkv, Lmax, 0, scale * LOG2E, 0, sc, kvc::SlabLayout{}, map);
 }
 
 template <int D, class C>
@@ -453,4 +508,20 @@ void launch_cache_attn_fp8(const void* q, const void* k8, const void* v8, const 
     const cache::Scales<kvc::Fp8Cache> sc{ks, vs};
     if (D == 64) cache_launch<64, kvc::Fp8Cache>(q, k8, v8, sc, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, pg, s);
     else cache_launch<128, kvc::Fp8Cache>(q, k8, v8, sc, out, pos, pos_stride, B, T, H, Hkv, Lmax, scale, pg, s);
+}
+
+void launch_cache_attn_packed(const void* q, const void* k, const void* v, void* out, const int* pos,
+                              const KvPacked& pk, int B, int H, int Hkv, int D, int Lmax, float scale, hipStream_t s,
+                              const KvPages& pg) {
+    const cache::Scales<kvc::Bf16Cache> none{};
+    if (D == 64) cache_launch_packed<64, kvc::Bf16Cache>(q, k, v, none, out, pos, pk, B, H, Hkv, Lmax, scale, pg, s);
+    else cache_launch_packed<128, kvc::Bf16Cache>(q, k, v, none, out, pos, pk, B, H, Hkv, Lmax, scale, pg, s);
+}
+
+void launch_cache_attn_packed_fp8(const void* q, const void* k8, const void* v8, const float* ks, const float* vs,
+                                  void* out, const int* pos, const KvPacked& pk, int B, int H, int Hkv, int D, int Lmax,
+                                  float scale, hipStream_t s, const KvPages& pg) {
+    const cache::Scales<kvc::Fp8Cache> sc{ks, vs};
+    if (D == 64) cache_launch_packed<64, kvc::Fp8Cache>(q, k8, v8, sc, out, pos, pk, B, H, Hkv, Lmax, scale, pg, s);
+    else cache_launch_packed<128, kvc::Fp8Cache>(q, k8, v8, sc, out, pos, pk, B, H, Hkv, Lmax, scale, pg, s);
 }

@@ -150,6 +150,14 @@ struct KvPages {
     const int* table = nullptr;
     int NB = 0, P = 0;
 };
+// Packed prefill (kv_cache.h PackedMap): q / qkv rows are the N tokens of S sequences end to end.  `seq` is the device
+// int32 table [S, 3] of (slot, off, n); `work` (the attention only) the device int32 list [W, 2] of (sequence, 128-row
+// query block) items, heaviest first.  pos is per slot ([B], read as pos[slot]); the block table's row is the slot.
+struct KvPacked {
+    const int* seq = nullptr;
+    const int* work = nullptr;
+    int S = 0, N = 0, W = 0;
+};
 int kv_page_rows();  // kvc::KV_PAGE (kv_cache.h, the one definition), for the bindings' shape checks
 int decode_attn_splits(int Lmax);
 bool decode_attn_ok(int H, int Hkv, int D, int T);
@@ -177,6 +185,22 @@ bool cache_attn_fp8_ok(int H, int Hkv, int D, int T, int Lmax);
 void launch_cache_attn_fp8(const void* q, const void* k8, const void* v8, const float* ks, const float* vs, void* out,
                            const int* pos, int pos_stride, int B, int T, int H, int Hkv, int D, int Lmax, float scale,
                            hipStream_t s, const KvPages& pg = KvPages{});
+// The packed forms (B: slots of the cache).  Appends: the prologue and epilogue of launch_kv_append(_fp8) with the
+// token's (slot, position) taken from pk.seq.  Attention: cache_attn_kernel's body, one workgroup per (pk.work item,
+// kv head); a sequence's row blocks start at its own row 0, so its rows are, bit for bit, those of launch_cache_attn
+// on that slot alone.
+void launch_kv_append_packed(const void* qkv, long ld, void* qo, void* Kc, void* Vc, const float* cosT,
+                             const float* sinT, const int* pos, const KvPacked& pk, int B, int H, int Hkv, int D,
+                             int Lmax, hipStream_t s, const KvPages& pg = KvPages{});
+void launch_kv_append_packed_fp8(const void* qkv, long ld, void* qo, void* k8, void* v8, float* ks, float* vs,
+                                 const float* cosT, const float* sinT, const int* pos, const KvPacked& pk, int B, int H,
+                                 int Hkv, int D, int Lmax, hipStream_t s, const KvPages& pg = KvPages{});
+void launch_cache_attn_packed(const void* q, const void* k, const void* v, void* out, const int* pos,
+                              const KvPacked& pk, int B, int H, int Hkv, int D, int Lmax, float scale, hipStream_t s,
+                              const KvPages& pg = KvPages{});
+void launch_cache_attn_packed_fp8(const void* q, const void* k8, const void* v8, const float* ks, const float* vs,
+                                  void* out, const int* pos, const KvPacked& pk, int B, int H, int Hkv, int D, int Lmax,
+                                  float scale, hipStream_t s, const KvPages& pg = KvPages{});
 
 // decode_gemv.hip (M <= 16 token rows; epi 0 plain, 1 SwiGLU over [W1; W3], 2 fused QKV + RoPE + KV-cache write)
 struct GemvArgs {

@@ -19,6 +19,13 @@
 // The table is device data like pos, and no content of either may address outside the pool: a reader clamps the page
 // id into [0, P - 1] (page_clamped), a writer whose entry is outside [0, P) writes nothing (paged_row).  The layout
 // is a compile-time property: the slab instantiations take an empty argument and are the code they were.
+//
+// A third policy is the token MAP -- which sequence and which of its tokens a row of q / qkv is.  UniformMap: B
+// sequences of T tokens each, row b * T + t, the cache slot is b.  PackedMap: the prompts of several sequences laid
+// end to end with no padding, described by a host-written device int32 table [S, 3] of (slot, off, n) -- the cache
+// slot (row of pos, of the slab batch and of the block table), the sequence's first packed row and its token count;
+// offs ascend and off[i + 1] = off[i] + n[i].  The position of a packed sequence is pos[slot], read on the device.
+// Like the layout it is a compile-time property, and the uniform instantiations take an empty argument.
 #pragma once
 #include "common.h"
 
@@ -48,6 +55,29 @@ struct PagedLayout {
         const int pg = table[(long)b * NB + p / KV_PAGE];
         if ((unsigned)pg >= (unsigned)P) return -1;
         return ((long)pg * Hkv + hk) * KV_PAGE + p % KV_PAGE;
+    }
+};
+
+struct UniformMap {
+    static constexpr bool packed = false;
+};
+
+struct PackedMap {
+    static constexpr bool packed = true;
+    const int* seq;  // [S, 3]: (slot, off, n) per sequence
+    int S, B;        // sequences; slots of the cache (slot ids are checked on the host and clamped here)
+    __device__ __forceinline__ int slot(int i) const { return min(max(seq[3 * i], 0), B - 1); }
+    __device__ __forceinline__ int off(int i) const { return seq[3 * i + 1]; }
+    __device__ __forceinline__ int n(int i) const { return seq[3 * i + 2]; }
+    // the sequence that holds packed row r (0 <= r < N): the last one whose off is <= r
+    __device__ __forceinline__ int find(int r) const {
+        int lo = 0, hi = S - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (off(mid) <= r) lo = mid;
+            else hi = mid - 1;
+        }
+        return lo;
     }
 };
 
@@ -111,11 +141,13 @@ struct AppendVec {
 // (cache full: nothing is written past the end; per sequence, like the position itself).  `pshared` = pos[0].
 // Paged: also a negative position (pos is device data), and a K or V vector whose table entry is no page of the pool
 // (the D / 8 vectors of a row share the entry, so a row is written or dropped as a whole).
-template <class Lay = SlabLayout>
+// Packed (PackedMap): row r is token r - off_i of the sequence i that holds it, at position pos[slot_i] + r - off_i of
+// slot slot_i; T, pstride and pshared are not read.  A negative position is dropped like one at or past Lmax.
+template <class Lay = SlabLayout, class Map = UniformMap>
 __device__ __forceinline__ bool append_vec(AppendVec& a, long idx, long total, const __bf16* __restrict__ qkv, long ld,
                                            const float* __restrict__ cosT, const float* __restrict__ sinT,
                                            const int* __restrict__ pos, int pstride, int pshared, int T, int H, int Hkv,
-                                           int D, int Lmax, const Lay& lay = Lay{}) {
+                                           int D, int Lmax, const Lay& lay = Lay{}, const Map& map = Map{}) {
     a.x = u16x8{};
     if (idx >= total) return false;
     const int dv = D / 8, W = (H + 2 * Hkv) * dv;
@@ -123,8 +155,16 @@ __device__ __forceinline__ bool append_vec(AppendVec& a, long idx, long total, c
     const int c = (int)(idx % W);
     a.hh = c / dv;
     a.d0 = (c % dv) * 8;
-    const int b = (int)(a.r / T);
-    const int p = (pstride ? pos[b] : pshared) + (int)(a.r % T);
+    int b, p;
+    if constexpr (Map::packed) {
+        const int i = map.find((int)a.r);
+        b = map.slot(i);
+        p = pos[b] + ((int)a.r - map.off(i));
+        if (p < 0) return false;
+    } else {
+        b = (int)(a.r / T);
+        p = (pstride ? pos[b] : pshared) + (int)(a.r % T);
+    }
     if (p >= Lmax) return false;
     if constexpr (Lay::paged) {
         if (p < 0) return false;

@@ -51,18 +51,19 @@ __device__ __forceinline__ float row_scale(unsigned amax16, float& inv) {
 // kv_append_kernel (decode_attn.hip) with quantised K / V rows.  The loop bound is uniform per workgroup and every
 // lane runs the shuffles, so the D / 8 lanes of a row (same r, same head: all active or all skipped together) always
 // find each other; a lane with nothing to do carries zeros.
-template <class Lay>
+// Map (kv_cache.h): the uniform rows or the packed ones (kv_append_packed_fp8), as in kv_append_kernel.
+template <class Lay, class Map>
 __global__ void __launch_bounds__(256)
 kv_append_fp8_kernel(const __bf16* __restrict__ qkv, long ld, __bf16* __restrict__ qo, unsigned char* __restrict__ K8,
                      unsigned char* __restrict__ V8, float* __restrict__ Ks, float* __restrict__ Vs,
                      const float* __restrict__ cosT, const float* __restrict__ sinT, const int* __restrict__ pos,
-                     int pstride, int T, int H, int Hkv, int D, int Lmax, long total, Lay lay) {
+                     int pstride, int T, int H, int Hkv, int D, int Lmax, long total, Lay lay, Map map) {
     const int dv = D / 8;
     const int pshared = pos[0];
     for (long base = blockIdx.x * 256L; base < total; base += (long)gridDim.x * 256) {
         AppendVec a;
         const bool act = append_vec(a, base + threadIdx.x, total, qkv, ld, cosT, sinT, pos, pstride, pshared, T, H,
-                                    Hkv, D, Lmax, lay);
+                                    Hkv, D, Lmax, lay, map);
         const u16x8 x = a.x;
         unsigned am = 0;
 #pragma unroll
@@ -126,20 +127,36 @@ kv_dequant_kernel(const unsigned char* __restrict__ K8, const unsigned char* __r
 
 using namespace bpe::kv8;
 
-void launch_kv_append_fp8(const void* qkv, long ld, void* qo, void* k8, void* v8, float* ks, float* vs,
-                          const float* cosT, const float* sinT, const int* pos, int pos_stride, int B, int T, int H,
-                          int Hkv, int D, int Lmax, hipStream_t s, const KvPages& pg) {
-    const long total = (long)B * T * (H + 2 * Hkv) * (D / 8);
+// `rows` token rows in all: B * T of the uniform map, N of the packed one
+template <class Map>
+static void append8_launch(const void* qkv, long ld, void* qo, void* k8, void* v8, float* ks, float* vs,
+                           const float* cosT, const float* sinT, const int* pos, int pos_stride, long rows, int T,
+                           int H, int Hkv, int D, int Lmax, Map map, hipStream_t s, const KvPages& pg) {
+    const long total = rows * (H + 2 * Hkv) * (D / 8);
     const long want = (total + 255) / 256;
     const int grid = (int)(want < 8192 ? want : 8192);
     if (pg.table != nullptr)
         kv_append_fp8_kernel<<<grid, 256, 0, s>>>((const __bf16*)qkv, ld, (__bf16*)qo, (unsigned char*)k8,
                                                   (unsigned char*)v8, ks, vs, cosT, sinT, pos, pos_stride, T, H, Hkv,
-                                                  D, Lmax, total, PagedLayout{pg.table, pg.NB, pg.P});
+                                                  D, Lmax, total, PagedLayout{pg.table, pg.NB, pg.P}, map);
     else
         kv_append_fp8_kernel<<<grid, 256, 0, s>>>((const __bf16*)qkv, ld, (__bf16*)qo, (unsigned char*)k8,
                                                   (unsigned char*)v8, ks, vs, cosT, sinT, pos, pos_stride, T, H, Hkv,
-                                                  D, Lmax, total, SlabLayout{});
+                                                  D, Lmax, total, SlabLayout{}, map);
+}
+
+void launch_kv_append_fp8(const void* qkv, long ld, void* qo, void* k8, void* v8, float* ks, float* vs,
+                          const float* cosT, const float* sinT, const int* pos, int pos_stride, int B, int T, int H,
+                          int Hkv, int D, int Lmax, hipStream_t s, const KvPages& pg) {
+    append8_launch(qkv, ld, qo, k8, v8, ks, vs, cosT, sinT, pos, pos_stride, (long)B * T, T, H, Hkv, D, Lmax,
+                   UniformMap{}, s, pg);
+}
+
+void launch_kv_append_packed_fp8(const void* qkv, long ld, void* qo, void* k8, void* v8, float* ks, float* vs,
+                                 const float* cosT, const float* sinT, const int* pos, const KvPacked& pk, int B, int H,
+                                 int Hkv, int D, int Lmax, hipStream_t s, const KvPages& pg) {
+    append8_launch(qkv, ld, qo, k8, v8, ks, vs, cosT, sinT, pos, 1, (long)pk.N, 1, H, Hkv, D, Lmax,
+                   PackedMap{pk.seq, pk.S, B}, s, pg);
 }
 
 void launch_kv_dequant(const void* k8, const void* v8, const float* ks, const float* vs, void* ko, void* vo,

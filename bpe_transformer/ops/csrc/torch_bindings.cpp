@@ -1196,6 +1196,150 @@ at::Tensor cache_attn_fp8(const at::Tensor& q, const at::Tensor& k8, const at::T
     return out;
 }
 
+// ---- packed prefill (kv_cache.h PackedMap): the N rows of q / qkv are the prompts of S sequences end to end.  `seq`
+// is the device int32 table [S, 3] of (slot, off, n) the kernels read; `seq_host` is the host's copy of it (3 S ints),
+// which is what is checked here -- slots distinct and inside the cache's B slots, n >= 1, offs the running sum, N in
+// all -- so no launch waits for a read-back.  (The kernels clamp what they read from the device copy all the same.)
+KvPacked check_packed(const char* op, const at::Tensor& seq, at::IntArrayRef seq_host, int64_t N, int64_t B) {
+    check_cuda(seq, "seq");
+    TORCH_CHECK(seq.scalar_type() == at::kInt && seq.dim() == 2 && seq.size(1) == 3 && seq.is_contiguous() &&
+                    seq.size(0) >= 1,
+                op, ": seq must be a contiguous device int32 [S, 3] tensor of (slot, off, n)");
+    const int64_t S = seq.size(0);
+    TORCH_CHECK((int64_t)seq_host.size() == 3 * S, op, ": seq_host must hold the 3 * S ints of seq");
+    TORCH_CHECK(N >= 1 && N < (1LL << 24) && B >= 1 && B < (1LL << 31), op, ": 1 <= N < 2^24 packed rows");
+    std::vector<char> seen((size_t)B, 0);
+    int64_t off = 0;
+    for (int64_t i = 0; i < S; ++i) {
+        const int64_t slot = seq_host[3 * i], o = seq_host[3 * i + 1], n = seq_host[3 * i + 2];
+        TORCH_CHECK(slot >= 0 && slot < B, op, ": slot ", slot, " of sequence ", i, " is outside the cache's ", B,
+                    " slots");
+        TORCH_CHECK(!seen[(size_t)slot], op, ": slot ", slot, " is named twice");
+        seen[(size_t)slot] = 1;
+        TORCH_CHECK(n >= 1 && o == off, op, ": sequence ", i, " needs n >= 1 and off = the sum of the lengths before it");
+        off += n;
+    }
+    TORCH_CHECK(off == N, op, ": the lengths in seq sum to ", off, ", q / qkv has ", N, " rows");
+    KvPacked pk;
+    pk.seq = seq.data_ptr<int>();
+    pk.S = (int)S;
+    pk.N = (int)N;
+    return pk;
+}
+
+// kv_append / kv_append_fp8 on packed rows: token t of sequence i is rotated at and written to position pos[slot_i] + t
+// of slot slot_i (dropped at or past Lmax); returns the roped q [N, H*D].  pos is the cache's per-slot [B].
+at::Tensor kv_append_packed_impl(const char* op, const at::Tensor& qkv, at::Tensor& kc, at::Tensor& vc, at::Tensor* ks,
+                                 at::Tensor* vs, const at::Tensor& cos, const at::Tensor& sin, const at::Tensor& pos,
+                                 const at::Tensor& seq, at::IntArrayRef seq_host, int64_t H, bool use_rope,
+                                 const c10::optional<at::Tensor>& table, int64_t max_len) {
+    const KvGeom kg = kv_geom(op, kc, table, max_len);
+    const int64_t B = kg.B, Hkv = kg.Hkv, Lmax = kg.Lmax, D = kg.D;
+    TORCH_CHECK(Lmax < (1LL << 30), op, ": Lmax below 2^30");
+    if (ks != nullptr) {
+        TORCH_CHECK((D == 64 || D == 128) && Hkv > 0 && H % Hkv == 0, op, ": head dim 64/128, H multiple of Hkv");
+    } else {
+        TORCH_CHECK(D % 8 == 0 && Hkv > 0 && H % Hkv == 0, op, ": head dim multiple of 8, H multiple of Hkv");
+    }
+    TORCH_CHECK(qkv.dim() == 2, op, ": qkv must be [N, (H + 2*Hkv)*D]");
+    const int64_t N = qkv.size(0);
+    check_qkv(qkv, N, (H + 2 * Hkv) * D, "qkv");
+    check_kv(kc, vc, ks, vs, kg.dim0(B), Hkv, op);
+    TORCH_CHECK(check_pos(pos, B) == 1 || B == 1, op, ": pos must hold one position per slot");
+    const KvPacked pk = check_packed(op, seq, seq_host, N, B);
+    if (use_rope)
+        TORCH_CHECK(cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
+                        sin.is_contiguous() && cos.size(0) >= Lmax && cos.size(1) == D / 2 && sin.sizes() == cos.sizes(),
+                    op, ": rope tables must be fp32 [>=Lmax, D/2]");
+    DevGuard g(qkv.device());
+    auto q = at::empty({N, H * D}, qkv.options());
+    const float* c = use_rope ? cos.data_ptr<float>() : nullptr;
+    const float* sn = use_rope ? sin.data_ptr<float>() : nullptr;
+    if (ks != nullptr)
+        launch_kv_append_packed_fp8(qkv.data_ptr(), qkv.stride(0), q.data_ptr(), kc.data_ptr(), vc.data_ptr(),
+                                    ks->data_ptr<float>(), vs->data_ptr<float>(), c, sn, pos.data_ptr<int>(), pk,
+                                    (int)B, (int)H, (int)Hkv, (int)D, (int)Lmax, cur_stream(), kg.pg);
+    else
+        launch_kv_append_packed(qkv.data_ptr(), qkv.stride(0), q.data_ptr(), kc.data_ptr(), vc.data_ptr(), c, sn,
+                                pos.data_ptr<int>(), pk, (int)B, (int)H, (int)Hkv, (int)D, (int)Lmax, cur_stream(),
+                                kg.pg);
+    return q;
+}
+
+at::Tensor kv_append_packed(const at::Tensor& qkv, at::Tensor kc, at::Tensor vc, const at::Tensor& cos,
+                            const at::Tensor& sin, const at::Tensor& pos, const at::Tensor& seq,
+                            at::IntArrayRef seq_host, int64_t H, bool use_rope,
+                            const c10::optional<at::Tensor>& block_table, int64_t max_len) {
+    return kv_append_packed_impl("kv_append_packed", qkv, kc, vc, nullptr, nullptr, cos, sin, pos, seq, seq_host, H,
+                                 use_rope, block_table, max_len);
+}
+
+at::Tensor kv_append_packed_fp8(const at::Tensor& qkv, at::Tensor k8, at::Tensor v8, at::Tensor ks, at::Tensor vs,
+                                const at::Tensor& cos, const at::Tensor& sin, const at::Tensor& pos,
+                                const at::Tensor& seq, at::IntArrayRef seq_host, int64_t H, bool use_rope,
+                                const c10::optional<at::Tensor>& block_table, int64_t max_len) {
+    return kv_append_packed_impl("kv_append_packed_fp8", qkv, k8, v8, &ks, &vs, cos, sin, pos, seq, seq_host, H,
+                                 use_rope, block_table, max_len);
+}
+
+// cache_attn / cache_attn_fp8 on packed rows (already appended): q [N, H*D] -> [N, H*D]; token t of sequence i sees
+// keys 0 .. min(pos[slot_i] + t, Lmax - 1) of slot slot_i.  `work`: the device int32 list [W, 2] of (sequence, 128-row
+// query block) items, one per block of G * n_i rows of every sequence, heaviest first.
+at::Tensor cache_attn_packed_impl(const char* op, const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc,
+                                  const at::Tensor* ks, const at::Tensor* vs, const at::Tensor& pos,
+                                  const at::Tensor& seq, at::IntArrayRef seq_host, const at::Tensor& work, int64_t H,
+                                  double scale, const c10::optional<at::Tensor>& table, int64_t max_len) {
+    const KvGeom kg = kv_geom(op, kc, table, max_len);
+    const int64_t B = kg.B, Hkv = kg.Hkv, Lmax = kg.Lmax, D = kg.D;
+    check_cuda(q, "q");
+    TORCH_CHECK(q.scalar_type() == at::kBFloat16 && q.is_contiguous() && q.dim() == 2 && q.size(0) >= 1 &&
+                    q.size(1) == H * D,
+                op, ": q must be contiguous bf16 [N, H*D]");
+    const int64_t N = q.size(0);
+    TORCH_CHECK(H > 0 && H < (1 << 16) && N < (1 << 24) && Lmax < (1LL << 31) &&
+                    (ks != nullptr ? cache_attn_fp8_ok((int)H, (int)Hkv, (int)D, (int)N, (int)Lmax)
+                                   : cache_attn_ok((int)H, (int)Hkv, (int)D, (int)N, (int)Lmax)),
+                op, ": head dim 64/128, H a multiple of Hkv with H / Hkv <= 8 and a cache slab below 2 GiB required");
+    check_kv(kc, vc, ks, vs, kg.dim0(B), Hkv, op);
+    TORCH_CHECK(check_pos(pos, B) == 1 || B == 1, op, ": pos must hold one position per slot");
+    KvPacked pk = check_packed(op, seq, seq_host, N, B);
+    int64_t W = 0;
+    for (int i = 0; i < pk.S; ++i) W += ((H / Hkv) * seq_host[3 * i + 2] + 127) / 128;
+    check_cuda(work, "work");
+    TORCH_CHECK(work.scalar_type() == at::kInt && work.dim() == 2 && work.size(1) == 2 && work.is_contiguous() &&
+                    work.size(0) == W,
+                op, ": work must be a contiguous device int32 [W, 2] tensor with one (sequence, block) item per 128 "
+                "rows of every sequence (", W, " items)");
+    TORCH_CHECK(W * Hkv < (1LL << 31), op, ": too many workgroups");
+    pk.work = work.data_ptr<int>();
+    pk.W = (int)W;
+    DevGuard g(q.device());
+    auto out = at::empty({N, H * D}, q.options());
+    if (ks != nullptr)
+        launch_cache_attn_packed_fp8(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), ks->data_ptr<float>(),
+                                     vs->data_ptr<float>(), out.data_ptr(), pos.data_ptr<int>(), pk, (int)B, (int)H,
+                                     (int)Hkv, (int)D, (int)Lmax, (float)scale, cur_stream(), kg.pg);
+    else
+        launch_cache_attn_packed(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), out.data_ptr(), pos.data_ptr<int>(), pk,
+                                 (int)B, (int)H, (int)Hkv, (int)D, (int)Lmax, (float)scale, cur_stream(), kg.pg);
+    return out;
+}
+
+at::Tensor cache_attn_packed(const at::Tensor& q, const at::Tensor& kc, const at::Tensor& vc, const at::Tensor& pos,
+                             const at::Tensor& seq, at::IntArrayRef seq_host, const at::Tensor& work, int64_t H,
+                             double scale, const c10::optional<at::Tensor>& block_table, int64_t max_len) {
+    return cache_attn_packed_impl("cache_attn_packed", q, kc, vc, nullptr, nullptr, pos, seq, seq_host, work, H, scale,
+                                  block_table, max_len);
+}
+
+at::Tensor cache_attn_packed_fp8(const at::Tensor& q, const at::Tensor& k8, const at::Tensor& v8, const at::Tensor& ks,
+                                 const at::Tensor& vs, const at::Tensor& pos, const at::Tensor& seq,
+                                 at::IntArrayRef seq_host, const at::Tensor& work, int64_t H, double scale,
+                                 const c10::optional<at::Tensor>& block_table, int64_t max_len) {
+    return cache_attn_packed_impl("cache_attn_packed_fp8", q, k8, v8, &ks, &vs, pos, seq, seq_host, work, H, scale,
+                                  block_table, max_len);
+}
+
 // rows [0, min(pos[b] + T, Lmax)) of every K and V slab -> bf16 k_out / v_out [B, Hkv, Lmax, D]; other rows untouched
 void kv_dequant(const at::Tensor& k8, const at::Tensor& v8, const at::Tensor& ks, const at::Tensor& vs,
                 const at::Tensor& pos, int64_t T, at::Tensor k_out, at::Tensor v_out) {
@@ -1884,6 +2028,16 @@ TORCH_LIBRARY(bpe_hip, m) {
           "Tensor? block_table=None, int max_len=0) -> Tensor");
     m.def("cache_attn_fp8(Tensor q, Tensor k8, Tensor v8, Tensor k_scale, Tensor v_scale, Tensor pos, int H, "
           "float scale, int T, Tensor? block_table=None, int max_len=0) -> Tensor");
+    m.def("kv_append_packed(Tensor qkv, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor cos, Tensor sin, Tensor pos, "
+          "Tensor seq, int[] seq_host, int H, bool rope, Tensor? block_table=None, int max_len=0) -> Tensor");
+    m.def("kv_append_packed_fp8(Tensor qkv, Tensor(a!) k8, Tensor(b!) v8, Tensor(c!) k_scale, Tensor(d!) v_scale, "
+          "Tensor cos, Tensor sin, Tensor pos, Tensor seq, int[] seq_host, int H, bool use_rope, "
+          "Tensor? block_table=None, int max_len=0) -> Tensor");
+    m.def("cache_attn_packed(Tensor q, Tensor k_cache, Tensor v_cache, Tensor pos, Tensor seq, int[] seq_host, "
+          "Tensor work, int H, float scale, Tensor? block_table=None, int max_len=0) -> Tensor");
+    m.def("cache_attn_packed_fp8(Tensor q, Tensor k8, Tensor v8, Tensor k_scale, Tensor v_scale, Tensor pos, "
+          "Tensor seq, int[] seq_host, Tensor work, int H, float scale, Tensor? block_table=None, int max_len=0) -> "
+          "Tensor");
     m.def("rmsnorm_fwd(Tensor x, Tensor w, float eps) -> (Tensor, Tensor)");
     m.def("add_rmsnorm_fwd(Tensor x, Tensor d, Tensor w, float eps) -> (Tensor, Tensor, Tensor)");
     m.def("rmsnorm_bwd(Tensor dy, Tensor x, Tensor w, Tensor rstd, Tensor? dres=None, Tensor(a!)? dw_acc=None) -> "
@@ -1991,6 +2145,10 @@ TORCH_LIBRARY_IMPL(bpe_hip, CUDA, m) {
     m.impl("decode_attn", &decode_attn);
     m.impl("cache_attn", &cache_attn);
     m.impl("cache_attn_fp8", &cache_attn_fp8);
+    m.impl("kv_append_packed", &kv_append_packed);
+    m.impl("kv_append_packed_fp8", &kv_append_packed_fp8);
+    m.impl("cache_attn_packed", &cache_attn_packed);
+    m.impl("cache_attn_packed_fp8", &cache_attn_packed_fp8);
     m.impl("decode_gemv", &decode_gemv);
     m.impl("decode_qkv", &decode_qkv);
     m.impl("decode_attn_proj", &decode_attn_proj);

@@ -70,6 +70,18 @@ P)`` writes nothing to the pool.  A paged call gives, bit for bit, what the slab
 :func:`paged_gather` of the pool -- a page is ``decode_attn``'s 256-key chunk and four of ``cache_attn``'s 64-key
 tiles, so only the row addresses differ -- and the CPU oracles are defined that way: the slab reference on the
 gathered slab, appends scattered back (:func:`paged_scatter`).  :func:`kv_dequant` stays slab-only.
+
+**Packed prefill** (``csrc/kv_cache.h``: ``PackedMap``).  :func:`kv_append_packed` / :func:`prefill_attention_packed`
+(and their ``_fp8`` forms) take the prompts of several sequences in one launch: ``qkv`` / ``q`` are ``[N, ...]`` with
+the ``n_i`` rows of sequence ``i`` laid end to end, no padding, and a :class:`PackedPrompts` says where each goes --
+per sequence ``(slot_i, off_i, n_i)``: the cache slot (row of ``pos``, of the slab batch and of the block table), its
+first packed row and its token count, as a device int32 table ``[S, 3]`` written by the host.  The slots are distinct,
+and ``pos`` is the cache's own per-slot ``[B]`` tensor, read on the device as ``pos[slot_i]``: token ``t`` of sequence
+``i`` is rotated at, written to and attends from position ``pos[slot_i] + t`` of slot ``slot_i``; slots not named are
+not touched.  The attention additionally takes a host-built work list ``[W, 2]`` of ``(sequence, 128-row query
+block)`` items, heaviest first; a sequence's blocks start at its own row 0, so each sequence's rows are, bit for bit,
+those of the unpacked op called on that slot alone.  The CPU references are defined that way: a loop over the
+sequences of the unpacked reference on the slot's slice.
 """
 
 from __future__ import annotations
@@ -237,6 +249,95 @@ def prefill_attention(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, 
         return ops().cache_attn(q.contiguous(), k_cache, v_cache, pos, n_heads, scale, n_new,
                                 *_pg(block_table, max_len))
     return decode_attention_reference(q, k_cache, v_cache, pos, n_heads, scale, n_new, block_table, max_len)
+
+
+# ------------------------------------------------------------------ packed prefill (csrc/kv_cache.h: PackedMap)
+class PackedPrompts:
+    """Where the rows of a packed call go (module docstring, "Packed prefill"): sequence ``i`` has ``lens[i]`` rows
+    from row ``offs[i]`` on and belongs to cache slot ``slots[i]`` (distinct).  ``seq`` is the device int32 table
+    ``[S, 3]`` of ``(slot, off, n)``, ``seq_host`` its flat host copy (the ops check that one, so no launch waits for
+    a read-back).  ``pos_host`` (optional): the host's mirror of ``pos[slots[i]]``, used only to order the attention's
+    work list heaviest first -- it changes the order workgroups start in, never a result."""
+
+    def __init__(self, slots, lens, device=None, pos_host=None):
+        self.slots, self.lens = [int(s) for s in slots], [int(n) for n in lens]
+        assert len(self.slots) == len(self.lens) >= 1, "one length per slot, at least one sequence"
+        assert len(set(self.slots)) == len(self.slots), "packed prefill: the slots must be distinct"
+        assert all(n >= 1 for n in self.lens) and all(s >= 0 for s in self.slots), "slots >= 0, lengths >= 1"
+        self.offs = [sum(self.lens[:i]) for i in range(len(self.lens))]
+        self.N = sum(self.lens)
+        self.pos_host = [0] * len(self.lens) if pos_host is None else [int(p) for p in pos_host]
+        self.seq_host = [x for t in zip(self.slots, self.offs, self.lens) for x in t]
+        self.device = torch.device("cpu") if device is None else torch.device(device)
+        self.seq = torch.tensor(self.seq_host, dtype=torch.int32).view(-1, 3).to(self.device)
+        self._work: dict[int, Tensor] = {}
+
+    def work_items(self, G: int) -> list[tuple[int, int]]:
+        """The attention's work list for ``G`` query heads per kv head: one ``(sequence, block)`` per 128 rows of the
+        ``G * n_i`` rows of every sequence, ordered by the keys the block's last row sees, descending."""
+        items = [(p + min((128 * qb + 127) // G, n - 1) + 1, i, qb)
+                 for i, (n, p) in enumerate(zip(self.lens, self.pos_host)) for qb in range((G * n + 127) // 128)]
+        items.sort(key=lambda t: -t[0])  # (stable: equal weights keep sequence / block order)
+        return [(i, qb) for _, i, qb in items]
+
+    def work(self, G: int) -> Tensor:
+        """:meth:`work_items` as the device int32 ``[W, 2]`` tensor the op takes (built once per ``G``)."""
+        if G not in self._work:
+            self._work[G] = torch.tensor(self.work_items(G), dtype=torch.int32).view(-1, 2).to(self.device)
+        return self._work[G]
+
+
+def _packed_loop(fn, packed: PackedPrompts, rows: Tensor, pos: Tensor, caches: tuple) -> Tensor:
+    """``fn(rows_i, *slot views, pos_i, n_i)`` for each sequence of ``packed`` on its slot's one-row views of the slab
+    ``caches`` (views: written in place) and its one-element ``pos``; the results concatenated in packed order."""
+    out = []
+    for s, o, n in zip(packed.slots, packed.offs, packed.lens):
+        out.append(fn(rows[o : o + n], *[c[s : s + 1] for c in caches], pos.reshape(-1)[s : s + 1], n))
+    return torch.cat(out)
+
+
+def kv_append_packed(qkv: Tensor, k_cache: Tensor, v_cache: Tensor, cos: Tensor | None, sin: Tensor | None,
+                     pos: Tensor, packed: PackedPrompts, n_heads: int, block_table: Tensor | None = None,
+                     max_len: int | None = None) -> Tensor:
+    """:func:`kv_append` of the packed rows ``qkv [N, (H + 2 Hkv) D]``: sequence ``i``'s ``n_i`` tokens go to slot
+    ``slots[i]`` at positions ``pos[slot] ..``; returns the roped ``q [N, H*D]``.  ``pos`` is the per-slot ``[B]``."""
+    if qkv.is_cuda:
+        c, s, use_rope = _rope_args(qkv, cos, sin)
+        return ops().kv_append_packed(qkv, k_cache, v_cache, c, s, pos, packed.seq, packed.seq_host, n_heads, use_rope,
+                                      *_pg(block_table, max_len))
+    return kv_append_packed_reference(qkv, k_cache, v_cache, cos, sin, pos, packed, n_heads, block_table, max_len)
+
+
+def kv_append_packed_reference(qkv, k_cache, v_cache, cos, sin, pos, packed, n_heads, block_table=None,
+                               max_len=None) -> Tensor:
+    if block_table is not None:
+        return _on_slab(lambda k, v: kv_append_packed_reference(qkv, k, v, cos, sin, pos, packed, n_heads),
+                        (k_cache, v_cache), block_table, max_len, write=True)
+    return _packed_loop(lambda x, k, v, p, n: kv_append_reference(x, k, v, cos, sin, p, 1, n, n_heads),
+                        packed, qkv, pos, (k_cache, v_cache))
+
+
+def prefill_attention_packed(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, packed: PackedPrompts,
+                             n_heads: int, scale: float | None = None, block_table: Tensor | None = None,
+                             max_len: int | None = None) -> Tensor:
+    """:func:`prefill_attention` of the packed rows ``q [N, H*D]`` (already appended by :func:`kv_append_packed`, with
+    ``pos`` not yet advanced): token ``t`` of sequence ``i`` sees keys ``0 .. pos[slot_i] + t`` of its slot.  Each
+    sequence's rows are bit for bit those of :func:`prefill_attention` on its slot alone."""
+    scale = _scale(k_cache, scale)
+    if q.is_cuda:
+        G = n_heads // k_cache.shape[1]
+        return ops().cache_attn_packed(q.contiguous(), k_cache, v_cache, pos, packed.seq, packed.seq_host,
+                                       packed.work(G), n_heads, scale, *_pg(block_table, max_len))
+    return prefill_attention_packed_reference(q, k_cache, v_cache, pos, packed, n_heads, scale, block_table, max_len)
+
+
+def prefill_attention_packed_reference(q, k_cache, v_cache, pos, packed, n_heads, scale=None, block_table=None,
+                                       max_len=None) -> Tensor:
+    if block_table is not None:
+        return _on_slab(lambda k, v: prefill_attention_packed_reference(q, k, v, pos, packed, n_heads, scale),
+                        (k_cache, v_cache), block_table, max_len)
+    return _packed_loop(lambda x, k, v, p, n: decode_attention_reference(x, k, v, p, n_heads, scale, n),
+                        packed, q, pos, (k_cache, v_cache))
 
 
 def decode_attention_partials(q: Tensor, k_cache: Tensor, v_cache: Tensor, pos: Tensor, n_heads: int,
@@ -449,6 +550,53 @@ def prefill_attention_fp8(q: Tensor, k8: Tensor, v8: Tensor, k_scale: Tensor, v_
                                     *_pg(block_table, max_len))
     return decode_attention_fp8_reference(q, k8, v8, k_scale, v_scale, pos, n_heads, scale, n_new, block_table,
                                           max_len)
+
+
+def kv_append_packed_fp8(qkv: Tensor, k8: Tensor, v8: Tensor, k_scale: Tensor, v_scale: Tensor, cos: Tensor | None,
+                         sin: Tensor | None, pos: Tensor, packed: PackedPrompts, n_heads: int,
+                         block_table: Tensor | None = None, max_len: int | None = None) -> Tensor:
+    """:func:`kv_append_packed` into an fp8 cache (the rows quantised as :func:`kv_append_fp8` does); the same ``q``."""
+    if qkv.is_cuda:
+        c, s, use_rope = _rope_args(qkv, cos, sin)
+        return ops().kv_append_packed_fp8(qkv, k8, v8, k_scale, v_scale, c, s, pos, packed.seq, packed.seq_host,
+                                          n_heads, use_rope, *_pg(block_table, max_len))
+    return kv_append_packed_fp8_reference(qkv, k8, v8, k_scale, v_scale, cos, sin, pos, packed, n_heads, block_table,
+                                          max_len)
+
+
+def kv_append_packed_fp8_reference(qkv, k8, v8, k_scale, v_scale, cos, sin, pos, packed, n_heads, block_table=None,
+                                   max_len=None) -> Tensor:
+    if block_table is not None:
+        return _on_slab(lambda k, v, ks, vs: kv_append_packed_fp8_reference(qkv, k, v, ks, vs, cos, sin, pos, packed,
+                                                                            n_heads),
+                        (k8, v8, k_scale, v_scale), block_table, max_len, write=True)
+    return _packed_loop(lambda x, k, v, ks, vs, p, n: kv_append_fp8_reference(x, k, v, ks, vs, cos, sin, p, 1, n,
+                                                                              n_heads),
+                        packed, qkv, pos, (k8, v8, k_scale, v_scale))
+
+
+def prefill_attention_packed_fp8(q: Tensor, k8: Tensor, v8: Tensor, k_scale: Tensor, v_scale: Tensor, pos: Tensor,
+                                 packed: PackedPrompts, n_heads: int, scale: float | None = None,
+                                 block_table: Tensor | None = None, max_len: int | None = None) -> Tensor:
+    """:func:`prefill_attention_packed` over an fp8 cache, the e4m3 rows and their scales read as stored."""
+    scale = _scale(k8, scale)
+    if q.is_cuda:
+        G = n_heads // k8.shape[1]
+        return ops().cache_attn_packed_fp8(q.contiguous(), k8, v8, k_scale, v_scale, pos, packed.seq, packed.seq_host,
+                                           packed.work(G), n_heads, scale, *_pg(block_table, max_len))
+    return prefill_attention_packed_fp8_reference(q, k8, v8, k_scale, v_scale, pos, packed, n_heads, scale,
+                                                  block_table, max_len)
+
+
+def prefill_attention_packed_fp8_reference(q, k8, v8, k_scale, v_scale, pos, packed, n_heads, scale=None,
+                                           block_table=None, max_len=None) -> Tensor:
+    if block_table is not None:
+        return _on_slab(lambda k, v, ks, vs: prefill_attention_packed_fp8_reference(q, k, v, ks, vs, pos, packed,
+                                                                                    n_heads, scale),
+                        (k8, v8, k_scale, v_scale), block_table, max_len)
+    return _packed_loop(lambda x, k, v, ks, vs, p, n: decode_attention_fp8_reference(x, k, v, ks, vs, p, n_heads,
+                                                                                     scale, n),
+                        packed, q, pos, (k8, v8, k_scale, v_scale))
 
 
 def decode_attention_partials_fp8(q: Tensor, k8: Tensor, v8: Tensor, k_scale: Tensor, v_scale: Tensor, pos: Tensor,
